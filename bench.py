@@ -1,12 +1,21 @@
 #!/usr/bin/env python3
 """bench.py — FLASH / FLASH-BS Viterbi decode throughput on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline]]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
 One "step" = one complete decode of the workload, model tables already resident in HBM (fv_set_model is
 outside the timed region; the observation upload and the path download, a few KB, are inside it).
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, roofline of the
+timed steps).  --full adds everything that takes runs of its own: the N > 1 single-rank check, single_pass_mode_ms,
+sparse_walk, cfg2's flash_bs extra and cpu_baseline (unless --no-cpu-baseline).
+
+--dump-outputs DIR (rank 0): what the last timed step returned, as float64 arrays DIR/path.npy (the decoded
+state per observation, -1 where a beam decode missed), DIR/score.npy (the final score, shape (1,)) and DIR/rc.npy
+(the return code, shape (1,)).  The inputs are seeded: the same arguments give the same inputs on every run.
 
   cfg2 (default)  BASELINE configs[1]: full-state FLASH, K=3965 T=256 M=50 prob=0.112 seed=12 n_split=8,
                   FV_MODE_REFERENCE (the reference's divide-and-conquer task tree replayed pass for pass)
@@ -23,7 +32,7 @@ runs the whole-sequence pass, one RCCL all-gather merges the path slices (includ
 fv_comm_init).  Same total work for every N => "scaling": "strong".  The whole-sequence pass is serial in
 T, so the curve is Amdahl-bound (Multi-GPU).
 
-cpu_baseline (rank 0, N = 1 only): SURVEY 8(d)'s protocol for the bench configuration — the reference
+cpu_baseline (--full, rank 0, N = 1 only): SURVEY 8(d)'s protocol for the bench configuration — the reference
 program itself (oracle/_ref, built from the reference's sources with run.py:54's flags), MAX_THREADS =
 n_split, on the FULL cfg2 sequence, 1 warm + 3 timed runs of its own `time:` line, median; plus one
 MAX_THREADS=1 run on a T=16 sample.  `cores` = physical cores of this host, `threads` = what the program
@@ -256,13 +265,19 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and figures that take runs of their own (sparse_walk, flash_bs, cpu_baseline, ...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's path / score / rc as float64 .npy files into DIR")
     args = ap.parse_args()
     w = WORKLOADS[args.workload]
     if args.steps is None:
         args.steps = w["steps"]
     if args.warmup is None:
         args.warmup = w["warmup"]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     K, T, beam = w["K"], w["T"], w["beam"]
     is_beam = w["kind"] == "beam"
 
@@ -306,7 +321,7 @@ def main():
 
     fv = new_decoder()
     single_rank_path = None
-    if dist is not None and world > 1:
+    if args.full and dist is not None and world > 1:
         # before the context is partitioned: the whole decode on this rank alone, to check the merged result against
         single_rank_path = (fv.decode_beam(ob, N_SPLIT, beam, decoder.MODE_REFERENCE) if is_beam
                             else fv.decode_full(ob, N_SPLIT, decoder.MODE_REFERENCE))[0].tolist()
@@ -390,6 +405,10 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     st = fv.stats()
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in (("path", path), ("score", [score]), ("rc", [rc])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(arr, dtype=np.float64))
 
     # Roofline of the dominant kernel: the step of the whole-sequence pass (T-1 dependent steps per decode).
     #   full-state: one trellis_step launch per step, 4*K*K algorithmic bytes (4 B per trellis cell);
@@ -420,7 +439,7 @@ def main():
         roofline["heaviest_by_total_time"] = heaviest_kernel(None)
 
     extra = {}
-    if not is_beam:
+    if args.full and not is_beam:
         fv.decode_full(ob, N_SPLIT, decoder.MODE_SINGLE_PASS)
         extra["single_pass_mode_ms"] = fv.stats()["gpu_ms"]
         # the library's AUTO kernel for this model (sparse walk over the non-zero transitions)
@@ -484,7 +503,7 @@ def main():
             "roofline": roofline,
         }
         line.update(extra)
-        if args.gpus == 1 and args.workload == "cfg2":
+        if args.full and args.gpus == 1 and args.workload == "cfg2":
             # extra: the FLASH-BS variant on the same model (never part of `value`)
             BEAM = 256
             fv.decode_beam(ob, N_SPLIT, BEAM)
@@ -506,7 +525,7 @@ def main():
                                                         "path_equal_to_hip": bool(bpath == hp.tolist())}
                 except (FileNotFoundError, OSError, RuntimeError) as e:
                     line["flash_bs"]["cpu_baseline"] = f"not run: {type(e).__name__}"
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             if is_beam:
                 line["cpu_baseline"] = cpu_baseline_beam(w, model64, ob, fv, (A, B, Pi))
             elif model64 is None:

@@ -1,16 +1,16 @@
 """Builds profiles/r03_pmc_summary.csv and profiles/traffic.json from the rocprofv3 --pmc passes that
-tools/prof_bench.sh leaves under gpurun_out/pmc{1,2,3}/ (default workload) and gpurun_out/bpmc{1,2,3}/ (cfg4 FLASH-BS):
+tools/prof_bench.sh leaves under prof_out/pmc{1,2,3}/ (default workload) and prof_out/bpmc{1,2,3}/ (cfg4 FLASH-BS):
 FETCH_SIZE; WRITE_SIZE; TCC_HIT_sum + TCC_MISS_sum.  Runs anywhere (no GPU)."""
 import csv, datetime, glob, json, os, re, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rows = {}
 for d in ("pmc1", "pmc2", "pmc3", "bpmc1", "bpmc2", "bpmc3"):
-    for path in glob.glob(os.path.join(ROOT, "gpurun_out", d, "**", "*counter_collection.csv"), recursive=True):
+    for path in glob.glob(os.path.join(ROOT, "prof_out", d, "**", "*counter_collection.csv"), recursive=True):
         with open(path) as f:
             for r in csv.DictReader(f):
                 rows.setdefault((r["Kernel_Name"], r["Counter_Name"]), []).append(float(r["Counter_Value"]))
 if not rows:
-    sys.exit("no counter_collection.csv under gpurun_out/pmc*/")
+    sys.exit("no counter_collection.csv under prof_out/pmc*/")
 out = os.path.join(ROOT, "profiles", "r03_pmc_summary.csv")
 with open(out, "w") as f:
     f.write("kernel,counter,dispatches,mean,median,min,max\n")

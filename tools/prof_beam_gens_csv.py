@@ -1,7 +1,7 @@
 """Per-generation break-down of the last complete decode in a rocprofv3 kernel trace (CSV) of a FLASH-BS bench run:
-   python tools/prof_beam_gens_csv.py [gpurun_out/prof_cfg4/beam_kernel_trace.csv]   — select and step durations per lock-step"""
+   python tools/prof_beam_gens_csv.py [prof_out/prof_cfg4/beam_kernel_trace.csv]   — select and step durations per lock-step"""
 import csv, sys
-path = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/prof_cfg4/beam_kernel_trace.csv"
+path = sys.argv[1] if len(sys.argv) > 1 else "prof_out/prof_cfg4/beam_kernel_trace.csv"
 rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
 names = [r["Kernel_Name"] for r in rows]
 dur = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows]
