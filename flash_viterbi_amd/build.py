@@ -61,7 +61,7 @@ def build_hip(force=False, timing=False):
     from concurrent.futures import ThreadPoolExecutor
     lib = HIP_TIMING_LIB if timing else HIP_LIB
     src = [os.path.join(CSRC, s) for s in HIP_SOURCES]
-    deps = src + [os.path.join(CSRC, d) for d in HIP_DEPS] + [os.path.join(INCLUDE, "flashvit.h")]
+    deps = src + [os.path.join(CSRC, d) for d in HIP_DEPS] + [os.path.join(INCLUDE, h) for h in ("flashvit.h", "flashvit_testing.h")]
     if not force and _newer(lib, deps):
         return lib
     objdir = OBJ_DIR + ("_timing" if timing else "")

@@ -2,6 +2,7 @@
 #include "fv_internal.h"
 #include "fv_device_common.h"
 #include "fv_beam_kernels.hip.inc"
+#include "flashvit_testing.h"
 
 namespace {
 int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_width, int mode, int *path_out, float *score_out);
@@ -23,6 +24,43 @@ inline int beam_groups(const fv_ctx *ctx, int np, int beam)
     if ((ctx->opt_debug & 65536) || np < 2) return 1;            // FV_OPT_DEBUG bit 16: one stream
     if (!(ctx->opt_debug & 131072) && (double)beam * ctx->K < 16e6) return 1;
     return std::min(1 + fv_ctx::BEAM_AUX, np);
+}
+
+// The step kernel of one beam launch: the one rule run_generation_beam and fv_test_beam_step share.
+int launch_beam_step(fv_ctx *ctx, const fvb::BeamStepArgs &a, hipStream_t st)
+{
+    const int K = ctx->K, beam = a.beam;
+    auto record = [&](unsigned long long bit) { if (ctx->test_record) ctx->test_variants |= bit; };
+    // The 16-bit filter kernel moves a quarter of the bytes but has two more dependent phases (window,
+    // float64 refine): measured at K = 16384, B = 256 it takes 13.7 us + 2.6 us per extra pass of the
+    // launch against 10.6 + 5.0 for the float64 kernel, so it is used from ~80 MB of float64 rows per
+    // launch on (cfg5: 537 MB per pass).  FV_OPT_DEBUG bit 8: never, bit 9: always.
+    const bool use_q16 = ctx->beam_q16_ready && !(ctx->opt_debug & 256) &&
+                         ((ctx->opt_debug & 512) || (double)a.n * beam * K * 8.0 >= 80e6);
+    // 8-wave workgroups once the launch has more 16-wave workgroups than fit the chip together (two per CU);
+    // FV_OPT_DEBUG bit 25: never, bit 26: always
+    const int panels = beam_ldq(K) / fvb::BEAMQ_COLS;
+    const bool narrow = !(ctx->opt_debug & (1 << 25)) &&
+                        ((ctx->opt_debug & (1 << 26)) || (long long)panels * a.n > 2LL * ctx->num_cus);
+    // (4-wave workgroups for launches beyond four 8-wave workgroups per CU: cfg4 right-hand 3.51 -> 3.56 ms, cfg5 95.8 -> 97.1)
+    if (use_q16 && narrow) {
+        record(FV_TV_BEAM_Q16_W8);
+        hipLaunchKernelGGL(fvb::beam_step_q16<8>, dim3(panels, a.n), dim3(8 * 64), fvb::beam_step_q16_lds(beam, 8), st, a);
+    } else if (use_q16) {
+        record(FV_TV_BEAM_Q16_W16);
+        hipLaunchKernelGGL(fvb::beam_step_q16<16>, dim3(panels, a.n), dim3(fvb::BEAM_BLOCK),
+                           fvb::beam_step_q16_lds(beam), st, a);
+    // (small beams: four waves per workgroup — K = 3965, B = 32: 4.55 -> 4.23 ms; eight waves at B = 256: 6.43 -> 6.50, not kept)
+    } else if (beam <= 64 && !(ctx->opt_debug & (1 << 25))) {
+        record(FV_TV_BEAM_W4);
+        hipLaunchKernelGGL(fvb::beam_step<4>, dim3(beam_ld(K) / fvb::BEAM_COLS, a.n), dim3(4 * 64), fvb::beam_step_lds(beam, 4), st, a);
+    } else {
+        record(FV_TV_BEAM_W16);
+        hipLaunchKernelGGL(fvb::beam_step<16>, dim3(beam_ld(K) / fvb::BEAM_COLS, a.n), dim3(fvb::BEAM_BLOCK), fvb::beam_step_lds(beam),
+                           st, a);
+    }
+    FV_HIP(hipGetLastError());
+    return 0;
 }
 
 int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t pass_off, int beam, int T)
@@ -119,30 +157,7 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
                     a.p[q].cut = ctx->d_cut.p + (size_t)(j - 1) * fvb::CUT_W;
                     a.p[q].dupwin = ctx->d_dupwin.p + j;
                 }
-                // The 16-bit filter kernel moves a quarter of the bytes but has two more dependent phases (window,
-                // float64 refine): measured at K = 16384, B = 256 it takes 13.7 us + 2.6 us per extra pass of the
-                // launch against 10.6 + 5.0 for the float64 kernel, so it is used from ~80 MB of float64 rows per
-                // launch on (cfg5: 537 MB per pass).  FV_OPT_DEBUG bit 8: never, bit 9: always.
-                const bool use_q16 = ctx->beam_q16_ready && !(ctx->opt_debug & 256) &&
-                                     ((ctx->opt_debug & 512) || (double)a.n * beam * K * 8.0 >= 80e6);
-                // 8-wave workgroups once the launch has more 16-wave workgroups than fit the chip together (two per CU);
-                // FV_OPT_DEBUG bit 25: never, bit 26: always
-                const int panels = beam_ldq(K) / fvb::BEAMQ_COLS;
-                const bool narrow = !(ctx->opt_debug & (1 << 25)) &&
-                                    ((ctx->opt_debug & (1 << 26)) || (long long)panels * a.n > 2LL * ctx->num_cus);
-                // (4-wave workgroups for launches beyond four 8-wave workgroups per CU: cfg4 right-hand 3.51 -> 3.56 ms, cfg5 95.8 -> 97.1)
-                if (use_q16 && narrow)
-                    hipLaunchKernelGGL(fvb::beam_step_q16<8>, dim3(panels, a.n), dim3(8 * 64), fvb::beam_step_q16_lds(beam, 8), st, a);
-                else if (use_q16)
-                    hipLaunchKernelGGL(fvb::beam_step_q16<16>, dim3(panels, a.n), dim3(fvb::BEAM_BLOCK),
-                                       fvb::beam_step_q16_lds(beam), st, a);
-                // (small beams: four waves per workgroup — K = 3965, B = 32: 4.55 -> 4.23 ms; eight waves at B = 256: 6.43 -> 6.50, not kept)
-                else if (beam <= 64 && !(ctx->opt_debug & (1 << 25)))
-                    hipLaunchKernelGGL(fvb::beam_step<4>, dim3(beam_ld(K) / fvb::BEAM_COLS, a.n), dim3(4 * 64), fvb::beam_step_lds(beam, 4), st, a);
-                else
-                    hipLaunchKernelGGL(fvb::beam_step<16>, dim3(beam_ld(K) / fvb::BEAM_COLS, a.n), dim3(fvb::BEAM_BLOCK), fvb::beam_step_lds(beam),
-                                       st, a);
-                FV_HIP(hipGetLastError());
+                if ((rc = launch_beam_step(ctx, a, st))) return rc;
                 ctx->stats.step_launches += 1;
                 ctx->stats.task_steps += a.n;
             }
@@ -244,20 +259,54 @@ extern "C" int fv_decode_beam(fv_ctx *ctx, const int *ob, int T, int n_split, in
 }
 
 namespace {
+// Beam widths the beam path takes: the admission fv_decode_beam and fv_test_beam_step share.
+int beam_admit(fv_ctx *ctx, int beam)
+{
+    // beam > K reads uninitialised heap slots in the reference (SURVEY App. A.4)
+    if (beam < 2 || beam > ctx->K) return FV_ERR_ARG;
+    if (fvb::beam_step_lds(beam) > 150 * 1024 || fvb::beam_step_q16_lds(beam) > 150 * 1024 ||
+        fvb::heap_lds(beam) > 150 * 1024) return FV_ERR_UNSUPPORTED;
+    return 0;
+}
+
+// The row-major tables of the beam step kernels (float64 LA64R, 16-bit LAQ16R and its parameters qpar), built on the
+// device by the first beam decode or test-hook call of a model.
+int beam_tables(fv_ctx *ctx)
+{
+    if (!ctx->LA64R.p) {
+        const int ld = beam_ld(ctx->K);
+        FV_HIP(ctx->LA64R.ensure((size_t)ctx->K * ld));
+        hipLaunchKernelGGL(fvb::relayout_rows, dim3(2048), dim3(256), 0, ctx->stream, ctx->LA64.p, ctx->LA64R.p, ctx->K, ctx->nrows, ld);
+        FV_HIP(hipGetLastError());
+    }
+    if (!ctx->beam_q16_ready && ctx->logs_nonpositive) {
+        // filter table of beam_step_q16, quantised on the device from LA64R
+        const int ld = beam_ld(ctx->K), ldq = beam_ldq(ctx->K);
+        FV_HIP(ctx->LAQ16R.ensure((size_t)ctx->K * ldq));
+        FV_HIP(ctx->d_qaux.ensure(3));
+        FV_HIP(hipMemsetAsync(ctx->d_qaux.p, 0, 3 * sizeof(unsigned long long), ctx->stream));
+        hipLaunchKernelGGL(fvb::q16_range, dim3(2048), dim3(256), 0, ctx->stream, ctx->LA64R.p, (size_t)ctx->K * ld, ctx->d_qaux.p);
+        hipLaunchKernelGGL(fvb::q16_rows, dim3(2048), dim3(256), 0, ctx->stream, ctx->LA64R.p, ctx->LAQ16R.p, ctx->K, ld, ldq,
+                           ctx->d_qaux.p, ctx->d_qaux.p + 1);
+        hipLaunchKernelGGL(fvb::q16_params, dim3(1), dim3(1), 0, ctx->stream, ctx->d_qaux.p, ctx->d_qaux.p + 1,
+                           reinterpret_cast<float *>(ctx->d_qaux.p + 2));
+        FV_HIP(hipGetLastError());
+        ctx->beam_q16_ready = true; ctx->rowq_ready = true;
+    }
+    return 0;
+}
+
 int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_width, int mode, int *path_out, float *score_out)
 {
     if (!ctx || !ob || !path_out || T < 2 || n_split < 1) return FV_ERR_ARG;
     if (ctx->K == 0) return FV_ERR_STATE;
-    // beam > K reads uninitialised heap slots in the reference (SURVEY App. A.4)
-    if (beam_width < 2 || beam_width > ctx->K) return FV_ERR_ARG;
-    if (fvb::beam_step_lds(beam_width) > 150 * 1024 || fvb::beam_step_q16_lds(beam_width) > 150 * 1024 ||
-        fvb::heap_lds(beam_width) > 150 * 1024) return FV_ERR_UNSUPPORTED;
+    int rc = beam_admit(ctx, beam_width);
+    if (rc) return rc;
     for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->M) return FV_ERR_ARG;
     auto t0 = clk::now();
     FV_HIP(hipSetDevice(ctx->device));
     fv::Plan plan;
-    int rc = fv::build_plan(T, n_split, mode, ctx->nranks, plan);
-    if (rc) return rc;
+    if ((rc = fv::build_plan(T, n_split, mode, ctx->nranks, plan))) return rc;
     std::vector<std::vector<fv::Pass>> gens(plan.generations());
     size_t most = 1;
     for (const fv::Pass &p : plan.passes)
@@ -282,26 +331,7 @@ int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_wi
     FV_HIP(ctx->d_dupwin.ensure(T));
     FV_HIP(ctx->d_needfull.ensure(4));
     FV_HIP(hipMemsetAsync(ctx->d_dupwin.p, 0, (size_t)T * sizeof(int), ctx->stream));
-    if (!ctx->LA64R.p) {
-        const int ld = beam_ld(ctx->K);
-        FV_HIP(ctx->LA64R.ensure((size_t)ctx->K * ld));
-        hipLaunchKernelGGL(fvb::relayout_rows, dim3(2048), dim3(256), 0, ctx->stream, ctx->LA64.p, ctx->LA64R.p, ctx->K, ctx->nrows, ld);
-        FV_HIP(hipGetLastError());
-    }
-    if (!ctx->beam_q16_ready && ctx->logs_nonpositive) {
-        // filter table of beam_step_q16, quantised on the device from LA64R
-        const int ld = beam_ld(ctx->K), ldq = beam_ldq(ctx->K);
-        FV_HIP(ctx->LAQ16R.ensure((size_t)ctx->K * ldq));
-        FV_HIP(ctx->d_qaux.ensure(3));
-        FV_HIP(hipMemsetAsync(ctx->d_qaux.p, 0, 3 * sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL(fvb::q16_range, dim3(2048), dim3(256), 0, ctx->stream, ctx->LA64R.p, (size_t)ctx->K * ld, ctx->d_qaux.p);
-        hipLaunchKernelGGL(fvb::q16_rows, dim3(2048), dim3(256), 0, ctx->stream, ctx->LA64R.p, ctx->LAQ16R.p, ctx->K, ld, ldq,
-                           ctx->d_qaux.p, ctx->d_qaux.p + 1);
-        hipLaunchKernelGGL(fvb::q16_params, dim3(1), dim3(1), 0, ctx->stream, ctx->d_qaux.p, ctx->d_qaux.p + 1,
-                           reinterpret_cast<float *>(ctx->d_qaux.p + 2));
-        FV_HIP(hipGetLastError());
-        ctx->beam_q16_ready = true; ctx->rowq_ready = true;
-    }
+    if ((rc = beam_tables(ctx))) return rc;
 
     const double keep_model_ms = ctx->stats.set_model_ms;
     ctx->stats = fv_stats{};
@@ -349,6 +379,116 @@ int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_wi
     return fvi::finish_decode(ctx, plan, T, path_out, score_out, t0, 0, true);
 }
 }  // namespace
+
+namespace {
+// fv_test_beam_step (include/flashvit_testing.h): one launch of the beam step kernel over caller-given slot sets.  Set q
+// plays step j = q: its slots, cut record, scores, back-pointers, doubt and candidate lists sit at index q of the
+// decode's own per-step buffers.
+int test_beam_step_impl(fv_ctx *ctx, int beam, const fv_test_beam_set *sets, int nsets, const int *sym, int speculative,
+                        float theta, float next_bound, int cand_cap, float *scores_out, int *bp_out, int *ties_out,
+                        int *tie_count_out, int *doubt_out, int *doubt_counts, fv_test_cand *cand_out, int *cand_counts,
+                        unsigned long long *variants_out)
+{
+    if (!sets || !sym || nsets < 1 || nsets > fvb::BEAM_CHUNK || !scores_out || !bp_out || !ties_out || !tie_count_out ||
+        !doubt_out || !doubt_counts || cand_cap < 0 || (cand_cap > 0 && (!cand_out || !cand_counts))) return FV_ERR_ARG;
+    if (ctx->K == 0) return FV_ERR_STATE;
+    int rc = beam_admit(ctx, beam);
+    if (rc) return rc;
+    const int K = ctx->K, BP = fvb::beam_pitch(beam);
+    // the kernels stage beam_pitch(beam) entries of every set, whatever its length: the rest is padding
+    std::vector<float> hv((size_t)nsets * BP, -HUGE_VALF), cut((size_t)nsets * fvb::CUT_W, 0.0f);
+    std::vector<int> hs((size_t)nsets * BP, 0);
+    for (int q = 0; q < nsets; ++q) {
+        const fv_test_beam_set &st = sets[q];
+        if (!st.val || !st.state || st.n < beam || st.n > BP || sym[q] < 0 || sym[q] >= ctx->M) return FV_ERR_ARG;
+        for (int e = 0; e < st.n; ++e) {
+            if (st.state[e] < 0 || st.state[e] >= K) return FV_ERR_ARG;
+            hv[(size_t)q * BP + e] = st.val[e];
+            hs[(size_t)q * BP + e] = st.state[e];
+        }
+        float *c = cut.data() + (size_t)q * fvb::CUT_W;
+        c[fvb::CUT_THETA] = theta;
+        c[fvb::CUT_STATE] = speculative ? 1.0f : 0.0f;
+        c[fvb::CUT_NEXT] = next_bound;
+        c[fvb::CUT_N] = (float)st.n;
+    }
+    FV_HIP(hipSetDevice(ctx->device));
+    if ((rc = beam_tables(ctx))) return rc;
+    FV_HIP(ctx->d_hval.ensure((size_t)nsets * BP));
+    FV_HIP(ctx->d_hstate.ensure((size_t)nsets * BP));
+    FV_HIP(ctx->d_cut.ensure((size_t)nsets * fvb::CUT_W));
+    FV_HIP(ctx->d_scores.ensure((size_t)nsets * K));
+    FV_HIP(ctx->d_bp.ensure((size_t)nsets * K));
+    FV_HIP(ctx->d_dupwin.ensure(nsets));
+    FV_HIP(ctx->d_doubt.ensure((size_t)nsets * fvb::DOUBT_CAP));
+    FV_HIP(ctx->d_doubt_count.ensure(nsets));
+    FV_HIP(ctx->d_tie_list.ensure((size_t)nsets * K));
+    FV_HIP(ctx->d_tie_count.ensure(4));
+    FV_HIP(ctx->d_counters.ensure(FV_NCOUNTERS));
+    FV_HIP(ctx->d_cand_count.ensure(nsets));
+    if (cand_cap) FV_HIP(ctx->d_cand.ensure((size_t)nsets * cand_cap));
+    FV_HIP(hipMemcpyAsync(ctx->d_hval.p, hv.data(), hv.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    FV_HIP(hipMemcpyAsync(ctx->d_hstate.p, hs.data(), hs.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    FV_HIP(hipMemcpyAsync(ctx->d_cut.p, cut.data(), cut.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_dupwin.p, 0, (size_t)nsets * sizeof(int), ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_doubt_count.p, 0, (size_t)nsets * sizeof(int), ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_cand_count.p, 0, (size_t)nsets * sizeof(int), ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_tie_count.p, 0, sizeof(unsigned int), ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_counters.p, 0, FV_NCOUNTERS * sizeof(unsigned long long), ctx->stream));
+    fvb::BeamStepArgs a;
+    a.LA64R = ctx->LA64R.p; a.tie_count = ctx->d_tie_count.p; a.tie_list = ctx->d_tie_list.p;
+    a.tie_cap = (unsigned int)ctx->d_tie_list.n;
+    a.counters = ctx->d_counters.p;
+    a.K = K; a.ld = beam_ld(K); a.ldq = beam_ldq(K); a.beam = beam;
+    a.LAQ16R = ctx->LAQ16R.p; a.qpar = ctx->beam_q16_ready ? reinterpret_cast<const float *>(ctx->d_qaux.p + 2) : nullptr;
+    a.cand = ctx->d_cand.p; a.cand_count = ctx->d_cand_count.p; a.cand_cap = cand_cap;
+    a.n = nsets;
+    for (int q = 0; q < nsets; ++q) {
+        a.p[q].sval = ctx->d_hval.p + (size_t)q * BP;
+        a.p[q].sstate = ctx->d_hstate.p + (size_t)q * BP;
+        a.p[q].doubt = ctx->d_doubt.p + (size_t)q * fvb::DOUBT_CAP;
+        a.p[q].doubt_count = ctx->d_doubt_count.p + q;
+        a.p[q].scores = ctx->d_scores.p + (size_t)q * K;
+        a.p[q].bp_row = ctx->d_bp.p + (size_t)q * K;
+        a.p[q].tmp_row = ctx->LB32T.p + (size_t)sym[q] * K;
+        a.p[q].j = q;
+        a.p[q].cut = ctx->d_cut.p + (size_t)q * fvb::CUT_W;
+        a.p[q].dupwin = ctx->d_dupwin.p + q;
+    }
+    struct Restore { fv_ctx *c; ~Restore() { c->test_record = false; } } restore{ ctx };
+    ctx->test_record = true;
+    ctx->test_variants = 0;
+    if ((rc = launch_beam_step(ctx, a, ctx->stream))) return rc;
+    unsigned int nties = 0;
+    FV_HIP(hipMemcpyAsync(scores_out, ctx->d_scores.p, (size_t)nsets * K * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    FV_HIP(hipMemcpyAsync(bp_out, ctx->d_bp.p, (size_t)nsets * K * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    FV_HIP(hipMemcpyAsync(&nties, ctx->d_tie_count.p, sizeof nties, hipMemcpyDeviceToHost, ctx->stream));
+    FV_HIP(hipMemcpyAsync(ties_out, ctx->d_tie_list.p, (size_t)nsets * K * sizeof(int2), hipMemcpyDeviceToHost, ctx->stream));
+    FV_HIP(hipMemcpyAsync(doubt_out, ctx->d_doubt.p, (size_t)nsets * fvb::DOUBT_CAP * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    FV_HIP(hipMemcpyAsync(doubt_counts, ctx->d_doubt_count.p, (size_t)nsets * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (cand_cap) {
+        static_assert(sizeof(fv_test_cand) == sizeof(fvb::HNode), "fv_test_cand mirrors HNode");
+        FV_HIP(hipMemcpyAsync(cand_out, ctx->d_cand.p, (size_t)nsets * cand_cap * sizeof(fvb::HNode), hipMemcpyDeviceToHost, ctx->stream));
+        FV_HIP(hipMemcpyAsync(cand_counts, ctx->d_cand_count.p, (size_t)nsets * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    FV_HIP(hipStreamSynchronize(ctx->stream));
+    *tie_count_out = (int)std::min<unsigned int>(nties, (unsigned int)(nsets * K));
+    if (variants_out) *variants_out = ctx->test_variants;
+    return FV_OK;
+}
+}  // namespace
+
+extern "C" int fv_test_beam_step(fv_ctx *ctx, int beam, const fv_test_beam_set *sets, int nsets, const int *sym, int speculative,
+                                 float theta, float next_bound, int cand_cap, float *scores_out, int *bp_out, int *ties_out,
+                                 int *tie_count_out, int *doubt_out, int *doubt_counts, fv_test_cand *cand_out, int *cand_counts,
+                                 unsigned long long *variants_out)
+{
+    if (!ctx) return FV_ERR_ARG;
+    if (fvi::group_size(ctx) > 1) { ctx->detail = "fv_test_beam_step: one device per context"; return FV_ERR_ARG; }
+    return fvi::drained(ctx, test_beam_step_impl(ctx, beam, sets, nsets, sym, speculative, theta, next_bound, cand_cap, scores_out,
+                                                 bp_out, ties_out, tie_count_out, doubt_out, doubt_counts, cand_out, cand_counts,
+                                                 variants_out));
+}
 
 #ifdef FV_REPLAY_PROF
 // Experiment builds only: read and reset the replay profile (fv_beam_kernels.hip.inc, replay_prof).

@@ -6,6 +6,7 @@
 // later pass consumes (Ans[L-1], Ans[R]) stays in device memory.  One sync at the end.
 #include "fv_internal.h"
 #include "fv_kernels.hip.inc"
+#include "flashvit_testing.h"
 
 namespace {
 
@@ -32,9 +33,34 @@ int pick_kernel(const fv_ctx *ctx)
 // evicted before they are re-read.  Kept behind FV_OPT_DEBUG bit 2 for experiments.
 constexpr int U_UP = 16, U_DB32 = 4, U_DB64 = 2, U_DB16 = 2;
 
+// FV_TV_* bit of each step-kernel instantiation (include/flashvit_testing.h), recorded by the launch helpers during a
+// test-hook call only.  U follows from the table type and DB.
+constexpr int nb_slot(int NB) { return NB == 1 ? 0 : NB == 2 ? 1 : NB == 4 ? 2 : 3; }
+template <typename TA> constexpr int tab_slot()
+{
+    return std::is_same<TA, double>::value ? 0 : std::is_same<TA, float>::value ? 1 : std::is_same<TA, fvk::half_t>::value ? 2 : 3;
+}
+template <typename TA, int NB, bool DB> constexpr unsigned long long step_variant()
+{
+    // per table type: the double-buffered forms (NB = 1, 2, 4, 8), then (all but float64) the whole-tile forms (NB = 1, 2)
+    return 1ull << ((tab_slot<TA>() == 0 ? 0 : 4 + (tab_slot<TA>() - 1) * 6) + (DB ? 0 : 4) + nb_slot(NB));
+}
+template <typename TA> constexpr unsigned long long slab_variant() { return 1ull << (22 + tab_slot<TA>()); }
+template <int NB, bool DB, int NWV> constexpr unsigned long long u16_variant()
+{
+    return 1ull << (26 + (NWV == 16 ? 0 : 8) + (DB ? 4 : 0) + nb_slot(NB));
+}
+template <int NB> constexpr unsigned long long sparse_variant() { return 1ull << (42 + nb_slot(NB)); }
+static_assert(step_variant<double, 8, true>() == FV_TV_F64_NB8 && step_variant<float, 2, false>() == FV_TV_F32_UP_NB2 &&
+              step_variant<fvk::half_t, 1, true>() == FV_TV_F16_NB1 && step_variant<fvk::q16_t, 2, false>() == FV_TV_Q16_UP_NB2 &&
+              slab_variant<fvk::q16_t>() == FV_TV_SLAB_Q16 && u16_variant<1, false, 16>() == FV_TV_U16_W16_UP_NB1 &&
+              u16_variant<8, true, 8>() == FV_TV_U16_W8_NB8 && sparse_variant<8>() == FV_TV_SPARSE_NB8,
+              "FV_TV_* bits of include/flashvit_testing.h");
+
 template <typename TA, int NB, int U, bool DB>
 int launch_variant(fv_ctx *ctx, const fvk::StepArgs<NB> &a, size_t lds)
 {
+    if (ctx->test_record) ctx->test_variants |= step_variant<TA, NB, DB>();
     hipLaunchKernelGGL((fvk::trellis_step<TA, NB, U, DB>), dim3(a.tiles_per_xcd * 8), dim3(fvk::BLOCK), lds, ctx->lstream ? ctx->lstream : ctx->stream, a);
     FV_HIP(hipGetLastError());
     return 0;
@@ -81,6 +107,7 @@ int launch_step_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb, int reverse)
     if (slab < ctx->nrows) {
         constexpr int U = std::is_same<TA, double>::value ? U_DB64 : std::is_same<TA, float>::value ? U_DB32 : U_DB16;
         a.reverse = 0;
+        if (ctx->test_record) ctx->test_variants |= slab_variant<TA>();
         for (int lo = 0; lo < ctx->nrows; lo += slab) {
             a.row_lo = lo; a.srows = std::min(slab, ctx->nrows - lo); a.merge = lo > 0 ? 1 : 0;
             const int rc = launch_variant<TA, NB, U, true>(ctx, a, fvk::step_lds_bytes<NB>(a.srows));
@@ -131,6 +158,7 @@ int launch_sparse_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb)
     a.nb = nb; a.debug = ctx->opt_debug;
     a.window = ctx->windowq; a.qscale = ctx->qscale;
     for (int t = 0; t < NB; ++t) a.t[t] = slots[t < nb ? t : 0];
+    if (ctx->test_record) ctx->test_variants |= sparse_variant<NB>();
     hipLaunchKernelGGL((fvk::trellis_step_sparse<NB>), dim3(a.tiles_per_xcd * 8), dim3(fvk::SP_BLOCK),
                        fvk::sparse_lds_bytes<NB>(ctx->nrows), ctx->lstream ? ctx->lstream : ctx->stream, a);
     FV_HIP(hipGetLastError());
@@ -149,6 +177,7 @@ template <int NB, int U, bool DB, int NWV>
 int launch_u16_variant(fv_ctx *ctx, const fvk::StepArgs<NB> &a)
 {
     const size_t lds = fvk::u16_lds_bytes<NB, NWV>(ctx->nrows);
+    if (ctx->test_record) ctx->test_variants |= u16_variant<NB, DB, NWV>();
     hipLaunchKernelGGL((fvk::trellis_step_u16<NB, U, DB, NWV>), dim3(a.tiles_per_xcd * 8), dim3(NWV * 64), lds, ctx->lstream ? ctx->lstream : ctx->stream, a);
     FV_HIP(hipGetLastError());
     return 0;
@@ -492,10 +521,12 @@ extern "C" int fv_decode_full(fv_ctx *ctx, const int *ob, int T, int n_split, in
 }
 
 namespace {
-int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, int *path_out, float *score_out)
+// What fv_decode_full and fv_test_forward do before their passes run, through this one path: admission of the kernel
+// choice for the model and of the sequence, the kernel choice itself, the 16-bit table of a model beyond the float32
+// kernels' limit (built on the device on first use) and the workspace for `rows_needed` passes in flight.  (The LDS
+// attributes of every step kernel, fvi::full_setup, are set once by fv_create.)
+int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &kernel)
 {
-    if (!ctx || !ob || !path_out || T < 2 || n_split < 1) return FV_ERR_ARG;
-    if (ctx->K == 0) return FV_ERR_STATE;
     // Beyond the float32 kernels' LDS limit (one score row of K floats) two routes remain:
     //   * the packed 16-bit kernel — a row of 16-bit score codes is half the bytes (K <= 65536); it needs every model entry
     //     in [0,1], and its table is built on the device on first use;
@@ -517,12 +548,8 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
         ctx->detail = "the filter+refine kernels need every model entry in [0,1]";
         return FV_ERR_UNSUPPORTED;
     }
-    auto t0 = clk::now();
     FV_HIP(hipSetDevice(ctx->device));
-    fv::Plan plan;
-    int rc = fv::build_plan(T, n_split, mode, ctx->nranks, plan);
-    if (rc) return rc;
-    const int kernel = big ? FV_KERNEL_U16_REFINE : wide_q16 ? FV_KERNEL_Q16_REFINE : wide ? FV_KERNEL_F64_STREAM : pick_kernel(ctx);
+    kernel = big ? FV_KERNEL_U16_REFINE : wide_q16 ? FV_KERNEL_Q16_REFINE : wide ? FV_KERNEL_F64_STREAM : pick_kernel(ctx);
     if ((big || wide_q16) && !ctx->laq16_ready) {      // (the flag, not the pointer: a build that failed half way leaves the buffer allocated)
         const int ntiles = (ctx->K + fvk::TILE_W - 1) / fvk::TILE_W;
         const size_t tab = (size_t)ntiles * ctx->nrows * fvk::TILE_W;
@@ -543,23 +570,38 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
         ctx->qscale = -stepf;
         ctx->laq16_ready = true;
     }
+    return fvi::ensure_workspace(ctx, T, rows_needed);
+}
 
+void reset_stats(fv_ctx *ctx, int kernel, int generations)
+{
+    const double keep_model_ms = ctx->stats.set_model_ms;
+    ctx->stats = fv_stats{};
+    ctx->stats.set_model_ms = keep_model_ms;
+    ctx->stats.kernel = kernel;
+    ctx->stats.generations = generations;
+    ctx->stats.table_bytes_per_step = (long long)((ctx->K + fvk::TILE_W - 1) / fvk::TILE_W) * ctx->nrows * fvk::TILE_W * (kernel == FV_KERNEL_F64_STREAM ? 8 : kernel == FV_KERNEL_F32_REFINE ? 4 : 2);
+    if (kernel == FV_KERNEL_SPARSE_Q16) ctx->stats.table_bytes_per_step = (long long)ctx->SPdata.bytes();
+    ctx->stats.density = ctx->density;
+}
+
+int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, int *path_out, float *score_out)
+{
+    if (!ctx || !ob || !path_out || T < 2 || n_split < 1) return FV_ERR_ARG;
+    if (ctx->K == 0) return FV_ERR_STATE;
+    auto t0 = clk::now();
+    fv::Plan plan;
+    int rc = fv::build_plan(T, n_split, mode, ctx->nranks, plan);
+    if (rc) return rc;
     // generations of passes this rank runs
     std::vector<std::vector<fv::Pass>> gens(plan.generations());
     size_t most = 1;
     for (const fv::Pass &p : plan.passes)
         if (p.owner < 0 || p.owner % ctx->nranks == ctx->rank) gens[p.generation].push_back(p);
     for (auto &g : gens) most = std::max(most, g.size());
-    if ((rc = fvi::ensure_workspace(ctx, T, most))) return rc;
-
-    const double keep_model_ms = ctx->stats.set_model_ms;
-    ctx->stats = fv_stats{};
-    ctx->stats.set_model_ms = keep_model_ms;
-    ctx->stats.kernel = kernel;
-    ctx->stats.generations = plan.generations();
-    ctx->stats.table_bytes_per_step = (long long)((ctx->K + fvk::TILE_W - 1) / fvk::TILE_W) * ctx->nrows * fvk::TILE_W * (kernel == FV_KERNEL_F64_STREAM ? 8 : kernel == FV_KERNEL_F32_REFINE ? 4 : 2);
-    if (kernel == FV_KERNEL_SPARSE_Q16) ctx->stats.table_bytes_per_step = (long long)ctx->SPdata.bytes();
-    ctx->stats.density = ctx->density;
+    int kernel = FV_KERNEL_AUTO;
+    if ((rc = prepare_full(ctx, ob, T, most, kernel))) return rc;
+    reset_stats(ctx, kernel, plan.generations());
 
     if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
     FV_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
@@ -574,7 +616,76 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
     ctx->stats.alg_bytes = 4 * ctx->stats.cells;
     return fvi::finish_decode(ctx, plan, T, path_out, score_out, t0, nprof, false);
 }
+
+// fv_test_forward (include/flashvit_testing.h): the caller's passes as one right-hand generation of run_generation_full
+int test_forward_impl(fv_ctx *ctx, const int *ob, int T, const fv_test_pass *tp, int np, float *rows_out, int *bp_out,
+                      unsigned long long *variants_out)
+{
+    if (!ob || !tp || np < 1 || !rows_out || !bp_out || T < 2) return FV_ERR_ARG;
+    if (ctx->K == 0) return FV_ERR_STATE;
+    const int K = ctx->K;
+    std::vector<fv::Pass> gen((size_t)np);
+    std::vector<int> byL((size_t)np);
+    for (int q = 0; q < np; ++q) {
+        const fv_test_pass &p = tp[q];
+        if (p.L < 0 || p.R <= p.L || p.R >= T) { ctx->detail = "fv_test_forward: a pass needs 0 <= L < R < T"; return FV_ERR_ARG; }
+        if (p.L == 0 ? p.init_state >= 0 : (p.init_state < 0 || p.init_state >= K)) {
+            ctx->detail = "fv_test_forward: init_state < 0 (Pi) at L = 0 only, a state in [0, K) at L > 0";
+            return FV_ERR_ARG;
+        }
+        gen[(size_t)q] = fv::Pass{ p.L, p.R, p.L == 0, false, 0, -1 };       // never the whole-sequence pass
+        byL[(size_t)q] = q;
+    }
+    std::sort(byL.begin(), byL.end(), [&](int a, int b) { return tp[a].L < tp[b].L; });
+    for (int q = 1; q < np; ++q)
+        if (tp[byL[q]].L <= tp[byL[q - 1]].R) { ctx->detail = "fv_test_forward: passes overlap"; return FV_ERR_ARG; }
+    int kernel = FV_KERNEL_AUTO;
+    int rc = prepare_full(ctx, ob, T, (size_t)np, kernel);
+    if (rc) return rc;
+    reset_stats(ctx, kernel, 1);
+    ctx->stats.passes = np;
+    if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
+    // Answer array: a valid state at every R (the generation's back-track starts there), then every pass's initial state
+    // at L - 1 (written last: it may be the R of the pass before).  Staged through the head of the pinned block, which
+    // begin_decode leaves free.
+    int *ans = ctx->h_pin;
+    std::fill(ans, ans + T, 0);
+    for (int q = 0; q < np; ++q) if (tp[q].L > 0) ans[tp[q].L - 1] = tp[q].init_state;
+    FV_HIP(hipMemcpyAsync(ctx->d_ans.p, ans, (size_t)T * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    struct Restore {
+        fv_ctx *c; int debug;
+        ~Restore() { c->opt_debug = debug; c->test_record = false; }
+    } restore{ ctx, ctx->opt_debug };
+    ctx->opt_debug |= 8;              // every last step a full step: the whole last row, not the one column a decode reads
+    ctx->test_record = true;
+    ctx->test_variants = 0;
+    ctx->fork_active = false;
+    size_t nprof = 0;
+    if ((rc = run_generation_full(ctx, gen, kernel, nprof))) return rc;      // (sorts `gen` longest first)
+    for (int q = 0; q < np; ++q) {
+        const fv::Pass &p = gen[(size_t)q];
+        int c = 0;
+        while (tp[c].L != p.L) ++c;
+        const float *row = ctx->d_rows.p + (size_t)q * 2 * ctx->nrows + (size_t)((p.R - p.L) & 1) * ctx->nrows;
+        FV_HIP(hipMemcpyAsync(rows_out + (size_t)c * K, row, (size_t)K * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        FV_HIP(hipMemcpyAsync(bp_out + (size_t)(p.L + 1) * K, ctx->d_bp.p + (size_t)(p.L + 1) * K,
+                              (size_t)(p.R - p.L) * K * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    FV_HIP(hipStreamSynchronize(ctx->stream));
+    for (hipGraphExec_t ge : ctx->graphs) (void)hipGraphExecDestroy(ge);
+    ctx->graphs.clear();
+    if (variants_out) *variants_out = ctx->test_variants;
+    return FV_OK;
+}
 }  // namespace
+
+extern "C" int fv_test_forward(fv_ctx *ctx, const int *ob, int T, const fv_test_pass *passes, int npasses,
+                               float *rows_out, int *bp_out, unsigned long long *variants_out)
+{
+    if (!ctx) return FV_ERR_ARG;
+    if (fvi::group_size(ctx) > 1) { ctx->detail = "fv_test_forward: one device per context"; return FV_ERR_ARG; }
+    return fvi::drained(ctx, test_forward_impl(ctx, ob, T, passes, npasses, rows_out, bp_out, variants_out));
+}
 
 extern "C" int fv_decode_vanilla(fv_ctx *ctx, const int *ob, int T, int *path_out, float *score_out)
 {

@@ -116,6 +116,10 @@ struct fv_ctx {
     std::vector<hipEvent_t> prof_events;
     std::vector<int> h_ob;
     std::vector<hipGraphExec_t> graphs;     // experiment (FV_OPT_DEBUG bit 6): destroyed after the decode's sync
+    // test hooks (include/flashvit_testing.h): while test_record is set, the launch helpers OR the FV_TV_* bit of every
+    // step-kernel instantiation they launch into test_variants (a host branch; nothing else runs on a decode)
+    bool test_record = false;
+    unsigned long long test_variants = 0;
 
     // comm
     ncclComm_t comm = nullptr;

@@ -52,6 +52,19 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_last_stats", "fv_strerror", "fv_last_error_detail", "fv_reference_memory_bytes",
            "fv_comm_unique_id", "fv_comm_init", "fv_plan_passes", "fv_merge_paths", "fv_set_partition",
            "fv_create_multi", "fv_device_count"]
+# include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
+TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step"]
+TIE_TAG = 1 << 30
+
+
+class ForwardPass(ctypes.Structure):
+    """fv_test_pass: steps L+1 .. R from Pi (init_state < 0, L = 0) or from state init_state at time L - 1."""
+    _fields_ = [("L", ctypes.c_int), ("R", ctypes.c_int), ("init_state", ctypes.c_int)]
+
+
+class BeamSet(ctypes.Structure):
+    """fv_test_beam_set: n entries (value, state) of one beam step's slot set."""
+    _fields_ = [("val", ctypes.c_void_p), ("state", ctypes.c_void_p), ("n", ctypes.c_int)]
 
 _lib = None
 
@@ -93,6 +106,10 @@ def load_library():
     L.fv_set_partition.argtypes = [vp, ci, ci]
     L.fv_plan_passes.argtypes = [ci, ci, ci, ci, ctypes.POINTER(PassInfo), ci]
     L.fv_merge_paths.argtypes = [ci, ci, ci, vp, vp]
+    L.fv_test_forward.argtypes = [vp, vp, ci, ctypes.POINTER(ForwardPass), ci, vp, vp, ctypes.POINTER(ctypes.c_ulonglong)]
+    cf = ctypes.c_float
+    L.fv_test_beam_step.argtypes = [vp, ci, ctypes.POINTER(BeamSet), ci, vp, ci, cf, cf, ci, vp, vp, vp, ctypes.POINTER(ci),
+                                    vp, vp, vp, vp, ctypes.POINTER(ctypes.c_ulonglong)]
     _lib = L
     return L
 
@@ -208,6 +225,51 @@ class FlashViterbi:
         score = ctypes.c_float(0)
         rc = self._check(self._L.fv_decode_checkpoint(self._h, _p(ob), ob.size, step, _p(path), ctypes.byref(score)))
         return path, np.float32(score.value), rc
+
+    def test_forward(self, ob, passes, bp_fill=-2):
+        """fv_test_forward: passes = [(L, R, init_state)], run as one generation of full-state passes.  Returns
+        (rows[npasses, K] float32, bp[T, K] int32, variants): the final score row of each pass, the back-pointer
+        rows L+1 .. R of each pass at their absolute times (every other row keeps bp_fill) and the FV_TV_* bits of
+        the step-kernel instantiations that ran."""
+        ob = np.ascontiguousarray(ob, dtype=np.int32)
+        pa = (ForwardPass * len(passes))(*[ForwardPass(int(L), int(R), int(s)) for L, R, s in passes])
+        rows = np.empty((len(passes), self.K), dtype=np.float32)
+        bp = np.full((ob.size, self.K), bp_fill, dtype=np.int32)
+        variants = ctypes.c_ulonglong(0)
+        self._check(self._L.fv_test_forward(self._h, _p(ob), ob.size, pa, len(passes), _p(rows), _p(bp), ctypes.byref(variants)))
+        return rows, bp, int(variants.value)
+
+    def test_beam_step(self, beam, sets, syms, speculative=False, theta=0.0, next_bound=float("inf"), cand_cap=0):
+        """fv_test_beam_step: one launch of the beam step kernel over sets = [(values, states)] (beam <= n <= beam + 32),
+        set q consuming symbol syms[q].  Returns a dict: scores[nsets, K] float32, bp[nsets, K] int32 (TIE_TAG-tagged
+        where the maximum is tied), ties = set of (q, column), doubt = per set (count, list), cand = per set (count,
+        list of (score, column)), variants."""
+        K = self.K
+        vals = [np.ascontiguousarray(v, dtype=np.float32) for v, _ in sets]
+        sts = [np.ascontiguousarray(s, dtype=np.int32) for _, s in sets]
+        arr = (BeamSet * len(sets))(*[BeamSet(_p(v).value, _p(s).value, v.size) for v, s in zip(vals, sts)])
+        syms = np.ascontiguousarray(syms, dtype=np.int32)
+        n = len(sets)
+        scores = np.empty((n, K), dtype=np.float32)
+        bp = np.empty((n, K), dtype=np.int32)
+        ties = np.empty((n * K, 2), dtype=np.int32)
+        nties = ctypes.c_int(0)
+        doubt = np.empty((n, 1024), dtype=np.int32)
+        doubt_counts = np.empty(n, dtype=np.int32)
+        cand = np.empty((n, max(cand_cap, 1), 2), dtype=np.int32)
+        cand_counts = np.zeros(n, dtype=np.int32)
+        variants = ctypes.c_ulonglong(0)
+        self._check(self._L.fv_test_beam_step(self._h, int(beam), arr, n, _p(syms), 1 if speculative else 0, float(theta),
+                                              float(next_bound), int(cand_cap), _p(scores), _p(bp), _p(ties), ctypes.byref(nties),
+                                              _p(doubt), _p(doubt_counts), _p(cand), _p(cand_counts), ctypes.byref(variants)))
+        out_cand = []
+        for q in range(n):
+            c = int(cand_counts[q])
+            rows = cand[q, :min(c, cand_cap)]
+            out_cand.append((c, [(rows[i, 0:1].view(np.float32)[0], int(rows[i, 1])) for i in range(rows.shape[0])]))
+        return dict(scores=scores, bp=bp, ties={(int(a), int(b)) for a, b in ties[:nties.value]},
+                    doubt=[(int(doubt_counts[q]), doubt[q, :min(int(doubt_counts[q]), 1024)].tolist()) for q in range(n)],
+                    cand=out_cand, variants=int(variants.value))
 
     def stats(self):
         s = Stats()

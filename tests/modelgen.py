@@ -39,6 +39,44 @@ def _ties_semi(K, M, seed):
     return A, B, np.full(K, 1.0 / K)
 
 
+def _classes(rs, shape, probs=(0.25, 0.25, 0.25, 0.25)):
+    """entries of {1e-16, 1e-8, 1e-3, U(0.1, 1)}"""
+    cls = rs.choice(4, size=shape, p=probs)
+    u = rs.uniform(0.1, 1.0, size=shape)
+    return np.where(cls == 0, 1e-16, np.where(cls == 1, 1e-8, np.where(cls == 2, 1e-3, u)))
+
+
+def wide_model(kind, K, M, T, seed):
+    """Wide-range models (float32 A, B, Pi and the observations): the inputs where the filter kernels' error bracket is
+    thinnest (tests/test_gpu_adversarial.py)."""
+    rs = np.random.RandomState(seed)
+    if kind == "wideA":
+        # every transition present, weights over 16 decades: the table's step is large (36.8 / 65534), the filter's
+        # window wide, the score rows stay inside the code range
+        A = _classes(rs, (K, K))
+        Bm = _classes(rs, (K, M), (0.1, 0.2, 0.3, 0.4))
+        Pi = _classes(rs, (K,), (0.1, 0.2, 0.3, 0.4))
+    elif kind == "wideB":
+        # sparse transitions of ordinary weights (code range = |log 0.1| = 2.3), emissions over 16 decades: most score
+        # rows lie further below the row maximum than the code range reaches; columns all of whose in-edges come from
+        # such rows have only saturated sums
+        p = min(1.0, 6.0 / K)
+        A = rs.uniform(0.1, 1.0, (K, K)) * (rs.uniform(0, 1, (K, K)) < p)
+        A[np.arange(K), rs.randint(0, K, K)] = rs.uniform(0.1, 1.0, K)        # every state has a successor
+        Bm = _classes(rs, (K, M))
+        Pi = _classes(rs, (K,), (0.1, 0.2, 0.3, 0.4))
+    elif kind == "wideAB":
+        # both: sparse transitions over 16 decades (a third of the graph), emissions likewise
+        A = _classes(rs, (K, K)) * (rs.uniform(0, 1, (K, K)) < 0.3)
+        A[np.arange(K), rs.randint(0, K, K)] = 0.5
+        Bm = _classes(rs, (K, M))
+        Pi = _classes(rs, (K,))
+    else:
+        raise ValueError(kind)
+    ob = rs.randint(0, M, T).astype(np.int32)
+    return hostio.quantize_text16(A), hostio.quantize_text16(Bm), hostio.quantize_text16(Pi), ob
+
+
 def model64(spec):
     kind = spec["kind"]
     K, M = spec["K"], spec["M"]

@@ -33,6 +33,18 @@ def test_hip_library_exports_every_declared_symbol():
     assert sorted(decoder.EXPORTS) == [n for n in names]
 
 
+def test_hip_library_exports_every_test_hook():
+    """include/flashvit_testing.h: hooks for the test suite, exported by the product library, listed in
+    decoder.TEST_EXPORTS and kept out of decoder.EXPORTS (the drop-in ABI of flashvit.h)."""
+    lib = decoder.load_library()
+    names = declared_functions("flashvit_testing.h")
+    assert "fv_test_forward" in names
+    for n in names:
+        assert hasattr(lib, n), f"{n} declared in include/flashvit_testing.h but not exported"
+    assert sorted(decoder.TEST_EXPORTS) == names
+    assert not set(names) & set(decoder.EXPORTS)
+
+
 def test_host_library_exports_every_declared_symbol():
     lib = hostio.lib()
     for n in declared_functions("flashvit_host.h"):

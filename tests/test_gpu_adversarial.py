@@ -33,49 +33,13 @@ FULL_KERNELS = [decoder.KERNEL_F64_STREAM, decoder.KERNEL_F32_REFINE, decoder.KE
 U16_FORMS = (0, 262144, 16384, 16384 | 8192, 16384 | 4, 262144 | 16384 | 8192)
 
 
-def _classes(rs, shape, probs=(0.25, 0.25, 0.25, 0.25)):
-    """entries of {1e-16, 1e-8, 1e-3, U(0.1, 1)}"""
-    cls = rs.choice(4, size=shape, p=probs)
-    u = rs.uniform(0.1, 1.0, size=shape)
-    return np.where(cls == 0, 1e-16, np.where(cls == 1, 1e-8, np.where(cls == 2, 1e-3, u)))
-
-
-def wide_model(kind, K, M, T, seed):
-    rs = np.random.RandomState(seed)
-    if kind == "wideA":
-        # every transition present, weights over 16 decades: the table's step is large (36.8 / 65534), the filter's
-        # window wide, the score rows stay inside the code range
-        A = _classes(rs, (K, K))
-        Bm = _classes(rs, (K, M), (0.1, 0.2, 0.3, 0.4))
-        Pi = _classes(rs, (K,), (0.1, 0.2, 0.3, 0.4))
-    elif kind == "wideB":
-        # sparse transitions of ordinary weights (code range = |log 0.1| = 2.3), emissions over 16 decades: most score
-        # rows lie further below the row maximum than the code range reaches; columns all of whose in-edges come from
-        # such rows have only saturated sums
-        p = min(1.0, 6.0 / K)
-        A = rs.uniform(0.1, 1.0, (K, K)) * (rs.uniform(0, 1, (K, K)) < p)
-        A[np.arange(K), rs.randint(0, K, K)] = rs.uniform(0.1, 1.0, K)        # every state has a successor
-        Bm = _classes(rs, (K, M))
-        Pi = _classes(rs, (K,), (0.1, 0.2, 0.3, 0.4))
-    elif kind == "wideAB":
-        # both: sparse transitions over 16 decades (a third of the graph), emissions likewise
-        A = _classes(rs, (K, K)) * (rs.uniform(0, 1, (K, K)) < 0.3)
-        A[np.arange(K), rs.randint(0, K, K)] = 0.5
-        Bm = _classes(rs, (K, M))
-        Pi = _classes(rs, (K,))
-    else:
-        raise ValueError(kind)
-    ob = rs.randint(0, M, T).astype(np.int32)
-    return hostio.quantize_text16(A), hostio.quantize_text16(Bm), hostio.quantize_text16(Pi), ob
-
-
 WIDE = [("wideA", 600, 6, 60, 401), ("wideB", 600, 6, 60, 402), ("wideAB", 600, 6, 60, 403),
         ("wideA", 4500, 5, 24, 404), ("wideB", 4500, 5, 24, 405)]
 
 
 @pytest.mark.parametrize("kind,K,M,T,seed", WIDE)
 def test_wide_dynamic_range_full_state(kind, K, M, T, seed):
-    A, Bm, Pi, ob = wide_model(kind, K, M, T, seed)
+    A, Bm, Pi, ob = modelgen.wide_model(kind, K, M, T, seed)
     om = oracle.OracleModel(A, Bm, Pi)
     want = {N: om.full_decode(ob, N, check=False) for N in (1, 4)}
     om.close()
@@ -112,7 +76,7 @@ def test_wide_dynamic_range_full_state(kind, K, M, T, seed):
 @pytest.mark.parametrize("kind,K,M,T,seed,B", [("wideA", 600, 6, 60, 411, 64), ("wideB", 600, 6, 60, 412, 100),
                                                ("wideAB", 600, 6, 60, 413, 37), ("wideB", 4500, 5, 24, 414, 300)])
 def test_wide_dynamic_range_beam(kind, K, M, T, seed, B):
-    A, Bm, Pi, ob = wide_model(kind, K, M, T, seed)
+    A, Bm, Pi, ob = modelgen.wide_model(kind, K, M, T, seed)
     om = oracle.OracleModel(A, Bm, Pi)
     want = {N: om.beam_decode(ob, N, B, check=False) for N in (1, 4)}
     om.close()
