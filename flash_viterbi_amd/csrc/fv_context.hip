@@ -35,29 +35,52 @@ size_t device_bytes(const fv_ctx *c)
            c->LA64R.bytes() + c->LAQ16R.bytes() + c->d_qaux.bytes() + c->d_tie_list.bytes() + c->d_tie_count.bytes() + c->d_cut.bytes() + c->d_dupwin.bytes() + c->d_cand.bytes() + c->d_cand_count.bytes() + c->d_passL.bytes() + c->d_needfull.bytes() + c->d_doubt.bytes() + c->d_doubt_count.bytes() + c->d_pack.bytes();
 }
 
-int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed)
+// ints in front of the answers in the result block: the counters (64-bit each), then the scores (one per sequence of a
+// batch decode) padded to a multiple of four
+inline size_t pack_head(int nscores) { return 2 * FV_NCOUNTERS + (size_t)std::max(4, round_up(nscores, 4)); }
+
+int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed, int nscores)
 {
+    const size_t want_rows = rows_needed * 2 * (size_t)ctx->nrows;
+    // result block + the staged observations
+    const size_t want_pack = pack_head(nscores) + (size_t)T * std::max(1, ctx->nranks) + (size_t)T;
+    if (nscores > 1) {
+        // A batch's working set grows with the total length (arg rows: T * K int32): sized in 64 bits and compared with
+        // what the device has free (plus what growing a buffer releases first) before anything is allocated.
+        unsigned long long grow = 0, released = 0;
+        auto need = [&](size_t have_bytes, unsigned long long want_bytes) {
+            if (want_bytes > have_bytes) { grow += want_bytes; released += have_bytes; }
+        };
+        need(ctx->d_ob.bytes(), 4ull * T);
+        need(ctx->d_ans.bytes(), 4ull * T);
+        need(ctx->d_bp.bytes(), 4ull * T * ctx->K);
+        need(ctx->d_rows.bytes(), 4ull * want_rows);
+        need(ctx->d_pack.bytes(), 4ull * want_pack);
+        if (grow) {
+            size_t free_b = 0, total_b = 0;
+            FV_HIP(hipMemGetInfo(&free_b, &total_b));
+            if (grow > (unsigned long long)free_b + released) {
+                ctx->detail = "batch workspace: " + std::to_string(grow) + " bytes needed (arg rows " + std::to_string(4ull * T * ctx->K) +
+                              "), " + std::to_string((unsigned long long)free_b + released) + " bytes of device memory free";
+                return FV_ERR_NOMEM;
+            }
+        }
+    }
     FV_HIP(ctx->d_ob.ensure(T));
     FV_HIP(ctx->d_ans.ensure(T));
     FV_HIP(ctx->d_bp.ensure((size_t)T * ctx->K));
-    {
-        const size_t want = rows_needed * 2 * (size_t)ctx->nrows;
-        if (want > ctx->d_rows.n) {
-            FV_HIP(ctx->d_rows.ensure(want));
-            FV_HIP(hipMemsetAsync(ctx->d_rows.p, 0, want * sizeof(float), ctx->stream));   // row pads stay zero
-        }
+    if (want_rows > ctx->d_rows.n) {
+        FV_HIP(ctx->d_rows.ensure(want_rows));
+        FV_HIP(hipMemsetAsync(ctx->d_rows.p, 0, want_rows * sizeof(float), ctx->stream));   // row pads stay zero
     }
-    FV_HIP(ctx->d_score.ensure(4));
+    FV_HIP(ctx->d_score.ensure((size_t)std::max(4, nscores)));
     FV_HIP(ctx->d_counters.ensure(FV_NCOUNTERS));
     if (ctx->comm || ctx->group) FV_HIP(ctx->d_gather.ensure((size_t)T * ctx->nranks));
-    {
-        const size_t want = 2 * FV_NCOUNTERS + 4 + (size_t)T * std::max(1, ctx->nranks) + (size_t)T;     // result block + the staged observations
-        FV_HIP(ctx->d_pack.ensure(want));
-        if (want > ctx->h_pin_n) {
-            if (ctx->h_pin) { (void)hipHostFree(ctx->h_pin); ctx->h_pin = nullptr; ctx->h_pin_n = 0; }
-            FV_HIP(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_pin), want * sizeof(int), hipHostMallocDefault));
-            ctx->h_pin_n = want;
-        }
+    FV_HIP(ctx->d_pack.ensure(want_pack));
+    if (want_pack > ctx->h_pin_n) {
+        if (ctx->h_pin) { (void)hipHostFree(ctx->h_pin); ctx->h_pin = nullptr; ctx->h_pin_n = 0; }
+        FV_HIP(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_pin), want_pack * sizeof(int), hipHostMallocDefault));
+        ctx->h_pin_n = want_pack;
     }
     return 0;
 }
@@ -70,6 +93,16 @@ __global__ void pack_result(const unsigned long long *counters, const float *sco
     if (tid < 2 * FV_NCOUNTERS) out[tid] = reinterpret_cast<const int *>(counters)[tid];
     if (tid == 0) out[2 * FV_NCOUNTERS] = __float_as_int(*score);
     for (size_t i = tid; i < nans; i += (size_t)gridDim.x * blockDim.x) out[PACK_HEAD + i] = ans[i];
+}
+
+// the same block for a batch decode: [counters | nscore scores, padded | answers of all sequences]
+__global__ void pack_result_batch(const unsigned long long *counters, const float *score, int nscore, size_t head, const int *ans,
+                                  size_t nans, int *out)
+{
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
+    if (tid < 2 * FV_NCOUNTERS) out[tid] = reinterpret_cast<const int *>(counters)[tid];
+    for (size_t i = tid; i < (size_t)nscore; i += nthr) out[2 * FV_NCOUNTERS + i] = __float_as_int(score[i]);
+    for (size_t i = tid; i < nans; i += nthr) out[head + i] = ans[i];
 }
 
 __global__ void clear_outputs(unsigned long long *counters, int *ans, int T)
@@ -88,6 +121,40 @@ int begin_decode(fv_ctx *ctx, const int *ob, int T)
     FV_HIP(hipMemcpyAsync(ctx->d_ob.p, stage, (size_t)T * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(clear_outputs, dim3(16), dim3(256), 0, ctx->stream, ctx->d_counters.p, ctx->d_ans.p, T);
     FV_HIP(hipGetLastError());
+    return 0;
+}
+
+// statistics of a finished decode: event times and the device counters the result block brought back
+static int read_stats(fv_ctx *ctx, const unsigned long long *counters, clk::time_point t0, size_t nprof)
+{
+    fv_stats &st = ctx->stats;
+    st.decode_ms = ms_since(t0);
+    float ms = 0.f;
+    FV_HIP(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop)); st.gpu_ms = ms;
+    FV_HIP(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_top)); st.top_pass_ms = ms;
+    FV_HIP(hipEventElapsedTime(&ms, ctx->ev_s0, ctx->ev_s1)); st.top_steps_ms = ms;
+    st.step_kernel_ms = 0;
+    for (size_t i = 0; i + 1 < nprof; i += 2) {
+        FV_HIP(hipEventElapsedTime(&ms, ctx->prof_events[i], ctx->prof_events[i + 1]));
+        st.step_kernel_ms += ms;
+    }
+    st.refine_near = (long long)counters[0];
+    st.refine_rescan = (long long)counters[1];
+    st.beam_exact_sets = (long long)counters[2];
+    st.beam_dup_cols = (long long)counters[3];
+    st.beam_dup_steps = (long long)counters[4];
+    st.beam_ties = (long long)counters[6];
+    st.beam_cand_selects = (long long)counters[7];
+    st.refine_saturated = (long long)counters[8];
+    st.beam_spec_steps = (long long)counters[9];
+    st.beam_reach_events = (long long)counters[10];
+    st.beam_list_short = (long long)counters[11];
+    st.beam_list_long = (long long)counters[12];
+    st.beam_list_entries = (long long)counters[13];
+    st.beam_chain_cuts = (long long)counters[14];
+    if (counters[5]) { ctx->detail = "heap replay: producer/consumer hand-shake timed out"; return FV_ERR_DEVICE; }
+    st.device_bytes = (long long)fvi::device_bytes(ctx);
+    st.ranks = ctx->nranks;
     return 0;
 }
 
@@ -123,38 +190,41 @@ int finish_decode(fv_ctx *ctx, const fv::Plan &plan, int T, int *path_out, float
     }
     if (score_out) *score_out = score;
 
-    fv_stats &st = ctx->stats;
-    st.decode_ms = ms_since(t0);
-    float ms = 0.f;
-    FV_HIP(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop)); st.gpu_ms = ms;
-    FV_HIP(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_top)); st.top_pass_ms = ms;
-    FV_HIP(hipEventElapsedTime(&ms, ctx->ev_s0, ctx->ev_s1)); st.top_steps_ms = ms;
-    st.step_kernel_ms = 0;
-    for (size_t i = 0; i + 1 < nprof; i += 2) {
-        FV_HIP(hipEventElapsedTime(&ms, ctx->prof_events[i], ctx->prof_events[i + 1]));
-        st.step_kernel_ms += ms;
-    }
-    st.refine_near = (long long)counters[0];
-    st.refine_rescan = (long long)counters[1];
-    st.beam_exact_sets = (long long)counters[2];
-    st.beam_dup_cols = (long long)counters[3];
-    st.beam_dup_steps = (long long)counters[4];
-    st.beam_ties = (long long)counters[6];
-    st.beam_cand_selects = (long long)counters[7];
-    st.refine_saturated = (long long)counters[8];
-    st.beam_spec_steps = (long long)counters[9];
-    st.beam_reach_events = (long long)counters[10];
-    st.beam_list_short = (long long)counters[11];
-    st.beam_list_long = (long long)counters[12];
-    st.beam_list_entries = (long long)counters[13];
-    st.beam_chain_cuts = (long long)counters[14];
-    if (counters[5]) { ctx->detail = "heap replay: producer/consumer hand-shake timed out"; return FV_ERR_DEVICE; }
-    st.device_bytes = (long long)fvi::device_bytes(ctx);
-    st.ranks = ctx->nranks;
+    if (int rc = read_stats(ctx, counters, t0, nprof)) return rc;
     bool neg = false;
     for (int j = 0; j < T; ++j) neg |= path_out[j] < 0;
     if (neg) return beam ? FV_WARN_BEAM_MISS : FV_ERR_NO_PRED;
     return FV_OK;
+}
+
+// Epilogue of fv_decode_full_batch: every sequence's answers, the nseq scores and the counters in one block, one
+// device-to-host copy, one sync; the scan for entries without a predecessor is per sequence.
+int finish_decode_batch(fv_ctx *ctx, const long long *offsets, int nseq, int *path_out, float *score_out, int *status_out,
+                        clk::time_point t0, size_t nprof)
+{
+    const size_t nans = (size_t)offsets[nseq], head = pack_head(nseq), total = head + nans;
+    FV_HIP(hipEventRecord(ctx->ev_stop, ctx->stream));
+    hipLaunchKernelGGL(pack_result_batch, dim3(64), dim3(256), 0, ctx->stream, ctx->d_counters.p, ctx->d_score.p, nseq, head,
+                       ctx->d_ans.p, nans, ctx->d_pack.p);
+    FV_HIP(hipGetLastError());
+    FV_HIP(hipMemcpyAsync(ctx->h_pin, ctx->d_pack.p, total * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    FV_HIP(hipStreamSynchronize(ctx->stream));
+    for (hipGraphExec_t ge : ctx->graphs) (void)hipGraphExecDestroy(ge);
+    ctx->graphs.clear();
+    unsigned long long counters[FV_NCOUNTERS];
+    std::memcpy(counters, ctx->h_pin, sizeof counters);
+    std::memcpy(path_out, ctx->h_pin + head, nans * sizeof(int));
+    if (score_out) std::memcpy(score_out, ctx->h_pin + 2 * FV_NCOUNTERS, (size_t)nseq * sizeof(float));
+    if (int rc = read_stats(ctx, counters, t0, nprof)) return rc;
+    int worst = FV_OK;
+    for (int s = 0; s < nseq; ++s) {
+        bool neg = false;
+        for (long long j = offsets[s]; j < offsets[s + 1]; ++j) neg |= path_out[j] < 0;
+        const int st = neg ? FV_ERR_NO_PRED : FV_OK;
+        if (status_out) status_out[s] = st;
+        worst = std::min(worst, st);
+    }
+    return worst;
 }
 
 // A decode that fails after its first enqueue must not leave kernels running on ctx->stream: the next call
@@ -494,7 +564,7 @@ extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
         // the timing build only (libflashvit_timing.so, tools/).  Every bit this library accepts is speed-only.
         if (value & FV_DEBUG_TIMING_ONLY) { ctx->detail = "FV_OPT_DEBUG: result-changing timing switches need the timing build"; return FV_ERR_ARG; }
 #endif
-        if (value < 0 || value >= (1ll << 27)) return FV_ERR_ARG;
+        if (value < 0 || value >= (1ll << 29) || (value & (1ll << 27))) return FV_ERR_ARG;      // (bit 27 is not assigned)
         ctx->opt_debug = (int)value; return FV_OK;
     default: return FV_ERR_ARG;
     }

@@ -291,7 +291,11 @@ int prof_event(fv_ctx *ctx, size_t idx, hipEvent_t *out)
 
 // Runs every pass of one generation in lock-step: at lock-step s each still-active pass advances
 // from time L+s-1 to L+s.  Passes are sorted longest first so the active set is a prefix.
-int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, size_t &nprof)
+// batch: 0 a single-sequence decode; else a generation of fv_decode_full_batch (passes of several sequences on one
+// concatenated time axis; the whole-sequence passes write their scores to d_score[seq]) — BATCH_FORK: its generation 0
+// takes the three-stream form of the right-hand generations, BATCH_SERIAL: it stays on one stream.
+enum { BATCH_NONE = 0, BATCH_SERIAL = 1, BATCH_FORK = 2 };
+int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, size_t &nprof, int batch = BATCH_NONE)
 {
     const int K = ctx->K;
     const int np = (int)passes.size();
@@ -330,7 +334,7 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
     // cfg3 43.8 -> 51.1 ms: workgroups of one launch run in phase, all in their prologue or all in their sweep; what the
     // streams provide is the stagger.)
     const bool two = ((kernel == FV_KERNEL_U16_REFINE && ctx->u16_ok) || (kernel == FV_KERNEL_SPARSE_Q16 && maxlen >= 64)) &&
-                     !(ctx->opt_debug & 262144) && !whole_gen && np > FORK_CAP &&
+                     !(ctx->opt_debug & 262144) && (!whole_gen || batch == BATCH_FORK) && np > FORK_CAP &&
                      !ctx->opt_profile && !(ctx->opt_debug & 64);
     const int nbatches = (np + FORK_CAP - 1) / FORK_CAP;
     const int nstreams = two ? std::min(FORK_STREAMS, nbatches) : 1;      // (batches of three tasks were slower: 2.16 / 54.9 ms)
@@ -438,10 +442,31 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
         ctx->graphs.push_back(ge);
         (void)hipGraphDestroy(g);
     }
-    if (whole_gen) FV_HIP(hipEventRecord(ctx->ev_s1, ctx->stream));
+    if (whole_gen && !two) FV_HIP(hipEventRecord(ctx->ev_s1, ctx->stream));
     if (two) { int rc = join(); if (rc) return rc; }
+    if (whole_gen && two) FV_HIP(hipEventRecord(ctx->ev_s1, ctx->stream));      // (a batch's forked generation 0: after the join)
     // end states + chains
-    for (int q = 0; q < np; ++q) {
+    if (batch) {
+        // one launch for the end picks of all whole-sequence passes (one per sequence), a workgroup each
+        fvk::ArgmaxArgs a;
+        a.rows = ctx->d_rows.p; a.ans = ctx->d_ans.p; a.score = ctx->d_score.p; a.K = K; a.nrows = ctx->nrows; a.n = 0;
+        auto flush = [&]() -> int {
+            if (a.n == 0) return 0;
+            hipLaunchKernelGGL(fvk::final_argmax_batch, dim3(a.n), dim3(1024), 0, ctx->stream, a);
+            FV_HIP(hipGetLastError());
+            a.n = 0;
+            return 0;
+        };
+        for (int q = 0; q < np; ++q) {
+            if (!passes[q].whole) continue;
+            const int len = passes[q].R - passes[q].L;
+            a.j[a.n++] = fvk::ArgmaxJob{ q * 2 + (len & 1), passes[q].R, passes[q].seq };
+            if (a.n == fvk::ARGMAX_CHUNK) { int rc = flush(); if (rc) return rc; }
+        }
+        int rc = flush();
+        if (rc) return rc;
+    }
+    for (int q = 0; q < np && !batch; ++q) {
         if (!passes[q].whole) continue;
         const int len = passes[q].R - passes[q].L;
         const float *last = ctx->d_rows.p + (size_t)q * 2 * ctx->nrows + (size_t)(len & 1) * ctx->nrows;
@@ -521,11 +546,27 @@ extern "C" int fv_decode_full(fv_ctx *ctx, const int *ob, int T, int n_split, in
 }
 
 namespace {
+int decode_full_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split, int mode, int *path_out,
+                           float *score_out, int *status_out);
+}  // namespace
+
+extern "C" int fv_decode_full_batch(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split, int mode,
+                                    int *path_out, float *score_out, int *status_out)
+{
+    if (!ctx) return FV_ERR_ARG;
+    if (ctx->group || ctx->comm || ctx->nranks > 1) {
+        ctx->detail = "fv_decode_full_batch: one device, no communicator and no partition (sequences are not dealt to ranks)";
+        return FV_ERR_UNSUPPORTED;
+    }
+    return fvi::drained(ctx, decode_full_batch_impl(ctx, ob, offsets, nseq, n_split, mode, path_out, score_out, status_out));
+}
+
+namespace {
 // What fv_decode_full and fv_test_forward do before their passes run, through this one path: admission of the kernel
 // choice for the model and of the sequence, the kernel choice itself, the 16-bit table of a model beyond the float32
 // kernels' limit (built on the device on first use) and the workspace for `rows_needed` passes in flight.  (The LDS
 // attributes of every step kernel, fvi::full_setup, are set once by fv_create.)
-int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &kernel)
+int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &kernel, int nscores = 1)
 {
     // Beyond the float32 kernels' LDS limit (one score row of K floats) two routes remain:
     //   * the packed 16-bit kernel — a row of 16-bit score codes is half the bytes (K <= 65536); it needs every model entry
@@ -570,7 +611,7 @@ int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &ker
         ctx->qscale = -stepf;
         ctx->laq16_ready = true;
     }
-    return fvi::ensure_workspace(ctx, T, rows_needed);
+    return fvi::ensure_workspace(ctx, T, rows_needed, nscores);
 }
 
 void reset_stats(fv_ctx *ctx, int kernel, int generations)
@@ -615,6 +656,67 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
     ctx->stats.cells = ctx->stats.task_steps * (long long)ctx->K * ctx->K + ctx->stats.column_steps * (long long)ctx->K;
     ctx->stats.alg_bytes = 4 * ctx->stats.cells;
     return fvi::finish_decode(ctx, plan, T, path_out, score_out, t0, nprof, false);
+}
+
+// fv_decode_full_batch: the forest plan (build_plan of every sequence on one concatenated time axis) run generation by
+// generation — generation g of the batch is generation g of every sequence, so a lock-step's launches carry passes of
+// different sequences.  Observations, answers and arg rows are indexed by absolute time, and a pass starts from Pi by
+// its flag, not by L == 0: init rows, step kernels, last columns and back-tracks run on the shifted passes as they are.
+int decode_full_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split, int mode, int *path_out,
+                           float *score_out, int *status_out)
+{
+    if (!ob || !offsets || !path_out || nseq < 1 || n_split < 1) return FV_ERR_ARG;
+    if (mode != FV_MODE_REFERENCE && mode != FV_MODE_SINGLE_PASS) return FV_ERR_ARG;
+    if (offsets[0] != 0) { ctx->detail = "fv_decode_full_batch: offsets[0] must be 0"; return FV_ERR_ARG; }
+    std::vector<int> lengths((size_t)nseq);
+    for (int s = 0; s < nseq; ++s) {
+        const long long len = offsets[s + 1] - offsets[s];
+        if (len < 0) { ctx->detail = "fv_decode_full_batch: offsets decrease at sequence " + std::to_string(s); return FV_ERR_ARG; }
+        if (len < 2) { ctx->detail = "fv_decode_full_batch: sequence " + std::to_string(s) + " has fewer than 2 observations"; return FV_ERR_ARG; }
+        if (offsets[s + 1] > 0x7fffffffLL) { ctx->detail = "fv_decode_full_batch: more than 2^31 - 1 observations in all (at sequence " + std::to_string(s) + ")"; return FV_ERR_ARG; }
+        lengths[(size_t)s] = (int)len;
+    }
+    if (ctx->K == 0) return FV_ERR_STATE;
+    for (int s = 0; s < nseq; ++s)
+        for (long long j = offsets[s]; j < offsets[s + 1]; ++j)
+            if (ob[j] < 0 || ob[j] >= ctx->M) {
+                ctx->detail = "fv_decode_full_batch: sequence " + std::to_string(s) + " holds a symbol outside [0, M) at position " + std::to_string(j - offsets[s]);
+                return FV_ERR_ARG;
+            }
+    auto t0 = clk::now();
+    const int sumT = (int)offsets[nseq];
+    fv::Plan plan;
+    int bad = -1;
+    int rc = fv::build_forest(lengths.data(), nseq, n_split, mode, plan, &bad);
+    if (rc) {
+        ctx->detail = "fv_decode_full_batch: sequence " + std::to_string(bad) + " of length " + std::to_string(lengths[(size_t)std::max(bad, 0)]) +
+                      " has no plan for n_split = " + std::to_string(n_split) + " (T == 2 * n_split with n_split > 2)";
+        return rc;
+    }
+    std::vector<std::vector<fv::Pass>> gens(plan.generations());
+    size_t most = 1;
+    for (const fv::Pass &p : plan.passes) gens[p.generation].push_back(p);
+    for (auto &g : gens) most = std::max(most, g.size());
+    int kernel = FV_KERNEL_AUTO;
+    if ((rc = prepare_full(ctx, ob, sumT, most, kernel, std::max(nseq, 2)))) return rc;
+    reset_stats(ctx, kernel, plan.generations());
+
+    if ((rc = fvi::begin_decode(ctx, ob, sumT))) return rc;
+    FV_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
+    size_t nprof = 0;
+    ctx->fork_active = false;
+    // Generation 0 — nseq whole-sequence passes in lock-step — in the three-stream, four-task form of the right-hand
+    // generations (DESIGN.md 5.2f has the measurement); FV_OPT_DEBUG bit 28: single-stream launches of up to
+    // FV_OPT_MAX_BATCH tasks instead.
+    const int gen0 = (ctx->opt_debug & (1 << 28)) ? BATCH_SERIAL : BATCH_FORK;
+    for (size_t g = 0; g < gens.size(); ++g) {
+        ctx->stats.passes += (int)gens[g].size();
+        if ((rc = run_generation_full(ctx, gens[g], kernel, nprof, gen0))) return rc;
+        if (g == 0) FV_HIP(hipEventRecord(ctx->ev_top, ctx->stream));
+    }
+    ctx->stats.cells = ctx->stats.task_steps * (long long)ctx->K * ctx->K + ctx->stats.column_steps * (long long)ctx->K;
+    ctx->stats.alg_bytes = 4 * ctx->stats.cells;
+    return fvi::finish_decode_batch(ctx, offsets, nseq, path_out, score_out, status_out, t0, nprof);
 }
 
 // fv_test_forward (include/flashvit_testing.h): the caller's passes as one right-hand generation of run_generation_full

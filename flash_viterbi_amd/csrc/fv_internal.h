@@ -165,10 +165,13 @@ int build_host_tables(const float *A, const float *B, const float *Pi, int K, in
 int upload_tables(fv_ctx *ctx, const HostTables &h);
 
 size_t device_bytes(const fv_ctx *c);
-int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed);
+// (nscores > 1: a batch decode — room for that many scores, sizes checked against free device memory first)
+int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed, int nscores = 1);
 // decode epilogue: (multi-rank: all-gather + merge,) path / score / counters to the host, one sync, statistics
 int finish_decode(fv_ctx *ctx, const fv::Plan &plan, int T, int *path_out, float *score_out, clk::time_point t0,
                   size_t nprof, bool beam);
+int finish_decode_batch(fv_ctx *ctx, const long long *offsets, int nseq, int *path_out, float *score_out, int *status_out,
+                        clk::time_point t0, size_t nprof);
 int drained(fv_ctx *ctx, int rc);
 // decode prologue: observation sequence to the device (through the pinned block), counters and answers cleared
 int begin_decode(fv_ctx *ctx, const int *ob, int T);

@@ -1286,6 +1286,44 @@ __global__ __launch_bounds__(1024) void final_argmax(const float *row, int K, in
     }
 }
 
+// The same end pick for every whole-sequence pass of a batch decode's generation 0 in ONE launch (a launch costs
+// 1.5-3 us; a batch has one whole pass per sequence): workgroup b takes job b — its pass's last score row — and writes
+// ans[R] and score[seq].  Per lane an ascending scan with strict '>', then the (value, lowest index) order of
+// `better` across lanes and waves: the lowest index among the maxima, as FLASH:186-196.
+struct ArgmaxJob { int row; int R; int seq; };          // row: index of the K-float row in units of `nrows` floats
+constexpr int ARGMAX_CHUNK = 256;
+struct ArgmaxArgs { const float *rows; int *ans; float *score; int K, nrows, n; ArgmaxJob j[ARGMAX_CHUNK]; };
+
+__global__ __launch_bounds__(1024) void final_argmax_batch(const ArgmaxArgs args)
+{
+    __shared__ float sv[16];
+    __shared__ int sk[16];
+    if ((int)blockIdx.x >= args.n) return;             // workgroup-uniform
+    const ArgmaxJob job = args.j[blockIdx.x];
+    const float *row = args.rows + (size_t)job.row * args.nrows;
+    float v = FV_NEG_INF;
+    int k = INT_MAX;
+    for (int i = threadIdx.x; i < args.K; i += blockDim.x) {
+        const float x = row[i];
+        if (x > v) { v = x; k = i; }
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        float ov = __shfl_xor(v, m);
+        int ok = __shfl_xor(k, m);
+        if (better(ov, ok, v, k)) { v = ov; k = ok; }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { sv[w] = v; sk[w] = k; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < (int)(blockDim.x >> 6); ++q)
+            if (better(sv[q], sk[q], v, k)) { v = sv[q]; k = sk[q]; }
+        args.ans[job.R] = k;
+        args.score[job.seq] = v;
+    }
+}
+
 // Last step of a pass whose end state is already fixed (every pass except the whole-sequence one):
 // the back-track only ever reads bp[R][Ans[R]], so only that one destination column is evaluated —
 // K cells instead of K*K — with the reference expression from the float64 table.  One workgroup per pass.

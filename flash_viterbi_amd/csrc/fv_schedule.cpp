@@ -97,7 +97,49 @@ int build_plan(int T, int n_split, int mode, int nranks, Plan &plan)
     return 0;
 }
 
+int build_forest(const int *lengths, int nseq, int n_split, int mode, Plan &plan, int *bad_seq)
+{
+    if (!lengths || nseq < 1) return FV_ERR_ARG;
+    plan = Plan();
+    std::vector<Pass> all;
+    long long off = 0;
+    for (int s = 0; s < nseq; ++s) {
+        Plan one;
+        const int rc = build_plan(lengths[s], n_split, mode, 1, one);
+        if (rc || off + lengths[s] > 0x7fffffffLL) {
+            if (bad_seq) *bad_seq = s;
+            return rc ? rc : FV_ERR_ARG;
+        }
+        for (Pass p : one.passes) {
+            p.L += (int)off; p.R += (int)off; p.seq = s;
+            all.push_back(p);
+        }
+        off += lengths[s];
+    }
+    // (stable: within a generation the sequences keep their order, within a sequence the passes keep build_plan's)
+    std::stable_sort(all.begin(), all.end(), [](const Pass &x, const Pass &y) { return x.generation < y.generation; });
+    plan.passes.swap(all);
+    int g = -1;
+    for (int i = 0; i < (int)plan.passes.size(); ++i)
+        while (g < plan.passes[i].generation) { plan.gen_begin.push_back(i); ++g; }
+    plan.gen_begin.push_back((int)plan.passes.size());
+    return 0;
+}
+
 }  // namespace fv
+
+extern "C" int fv_plan_passes_batch(const int *lengths, int nseq, int n_split, int mode, fv_pass_info *out, int cap)
+{
+    fv::Plan plan;
+    int rc = fv::build_forest(lengths, nseq, n_split, mode, plan, nullptr);
+    if (rc) return rc;
+    int n = (int)plan.passes.size();
+    for (int i = 0; i < n && i < cap && out; ++i) {
+        out[i].L = plan.passes[i].L; out[i].R = plan.passes[i].R;
+        out[i].generation = plan.passes[i].generation; out[i].owner = plan.passes[i].seq;
+    }
+    return n;
+}
 
 extern "C" int fv_plan_passes(int T, int n_split, int mode, int nranks, fv_pass_info *out, int cap)
 {

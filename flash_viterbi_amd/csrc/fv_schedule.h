@@ -10,6 +10,8 @@ struct Pass {
     bool whole;        // the whole-sequence pass: end state = argmax of the last row
     int generation;    // passes of one generation are mutually independent
     int owner;         // rank that runs it (-1: every rank)
+    int seq = 0;       // batch decode: index of the sequence the pass belongs to (L and R are positions in the
+                       // concatenated time axis of the batch)
 };
 
 struct Plan {
@@ -28,5 +30,11 @@ void split_points(int L, int R, int N, std::vector<int> &mid);
 // mode 1: one pass over [0,T-1].
 // Returns 0 or a negative FV_ERR_* code.
 int build_plan(int T, int n_split, int mode, int nranks, Plan &plan);
+
+// A batch of sequences laid end to end on one time axis: build_plan of every sequence (one rank), shifted to the
+// sequence's offset; generation g of the forest is the union of generation g of every sequence, in sequence order.
+// midpoints / seg_* stay empty (they serve the multi-rank merge).  On failure *bad_seq (may be null) is the index of
+// the sequence build_plan refused.
+int build_forest(const int *lengths, int nseq, int n_split, int mode, Plan &plan, int *bad_seq);
 
 }  // namespace fv

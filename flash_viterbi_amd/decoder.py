@@ -17,7 +17,9 @@ KERNEL_AUTO, KERNEL_F64_STREAM, KERNEL_F32_REFINE, KERNEL_F16_REFINE, KERNEL_Q16
 KERNEL_U16_REFINE = 6
 OPT_KERNEL, OPT_MAX_BATCH, OPT_PROFILE, OPT_SEL_MARGIN, OPT_DEBUG = 1, 2, 3, 4, 100
 DEBUG_TIMING_ONLY = (1 << 0) | (1 << 4) | (1 << 5) | (1 << 11) | (1 << 12)      # refused by the shipped library
+DEBUG_BATCH_GEN0_SERIAL = 1 << 28      # decode_full_batch: the whole-sequence passes on one stream (speed only)
 WARN_BEAM_MISS = 1
+ERR_ARG, ERR_NOMEM, ERR_NO_PRED, ERR_DEVICE, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 UNIQUE_ID_BYTES = 128
 
 
@@ -51,7 +53,7 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_decode_vanilla", "fv_decode_checkpoint", "fv_checkpoint_memory_bytes",
            "fv_last_stats", "fv_strerror", "fv_last_error_detail", "fv_reference_memory_bytes",
            "fv_comm_unique_id", "fv_comm_init", "fv_plan_passes", "fv_merge_paths", "fv_set_partition",
-           "fv_create_multi", "fv_device_count"]
+           "fv_create_multi", "fv_device_count", "fv_decode_full_batch", "fv_plan_passes_batch"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step"]
 TIE_TAG = 1 << 30
@@ -90,6 +92,8 @@ def load_library():
     L.fv_set_option.argtypes = [vp, ci, cll]
     L.fv_decode_full.argtypes = [vp, vp, ci, ci, ci, vp, vp]
     L.fv_decode_beam.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
+    L.fv_decode_full_batch.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
+    L.fv_plan_passes_batch.argtypes = [vp, ci, ci, ci, ctypes.POINTER(PassInfo), ci]
     L.fv_decode_vanilla.argtypes = [vp, vp, ci, vp, vp]
     L.fv_decode_checkpoint.argtypes = [vp, vp, ci, ci, vp, vp]
     L.fv_checkpoint_memory_bytes.argtypes = [ci, ci, ci]
@@ -129,6 +133,19 @@ def plan_passes(T, n_split, mode=MODE_REFERENCE, nranks=1):
         raise FlashVitError(n)
     buf = (PassInfo * n)()
     L.fv_plan_passes(T, n_split, mode, nranks, buf, n)
+    return [(p.L, p.R, p.generation, p.owner) for p in buf]
+
+
+def plan_passes_batch(lengths, n_split, mode=MODE_REFERENCE):
+    """Host-side schedule of decode_full_batch (no GPU): list of (L, R, generation, sequence index), L and R on the
+    concatenated time axis (sequence s starts at sum(lengths[:s]))."""
+    L = load_library()
+    lens = np.ascontiguousarray(lengths, dtype=np.int32)
+    n = L.fv_plan_passes_batch(_p(lens), lens.size, n_split, mode, None, 0)
+    if n < 0:
+        raise FlashVitError(n)
+    buf = (PassInfo * n)()
+    L.fv_plan_passes_batch(_p(lens), lens.size, n_split, mode, buf, n)
     return [(p.L, p.R, p.generation, p.owner) for p in buf]
 
 
@@ -204,6 +221,25 @@ class FlashViterbi:
         score = ctypes.c_float(0)
         rc = self._check(self._L.fv_decode_full(self._h, _p(ob), ob.size, n_split, mode, _p(path), ctypes.byref(score)))
         return path, np.float32(score.value), rc
+
+    def decode_full_batch(self, obs, n_split=1, mode=MODE_REFERENCE):
+        """fv_decode_full_batch: obs is a list of int sequences (lengths may differ) for the model of this context.
+        Returns (paths: list of int32 arrays, scores: float32 array, statuses: int32 array), per sequence what
+        decode_full returns for it alone.  A sequence whose path has an entry without a finite predecessor reports
+        ERR_NO_PRED in `statuses` (its path holds the -1 entries) and does not raise: the other sequences' results
+        stand.  Every other negative return raises FlashVitError."""
+        seqs = [np.ascontiguousarray(o, dtype=np.int32).reshape(-1) for o in obs]
+        offsets = np.zeros(len(seqs) + 1, dtype=np.int64)
+        if seqs:
+            offsets[1:] = np.cumsum([o.size for o in seqs])
+        ob = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.int32)
+        path = np.empty(max(ob.size, 1), dtype=np.int32)
+        scores = np.zeros(len(seqs), dtype=np.float32)
+        statuses = np.zeros(len(seqs), dtype=np.int32)
+        rc = self._L.fv_decode_full_batch(self._h, _p(ob), _p(offsets), len(seqs), n_split, mode, _p(path), _p(scores), _p(statuses))
+        if rc != ERR_NO_PRED:
+            self._check(rc)
+        return [path[offsets[s]:offsets[s + 1]].copy() for s in range(len(seqs))], scores, statuses
 
     def decode_beam(self, ob, n_split, beam, mode=MODE_REFERENCE):
         ob = np.ascontiguousarray(ob, dtype=np.int32)

@@ -11,6 +11,13 @@ compiled from the reference's own sources — that checker lives outside this pa
   python3 run_hip.py                      # every parameter set x every program
   python3 run_hip.py --gen                # generate missing input files first (generate_data counterpart)
   python3 run_hip.py --ref-md5 FILE.json  # fill ref_path_equal from {"<program>|K|M|T|prob|N|B": "<md5 of the path>"}
+  python3 run_hip.py --batch OB_FILE...   # decode several observation files against the model of parameters[0] in ONE
+                                          # fv_decode_full_batch call (Python binding; the C host programs keep the
+                                          # reference's one-sequence command line): the model is read from data/ under the
+                                          # names the host programs open, every OB_FILE holds whitespace-separated symbols
+                                          # (any length >= 2), and one `path: [...]` line per file is printed, in order,
+                                          # after a `time:` line for the whole batch.  Exit status 3 if a decode failed;
+                                          # a sequence without a finite predecessor prints its path with the -1 entries.
 """
 import csv
 import hashlib
@@ -105,7 +112,51 @@ def path_md5(path_tokens):
     return hashlib.md5((" ".join(str(x) for x in path_tokens)).encode()).hexdigest()
 
 
+def run_batch(files):
+    """--batch: the full-state FLASH decode of every file's sequence against parameters[0]'s model, one library call."""
+    import time
+
+    import numpy as np
+
+    from flash_viterbi_amd import decoder, hostio
+    p = parameters[0]
+    K, M, T, prob = p["K_STATE"], p["T_STATE"], p["obserRouteLEN"], p["prob"]
+    if "--gen" in sys.argv:
+        ensure_inputs(p)
+    A, B, Pi, _ = hostio.load_model_text(data_path, K, M, T, prob)
+    obs = []
+    for f in files:
+        with open(f) as fh:
+            obs.append(np.asarray([int(tok) for tok in fh.read().split()], dtype=np.int32))
+    fv = decoder.FlashViterbi(0)
+    try:
+        fv.set_model(A, B, Pi)
+        t0 = time.perf_counter()
+        paths, scores, statuses = fv.decode_full_batch(obs, p["MAX_THREADS"])
+        dt = time.perf_counter() - t0
+    except decoder.FlashVitError as e:
+        print(f"fv_decode_full_batch: {e}", file=sys.stderr)
+        return 3
+    finally:
+        fv.close()
+    print(f"time: {dt:f} ")
+    for f, path, st in zip(files, paths, statuses):
+        print("path: [" + "".join(f"{int(x)} " for x in path) + "]")
+        if st:
+            print(f"{f}: {decoder.load_library().fv_strerror(int(st)).decode()} ({int(st)})", file=sys.stderr)
+    return 0
+
+
 def main():
+    if "--batch" in sys.argv:
+        i = sys.argv.index("--batch")
+        files = [a for a in sys.argv[i + 1:] if not a.startswith("--")]
+        if not files:
+            print("--batch needs at least one observation file", file=sys.stderr)
+            sys.exit(2)
+        fvbuild.build_host()
+        fvbuild.build_hip()
+        sys.exit(run_batch(files))
     os.makedirs(result_path, exist_ok=True)
     os.makedirs(data_path, exist_ok=True)
     fvbuild.build_host()

@@ -69,7 +69,9 @@ enum {
                                Full-state: 1 no reverse sweep, 2 alternate load schedule, 3 full last step instead of one
                                column, 6 hipGraph replay of a generation, 13 packed kernel in 16-wave workgroups, 14 packed
                                kernel for every batched launch, 18 right-hand generations on one stream, 21 F64 / F32 / F16 / Q16
-                               kernels in three slabs of source rows (the route of K > 65536) at any size.  FLASH-BS: 7 the cut predictor uses the pass's own
+                               kernels in three slabs of source rows (the route of K > 65536) at any size, 28 fv_decode_full_batch: the whole-sequence
+                               passes (generation 0) in single-stream launches of up to FV_OPT_MAX_BATCH tasks instead of the
+                               three-stream, four-task form (bit 27 is not assigned and refused).  FLASH-BS: 7 the cut predictor uses the pass's own
                                cuts only, 8 / 9
                                float64 / 16-bit step kernel always, 10 no candidate lists, 15 whole-workgroup select for short
                                lists too, 16 / 17 pass groups on one stream / on four streams whatever the size, 19 every heap
@@ -174,6 +176,22 @@ int fv_set_option(fv_ctx *ctx, int key, long long value);
 int fv_decode_full(fv_ctx *ctx, const int *ob, int T, int n_split, int mode,
                    int *path_out, float *score_out);
 
+/* nseq observation sequences against the model of ctx, decoded together: the reference is one process, one sequence
+ * (main :370-380); a caller with many sequences for one model would run it nseq times.  Here the forward passes of
+ * different sequences share the step launches (up to FV_OPT_MAX_BATCH passes per sweep of the transition table).
+ * ob holds the sequences back to back; sequence s is ob[offsets[s] .. offsets[s+1]) (offsets[0] == 0, nseq + 1
+ * non-decreasing entries, lengths may differ, the total below 2^31).  path_out has the same layout.  score_out (may
+ * be NULL) and status_out (may be NULL) have nseq entries: per sequence exactly what
+ * fv_decode_full(ctx, ob + offsets[s], T_s, n_split, mode, ...) delivers in *score_out and as its return code —
+ * FV_OK, or FV_ERR_NO_PRED with the -1 entries in that sequence's path (the other sequences are intact).
+ * Return: 0, or the most negative per-sequence status.  A sequence fv_decode_full would refuse (T_s < 2, a symbol
+ * outside [0,M), T_s == 2*n_split with n_split > 2) fails the whole call with FV_ERR_ARG before any device work;
+ * fv_last_error_detail names its index.  A context with a communicator, a partition or several devices answers
+ * FV_ERR_UNSUPPORTED.  fv_last_stats reports the batch as one decode (counters are totals, `generations` the largest
+ * of any sequence). */
+int fv_decode_full_batch(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split, int mode,
+                         int *path_out, float *score_out, int *status_out);
+
 /* calc() of FLASH_BS_Viterbi_multithread.c:548-577 with MAX_THREADS = n_split and
  * BeamSearchWidth = beam_width (2 <= beam_width <= K). */
 int fv_decode_beam(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_width, int mode,
@@ -230,6 +248,11 @@ int fv_merge_paths(int T, int n_split, int nranks, const int *gathered, int *pat
  * the number of passes (or <0).  Pass 0 is always the whole-sequence pass. */
 typedef struct { int L, R, generation, owner; } fv_pass_info;
 int fv_plan_passes(int T, int n_split, int mode, int nranks, fv_pass_info *out, int cap);
+
+/* The schedule of fv_decode_full_batch: the passes of all sequences in launch order (sorted by generation), L and R
+ * as positions in the concatenated time axis (sequence s starts at lengths[0] + .. + lengths[s-1]), `owner` = index
+ * of the sequence the pass belongs to.  Returns the number of passes (or <0). */
+int fv_plan_passes_batch(const int *lengths, int nseq, int n_split, int mode, fv_pass_info *out, int cap);
 
 #ifdef __cplusplus
 }
