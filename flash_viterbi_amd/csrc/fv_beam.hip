@@ -6,6 +6,8 @@
 
 namespace {
 int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_width, int mode, int *path_out, float *score_out);
+int decode_beam_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split, int beam_width, int mode,
+                           int *path_out, float *score_out, int *status_out);
 
 // row pitch of the row-major float64 table the beam kernels gather from
 inline int beam_ld(int K) { return (K + fvb::BEAM_COLS - 1) / fvb::BEAM_COLS * fvb::BEAM_COLS; }
@@ -24,6 +26,24 @@ inline int beam_groups(const fv_ctx *ctx, int np, int beam)
     if ((ctx->opt_debug & 65536) || np < 2) return 1;            // FV_OPT_DEBUG bit 16: one stream
     if (!(ctx->opt_debug & 131072) && (double)beam * ctx->K < 16e6) return 1;
     return std::min(1 + fv_ctx::BEAM_AUX, np);
+}
+
+// Generation 0 of fv_decode_beam_batch: np whole-sequence passes in lock-step.  A select launch lasts as long as its slowest
+// workgroup, and a workgroup that meets a reach event replays heaps for tens of microseconds: on one stream every pass
+// of the lock-step waits behind it, dealt to the stream groups only the passes of its group do — at the price of the
+// dispatch overhead queued auxiliary streams put on the main one (beam_groups).  DESIGN.md 5.4b has both forms' numbers;
+// FV_OPT_DEBUG bit 29 selects the form that is not the default, bits 16 / 17 force one stream / the groups as elsewhere.
+constexpr bool BATCH_GEN0_DEALT = true;
+inline int batch_gen0_groups(const fv_ctx *ctx, int np)
+{
+    if ((ctx->opt_debug & 65536) || np < 2) return 1;
+    const bool dealt = (ctx->opt_debug & 131072) || BATCH_GEN0_DEALT != !!(ctx->opt_debug & (1 << 29));
+    return dealt ? std::min(1 + fv_ctx::BEAM_AUX, np) : 1;
+}
+// stream groups of generation g of a decode of nseq sequences
+inline int gen_groups(const fv_ctx *ctx, size_t g, int np, int beam, int nseq)
+{
+    return (g == 0 && nseq > 1) ? batch_gen0_groups(ctx, np) : beam_groups(ctx, np, beam);
 }
 
 // The step kernel of one beam launch: the one rule run_generation_beam and fv_test_beam_step share.
@@ -63,7 +83,10 @@ int launch_beam_step(fv_ctx *ctx, const fvb::BeamStepArgs &a, hipStream_t st)
     return 0;
 }
 
-int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t pass_off, int beam, int T)
+// T: length of the time axis (a batch: all sequences end to end); ng: stream groups the passes were ordered for;
+// nseq / seq_of: fv_decode_beam_batch — the tie gates are per sequence (seq_of: the device's time -> sequence map).
+int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t pass_off, int beam, int T, int ng,
+                        int nseq = 1, const int *seq_of = nullptr)
 {
     const int K = ctx->K, np = (int)passes.size();
     if (np == 0) return 0;
@@ -123,7 +146,6 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
     // Every group runs its passes in lock-step on its own stream: first heaps' members, then step + select per position.
     // A select launch lasts as long as its slowest exact replay and keeps one CU per pass busy; the step kernels of
     // the other groups fill the rest of the chip meanwhile.
-    const int ng = beam_groups(ctx, np, beam);
     if (ng > 1) FV_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
     int rc = 0;
     for (int g = 0, first = 0; g < ng; ++g) {
@@ -173,12 +195,12 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
     // needs a layout for that — its last heap's.  The exact layouts of every step's heap and the tie fix-up are queued
     // behind it but run only if the walk met a tied cell (FV_OPT_DEBUG bit 19: always).
     const bool lazy = !(ctx->opt_debug & 524288);
-    FV_HIP(hipMemsetAsync(ctx->d_needfull.p, 0, sizeof(int), ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_needfull.p, 0, (size_t)nseq * sizeof(int), ctx->stream));
     auto layouts = [&](bool last_only, const int *gate) -> int {
         for (int base = 0; base < np; base += fvb::HEAP_CHUNK) {
             fvb::HeapAllArgs h;
             h.scores_all = ctx->d_scores.p; h.slot_val = ctx->d_slot_val.p; h.slot_state = ctx->d_slot_state.p;
-            h.err_counter = ctx->d_counters.p + 5; h.gate = gate;
+            h.err_counter = ctx->d_counters.p + 5; h.gate = gate; h.seq_of = seq_of;
             h.K = K; h.beam = beam; h.n = 0;
             int longest = 0;
             for (int q = 0; q < std::min(fvb::HEAP_CHUNK, np - base); ++q) {
@@ -198,7 +220,8 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
             fvb::BeamEndArgs e;
             e.K = K; e.beam = beam; e.n = std::min(fvb::BEAM_CHUNK, np - base);
             e.lazy = lazy_walk; e.flag = ctx->d_needfull.p;
-            for (int q = 0; q < e.n; ++q) e.p[q] = fvb::BeamEnd{ passes[base + q].L, passes[base + q].R, passes[base + q].whole ? 1 : 0 };
+            for (int q = 0; q < e.n; ++q)
+                e.p[q] = fvb::BeamEnd{ passes[base + q].L, passes[base + q].R, passes[base + q].whole ? 1 : 0, passes[base + q].seq };
             hipLaunchKernelGGL(fvb::beam_end_backtrack, dim3(e.n), dim3(64), 0, ctx->stream, e, ctx->d_slot_val.p,
                                ctx->d_slot_state.p, ctx->d_hstate.p, ctx->d_cut.p, ctx->d_bp.p, ctx->d_ans.p, ctx->d_score.p);
             FV_HIP(hipGetLastError());
@@ -212,7 +235,8 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
             fvb::ResolveArgs r;
             r.rc = rcx; r.mode = mode; r.gate = gate; r.ans = ctx->d_ans.p;
             r.n = std::min(fvb::BEAM_CHUNK, np - base);
-            for (int q = 0; q < r.n; ++q) r.p[q] = fvb::BeamEnd{ passes[base + q].L, passes[base + q].R, passes[base + q].whole ? 1 : 0 };
+            for (int q = 0; q < r.n; ++q)
+                r.p[q] = fvb::BeamEnd{ passes[base + q].L, passes[base + q].R, passes[base + q].whole ? 1 : 0, passes[base + q].seq };
             hipLaunchKernelGGL(fvb::beam_resolve, dim3(r.n), dim3(fvb::RESOLVE_BLOCK), fvb::heap_lds(beam), ctx->stream, r);
             FV_HIP(hipGetLastError());
         }
@@ -222,6 +246,8 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
     if (lazy) {
         if ((rc = layouts(true, nullptr))) return rc;
         if ((rc = ends(1))) return rc;
+    } else if (seq_of) {
+        FV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctx->d_needfull.p), 1, (size_t)nseq, ctx->stream));    // every flag up
     } else {
         int one = 1;
         FV_HIP(hipMemcpyAsync(ctx->d_needfull.p, &one, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
@@ -235,6 +261,7 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
         f.tie_count = ctx->d_tie_count.p; f.tie_list = ctx->d_tie_list.p; f.tie_cap = (unsigned int)ctx->d_tie_list.n;
         f.slot_val = ctx->d_slot_val.p; f.slot_state = ctx->d_slot_state.p; f.bp = ctx->d_bp.p;
         f.K = K; f.ld = beam_ld(K); f.beam = beam; f.total = ctx->d_counters.p + 6; f.gate = ctx->d_needfull.p;
+        f.seq_of = seq_of;
         hipLaunchKernelGGL(fvb::tie_fixup, dim3(512), dim3(256), 0, ctx->stream, f);
         FV_HIP(hipGetLastError());
     }
@@ -296,51 +323,52 @@ int beam_tables(fv_ctx *ctx)
     return 0;
 }
 
-int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_width, int mode, int *path_out, float *score_out)
+// The per-step buffers of a beam decode over T observations (a batch: all sequences end to end), indexed by absolute
+// time.  nseq > 0 (fv_decode_beam_batch): the sizes — these and fvi::ensure_workspace's — are first added up in 64 bits and
+// compared with the free device memory plus what growing a buffer releases, before anything is allocated.
+int beam_workspace(fv_ctx *ctx, int T, int beam, int nseq)
 {
-    if (!ctx || !ob || !path_out || T < 2 || n_split < 1) return FV_ERR_ARG;
-    if (ctx->K == 0) return FV_ERR_STATE;
-    int rc = beam_admit(ctx, beam_width);
-    if (rc) return rc;
-    for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->M) return FV_ERR_ARG;
-    auto t0 = clk::now();
-    FV_HIP(hipSetDevice(ctx->device));
-    fv::Plan plan;
-    if ((rc = fv::build_plan(T, n_split, mode, ctx->nranks, plan))) return rc;
-    std::vector<std::vector<fv::Pass>> gens(plan.generations());
-    size_t most = 1;
-    for (const fv::Pass &p : plan.passes)
-        if (p.owner < 0 || p.owner % ctx->nranks == ctx->rank) gens[p.generation].push_back(p);
-    for (auto &g : gens) most = std::max(most, g.size());
-    if ((rc = fvi::ensure_workspace(ctx, T, 1))) return rc;
-    (void)most;
-    FV_HIP(ctx->d_scores.ensure((size_t)T * ctx->K));
-    FV_HIP(ctx->d_hval.ensure((size_t)T * fvb::beam_pitch(beam_width)));
-    FV_HIP(ctx->d_hstate.ensure((size_t)T * fvb::beam_pitch(beam_width)));
-    FV_HIP(ctx->d_doubt.ensure((size_t)T * fvb::DOUBT_CAP));
-    FV_HIP(ctx->d_doubt_count.ensure(T));
-    FV_HIP(ctx->d_slot_val.ensure((size_t)T * beam_width));
-    FV_HIP(ctx->d_slot_state.ensure((size_t)T * beam_width));
-    FV_HIP(ctx->d_tie_list.ensure((size_t)T * ctx->K));
-    FV_HIP(ctx->d_tie_count.ensure(4));
-    FV_HIP(ctx->d_cut.ensure((size_t)T * fvb::CUT_W));
-    FV_HIP(hipMemsetAsync(ctx->d_cut.p, 0xFF, (size_t)T * fvb::CUT_W * sizeof(float), ctx->stream));      // NaN: no earlier pass has left a cut here
-    FV_HIP(ctx->d_cand_count.ensure(T));
-    FV_HIP(hipMemsetAsync(ctx->d_cand_count.p, 0, (size_t)T * sizeof(int), ctx->stream));
-    if (const int cap = fvb::cand_cap_for(ctx->K, beam_width)) FV_HIP(ctx->d_cand.ensure((size_t)T * cap));
-    FV_HIP(ctx->d_dupwin.ensure(T));
-    FV_HIP(ctx->d_needfull.ensure(4));
-    FV_HIP(hipMemsetAsync(ctx->d_dupwin.p, 0, (size_t)T * sizeof(int), ctx->stream));
-    if ((rc = beam_tables(ctx))) return rc;
+    const size_t K = (size_t)ctx->K, BP = (size_t)fvb::beam_pitch(beam), cap = (size_t)fvb::cand_cap_for(ctx->K, beam), t = (size_t)T;
+    auto each = [&](auto &&f) {
+        f(ctx->d_scores, t * K); f(ctx->d_hval, t * BP); f(ctx->d_hstate, t * BP);
+        f(ctx->d_doubt, t * fvb::DOUBT_CAP); f(ctx->d_doubt_count, t);
+        f(ctx->d_slot_val, t * beam); f(ctx->d_slot_state, t * beam);
+        f(ctx->d_tie_list, t * K); f(ctx->d_tie_count, (size_t)4);
+        f(ctx->d_cut, t * fvb::CUT_W); f(ctx->d_cand_count, t);
+        if (cap) f(ctx->d_cand, t * cap);
+        f(ctx->d_dupwin, t); f(ctx->d_needfull, (size_t)std::max(4, nseq));
+        if (nseq > 0) f(ctx->d_seqof, t);
+    };
+    if (nseq > 0) {
+        unsigned long long grow = 0, released = 0;
+        auto need = [&](auto &b, size_t n) { if (n > b.n) { grow += (unsigned long long)n * sizeof(*b.p); released += b.bytes(); } };
+        each(need);
+        need(ctx->d_ob, t); need(ctx->d_ans, t); need(ctx->d_bp, t * K);
+        need(ctx->d_rows, (size_t)2 * ctx->nrows); need(ctx->d_pack, fvi::pack_ints(ctx, T, std::max(nseq, 2)));
+        if (grow) {
+            size_t free_b = 0, total_b = 0;
+            FV_HIP(hipMemGetInfo(&free_b, &total_b));
+            if (grow > (unsigned long long)free_b + released) {
+                ctx->detail = "beam batch workspace: " + std::to_string(grow) + " bytes needed (score rows, back-pointers and tie list: " +
+                              std::to_string(16ull * t * K) + "), " + std::to_string((unsigned long long)free_b + released) +
+                              " bytes of device memory free";
+                return FV_ERR_NOMEM;
+            }
+        }
+    }
+    hipError_t first = hipSuccess;
+    each([&](auto &b, size_t n) { if (first == hipSuccess) first = b.ensure(n); });
+    FV_HIP(first);
+    FV_HIP(hipMemsetAsync(ctx->d_cut.p, 0xFF, t * fvb::CUT_W * sizeof(float), ctx->stream));      // NaN: no earlier pass has left a cut here
+    FV_HIP(hipMemsetAsync(ctx->d_cand_count.p, 0, t * sizeof(int), ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_dupwin.p, 0, t * sizeof(int), ctx->stream));
+    return 0;
+}
 
-    const double keep_model_ms = ctx->stats.set_model_ms;
-    ctx->stats = fv_stats{};
-    ctx->stats.set_model_ms = keep_model_ms;
-    ctx->stats.kernel = FV_KERNEL_F64_STREAM;
-    ctx->stats.generations = plan.generations();
-    ctx->stats.table_bytes_per_step = (long long)beam_width * ctx->K * 8;
-
-    if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
+// The generations of a beam decode, after begin_decode: pass lists to the device, then generation by generation.
+int run_beam_generations(fv_ctx *ctx, std::vector<std::vector<fv::Pass>> &gens, int beam_width, int T, int nseq, const int *seq_of)
+{
+    int rc = 0;
     // The passes of a generation run in lock-step, longest first (the active ones are a prefix); the kernels find a
     // pass's rows from its first position, so the whole plan's pass lists go to the device once, before the clock starts.
     std::vector<size_t> pass_off(gens.size(), 0);
@@ -349,7 +377,7 @@ int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_wi
         std::stable_sort(gens[g].begin(), gens[g].end(),
                          [](const fv::Pass &a, const fv::Pass &b) { return a.R - a.L > b.R - b.L; });
         {   // group-major: the passes of stream group q (i % ng == q), longest first, then those of group q + 1
-            const int np = (int)gens[g].size(), ng = beam_groups(ctx, np, beam_width);
+            const int np = (int)gens[g].size(), ng = gen_groups(ctx, g, np, beam_width, nseq);
             std::vector<fv::Pass> byg;
             byg.reserve(gens[g].size());
             for (int q = 0; q < ng; ++q)
@@ -369,16 +397,121 @@ int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_wi
         // Work queued on the auxiliary streams slows every dispatch of the main one while it waits there for its fork
         // event (the command processor keeps re-examining the blocked queues: +2 us per launch, 1 ms over the
         // whole-sequence pass of cfg4).  The host therefore does not run ahead of a serial generation into a forked one.
-        if (g > 0 && beam_groups(ctx, (int)gens[g].size(), beam_width) > 1 && beam_groups(ctx, (int)gens[g - 1].size(), beam_width) == 1)
+        if (g > 0 && gen_groups(ctx, g, (int)gens[g].size(), beam_width, nseq) > 1 &&
+            gen_groups(ctx, g - 1, (int)gens[g - 1].size(), beam_width, nseq) == 1)
             FV_HIP(hipStreamSynchronize(ctx->stream));
-        if ((rc = run_generation_beam(ctx, gens[g], pass_off[g], beam_width, T))) return rc;
+        if ((rc = run_generation_beam(ctx, gens[g], pass_off[g], beam_width, T, gen_groups(ctx, g, (int)gens[g].size(), beam_width, nseq), nseq, seq_of))) return rc;
         if (g == 0) { FV_HIP(hipEventRecord(ctx->ev_top, ctx->stream)); FV_HIP(hipEventRecord(ctx->ev_s1, ctx->stream)); }
     }
+    return 0;
+}
+
+int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_width, int mode, int *path_out, float *score_out)
+{
+    if (!ctx || !ob || !path_out || T < 2 || n_split < 1) return FV_ERR_ARG;
+    if (ctx->K == 0) return FV_ERR_STATE;
+    int rc = beam_admit(ctx, beam_width);
+    if (rc) return rc;
+    for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->M) return FV_ERR_ARG;
+    auto t0 = clk::now();
+    FV_HIP(hipSetDevice(ctx->device));
+    fv::Plan plan;
+    if ((rc = fv::build_plan(T, n_split, mode, ctx->nranks, plan))) return rc;
+    std::vector<std::vector<fv::Pass>> gens(plan.generations());
+    size_t most = 1;
+    for (const fv::Pass &p : plan.passes)
+        if (p.owner < 0 || p.owner % ctx->nranks == ctx->rank) gens[p.generation].push_back(p);
+    for (auto &g : gens) most = std::max(most, g.size());
+    if ((rc = fvi::ensure_workspace(ctx, T, 1))) return rc;
+    (void)most;
+    if ((rc = beam_workspace(ctx, T, beam_width, 0))) return rc;
+    if ((rc = beam_tables(ctx))) return rc;
+
+    const double keep_model_ms = ctx->stats.set_model_ms;
+    ctx->stats = fv_stats{};
+    ctx->stats.set_model_ms = keep_model_ms;
+    ctx->stats.kernel = FV_KERNEL_F64_STREAM;
+    ctx->stats.generations = plan.generations();
+    ctx->stats.table_bytes_per_step = (long long)beam_width * ctx->K * 8;
+
+    if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
+    if ((rc = run_beam_generations(ctx, gens, beam_width, T, 1, nullptr))) return rc;
     ctx->stats.cells = ctx->stats.task_steps * (long long)ctx->K * beam_width;
     ctx->stats.alg_bytes = 4 * ctx->stats.cells;
     return fvi::finish_decode(ctx, plan, T, path_out, score_out, t0, 0, true);
 }
+
+// fv_decode_beam_batch: the forest plan (fv::build_forest, as fv_decode_full_batch) run by the beam generation driver.
+// Every beam buffer is indexed by absolute time, so the passes of different sequences share the lock-step launches as
+// the passes of one sequence's right-hand generations do; what is per sequence is the end pick's score and the tie gate.
+int decode_beam_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split, int beam_width, int mode,
+                           int *path_out, float *score_out, int *status_out)
+{
+    if (!ob || !offsets || !path_out || nseq < 1 || n_split < 1) return FV_ERR_ARG;
+    if (mode != FV_MODE_REFERENCE && mode != FV_MODE_SINGLE_PASS) return FV_ERR_ARG;
+    if (offsets[0] != 0) { ctx->detail = "fv_decode_beam_batch: offsets[0] must be 0"; return FV_ERR_ARG; }
+    std::vector<int> lengths((size_t)nseq);
+    for (int s = 0; s < nseq; ++s) {
+        const long long len = offsets[s + 1] - offsets[s];
+        if (len < 0) { ctx->detail = "fv_decode_beam_batch: offsets decrease at sequence " + std::to_string(s); return FV_ERR_ARG; }
+        if (len < 2) { ctx->detail = "fv_decode_beam_batch: sequence " + std::to_string(s) + " has fewer than 2 observations"; return FV_ERR_ARG; }
+        if (offsets[s + 1] > 0x7fffffffLL) { ctx->detail = "fv_decode_beam_batch: more than 2^31 - 1 observations in all (at sequence " + std::to_string(s) + ")"; return FV_ERR_ARG; }
+        lengths[(size_t)s] = (int)len;
+    }
+    if (ctx->K == 0) return FV_ERR_STATE;
+    int rc = beam_admit(ctx, beam_width);
+    if (rc) return rc;
+    for (int s = 0; s < nseq; ++s)
+        for (long long j = offsets[s]; j < offsets[s + 1]; ++j)
+            if (ob[j] < 0 || ob[j] >= ctx->M) {
+                ctx->detail = "fv_decode_beam_batch: sequence " + std::to_string(s) + " holds a symbol outside [0, M) at position " + std::to_string(j - offsets[s]);
+                return FV_ERR_ARG;
+            }
+    auto t0 = clk::now();
+    const int sumT = (int)offsets[nseq];
+    fv::Plan plan;
+    int bad = -1;
+    if ((rc = fv::build_forest(lengths.data(), nseq, n_split, mode, plan, &bad))) {
+        ctx->detail = "fv_decode_beam_batch: sequence " + std::to_string(bad) + " of length " + std::to_string(lengths[(size_t)std::max(bad, 0)]) +
+                      " has no plan for n_split = " + std::to_string(n_split) + " (T == 2 * n_split with n_split > 2)";
+        return rc;
+    }
+    std::vector<std::vector<fv::Pass>> gens(plan.generations());
+    for (const fv::Pass &p : plan.passes) gens[p.generation].push_back(p);
+    FV_HIP(hipSetDevice(ctx->device));
+    if ((rc = beam_workspace(ctx, sumT, beam_width, nseq))) return rc;           // (checks the whole working set first)
+    if ((rc = fvi::ensure_workspace(ctx, sumT, 1, std::max(nseq, 2)))) return rc;
+    if ((rc = beam_tables(ctx))) return rc;
+
+    const double keep_model_ms = ctx->stats.set_model_ms;
+    ctx->stats = fv_stats{};
+    ctx->stats.set_model_ms = keep_model_ms;
+    ctx->stats.kernel = FV_KERNEL_F64_STREAM;
+    ctx->stats.generations = plan.generations();
+    ctx->stats.table_bytes_per_step = (long long)beam_width * ctx->K * 8;
+
+    if ((rc = fvi::begin_decode(ctx, ob, sumT))) return rc;
+    // time -> sequence: how heap_build_all and tie_fixup find the gate of a step (4 bytes per observation)
+    ctx->h_seqof.resize((size_t)sumT);
+    for (int s = 0; s < nseq; ++s) std::fill(ctx->h_seqof.begin() + offsets[s], ctx->h_seqof.begin() + offsets[s + 1], s);
+    FV_HIP(hipMemcpyAsync(ctx->d_seqof.p, ctx->h_seqof.data(), (size_t)sumT * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = run_beam_generations(ctx, gens, beam_width, sumT, nseq, ctx->d_seqof.p))) return rc;
+    ctx->stats.cells = ctx->stats.task_steps * (long long)ctx->K * beam_width;
+    ctx->stats.alg_bytes = 4 * ctx->stats.cells;
+    return fvi::finish_decode_batch(ctx, offsets, nseq, path_out, score_out, status_out, t0, 0, true);
+}
 }  // namespace
+
+extern "C" int fv_decode_beam_batch(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split, int beam_width,
+                                    int mode, int *path_out, float *score_out, int *status_out)
+{
+    if (!ctx) return FV_ERR_ARG;
+    if (ctx->group || ctx->comm || ctx->nranks > 1) {
+        ctx->detail = "fv_decode_beam_batch: one device, no communicator and no partition (sequences are not dealt to ranks)";
+        return FV_ERR_UNSUPPORTED;
+    }
+    return fvi::drained(ctx, decode_beam_batch_impl(ctx, ob, offsets, nseq, n_split, beam_width, mode, path_out, score_out, status_out));
+}
 
 namespace {
 // fv_test_beam_step (include/flashvit_testing.h): one launch of the beam step kernel over caller-given slot sets.  Set q

@@ -733,7 +733,9 @@ struct HeapAllArgs {
     float *slot_val;           // [T][B]   exact heap layout per step, slot order
     int *slot_state;           // [T][B]
     unsigned long long *err_counter;   // broken producer/consumer hand-shake (never expected)
-    const int *gate;                   // nullptr, or: run only if *gate != 0 (the back-track met a tied cell)
+    const int *gate;                   // nullptr, or: run only if the flag of the range's sequence is up (its back-track met a tied cell)
+    const int *seq_of;                 // batch decode: [total T] sequence of every absolute time (the flags are per sequence);
+                                       // nullptr: one sequence, one flag
     int K, beam, n;
     HeapRange p[HEAP_CHUNK];
 };
@@ -743,8 +745,8 @@ struct HeapAllArgs {
 __global__ __launch_bounds__(128) void heap_build_all(const HeapAllArgs args)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    if (args.gate && *args.gate == 0) return;
     const HeapRange r = args.p[blockIdx.y];
+    if (args.gate && args.gate[args.seq_of ? args.seq_of[r.L] : 0] == 0) return;
     const int j = r.L + (int)blockIdx.x;
     if (j > r.R) return;
     const int B = args.beam;
@@ -1445,9 +1447,9 @@ __global__ __launch_bounds__(SEL_BLOCK) void topb_select_cand(const SelArgs args
 //           last heap, so that step's scores must be exact; any other pass asks whether its fixed end state is a MEMBER
 //           of its last heap (Find_T3_State, FLASH_BS:73-86) — undecided only if that state is one of the theta-valued
 //           duplicates of a speculative list, in which case the last step is decided now.
-//   mode 1  (only if *gate != 0: the back-tracked path met a tied cell, every layout is about to be rebuilt) every
-//           step's scores exact.
-struct BeamEnd { int L, R, whole; };
+//   mode 1  (only if the flag of the pass's sequence is up: its back-tracked path met a tied cell, every layout of the
+//           sequence is about to be rebuilt) every step's scores exact.
+struct BeamEnd { int L, R, whole, seq; };   // seq: the sequence the pass belongs to (fv_decode_beam_batch; else 0) — its flag, its score
 struct ResolveArgs {
     ResolveCtx rc;
     int mode, n;
@@ -1464,7 +1466,7 @@ __global__ __launch_bounds__(RESOLVE_BLOCK) void beam_resolve(const ResolveArgs 
     const BeamEnd p = args.p[blockIdx.x];
     constexpr int NW = RESOLVE_BLOCK / 64;
     if (args.mode == 1) {
-        if (args.gate && *args.gate == 0) return;
+        if (args.gate && args.gate[p.seq] == 0) return;
         resolve_range(c, p.L, p.L + 1, p.R, smem, &bcast, NW);
         return;
     }
@@ -1530,6 +1532,8 @@ struct FixArgs {
     int *bp;                   // [T][K]
     unsigned long long *total; // statistics: cells re-decided, summed over the generations of a decode
     const int *gate;           // nullptr, or: run only if *gate != 0
+    const int *seq_of;         // batch decode: [total T] sequence of every absolute time — gate[seq_of[j]] decides per listed
+                               // cell (j, i), and `total` counts the cells re-decided; nullptr: one sequence, one flag
     int K, ld, beam;
 };
 
@@ -1537,9 +1541,11 @@ struct FixArgs {
 // strict '>' (FLASH_BS:440-446) and store the state of the winning slot.  One wave per cell.
 __global__ __launch_bounds__(256) void tie_fixup(const FixArgs args)
 {
-    if (args.gate && *args.gate == 0) return;
+    const bool per_seq = args.gate && args.seq_of;
+    if (args.gate && !per_seq && *args.gate == 0) return;
     const unsigned int n = min(*args.tie_count, args.tie_cap);
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(args.total, (unsigned long long)n);
+    if (!per_seq && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(args.total, (unsigned long long)n);
+    unsigned int mine = 0;             // per_seq: cells this wave re-decided
     const int lane = threadIdx.x & 63;
     const unsigned int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const unsigned int nwaves = gridDim.x * (blockDim.x >> 6);
@@ -1547,6 +1553,10 @@ __global__ __launch_bounds__(256) void tie_fixup(const FixArgs args)
     for (unsigned int e = wave; e < n; e += nwaves) {
         const int2 cell = args.tie_list[e];
         const int j = cell.x, i = cell.y;
+        if (per_seq) {                 // (wave-uniform: one cell per wave)
+            if (args.gate[args.seq_of[j]] == 0) continue;
+            ++mine;
+        }
         const float tmp = args.LB32T[(size_t)args.ob[j] * args.K + i];
         const double *Lt = args.LA64R + i;
         const float *sv = args.slot_val + (size_t)(j - 1) * B;
@@ -1580,13 +1590,15 @@ __global__ __launch_bounds__(256) void tie_fixup(const FixArgs args)
         }
         if (lane == 0 && best > -FLT_MAX) args.bp[(size_t)j * args.K + i] = ss[arg];
     }
+    if (per_seq && lane == 0 && mine) atomicAdd(args.total, (unsigned long long)mine);
 }
 
 struct BeamEndArgs {
     int K, beam, n;
-    int lazy;          // 1: first attempt, on provisional back-pointers: a tied cell on the path raises *flag and ends the walk
-                       // 0: after tie_fixup; runs only if *flag != 0
-    int *flag;
+    int lazy;          // 1: first attempt, on provisional back-pointers: a tied cell on the path raises the flag of the pass's
+                       //    sequence (flag[p.seq]) and ends the walk
+                       // 0: after tie_fixup; runs only if that flag is up
+    int *flag;         // one per sequence of the call
     BeamEnd p[BEAM_CHUNK];
 };
 
@@ -1599,11 +1611,14 @@ struct BeamEndArgs {
 // (heap_build_all + tie_fixup: a full replay per step, 5 % of cfg4) is needed only if the PATH runs through such a cell
 // — 0.03 % of the cells at cfg4 — so the walk is first tried on the provisional pointers (lazy = 1); if it meets a
 // tagged cell it raises the flag, and the gated heap_build_all / tie_fixup / second walk (queued behind it) do the work.
+// In a batch decode the flags are per sequence (a tie on one sequence's path rebuilds that sequence's layouts only) and
+// the whole-sequence pass of sequence s writes score_out[s].
 __global__ __launch_bounds__(64) void beam_end_backtrack(const BeamEndArgs args, const float *slot_val, const int *slot_state,
                                                          const int *member_state, const float *cut, const int *bp, int *ans, float *score_out)
 {
-    if (!args.lazy && *args.flag == 0) return;
     const BeamEnd &p = args.p[blockIdx.x];
+    int *const flag = args.flag + p.seq;
+    if (!args.lazy && *flag == 0) return;
     const int B = args.beam, lane = threadIdx.x;
     int stt;
     if (p.whole) {
@@ -1623,7 +1638,7 @@ __global__ __launch_bounds__(64) void beam_end_backtrack(const BeamEndArgs args,
             if (fvk::better(ov, ok, score, arg)) { score = ov; arg = ok; }
         }
         stt = hstate[arg];
-        if (lane == 0) { ans[p.R] = stt; *score_out = score; }
+        if (lane == 0) { ans[p.R] = stt; score_out[p.seq] = score; }
     } else {
         // members of the last heap: B entries, or the scores above the cut plus every cut-valued duplicate while the
         // step is still speculative (beam_resolve has decided it if `want` is one of those duplicates)
@@ -1647,7 +1662,7 @@ __global__ __launch_bounds__(64) void beam_end_backtrack(const BeamEndArgs args,
         for (int j = p.R; j > p.L; --j) {
             bool tag = false;
             stt = hop(stt, j, tag);
-            if (tag && args.lazy) { atomicExch(args.flag, 1); return; }      // (not lazy: tie_fixup has rewritten every listed cell)
+            if (tag && args.lazy) { atomicExch(flag, 1); return; }      // (not lazy: tie_fixup has rewritten every listed cell)
             ans[j - 1] = stt;
         }
         return;
@@ -1679,7 +1694,7 @@ __global__ __launch_bounds__(64) void beam_end_backtrack(const BeamEndArgs args,
         exact = __shfl(y, f - 1);
         base = f;
     }
-    if (met_tag && args.lazy && lane == 0) atomicExch(args.flag, 1);
+    if (met_tag && args.lazy && lane == 0) atomicExch(flag, 1);
 }
 
 static inline int allow_big_lds(std::string &detail)

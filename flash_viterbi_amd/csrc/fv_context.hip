@@ -32,18 +32,20 @@ size_t device_bytes(const fv_ctx *c)
            c->d_ob.bytes() + c->d_ans.bytes() + c->d_bp.bytes() + c->d_gather.bytes() + c->d_rows.bytes() + c->d_ckpt.bytes() +
            c->d_score.bytes() + c->d_counters.bytes() + c->d_hval.bytes() + c->d_scores.bytes() +
            c->d_hstate.bytes() + c->d_flags.bytes() + c->d_slot_val.bytes() + c->d_slot_state.bytes() +
-           c->LA64R.bytes() + c->LAQ16R.bytes() + c->d_qaux.bytes() + c->d_tie_list.bytes() + c->d_tie_count.bytes() + c->d_cut.bytes() + c->d_dupwin.bytes() + c->d_cand.bytes() + c->d_cand_count.bytes() + c->d_passL.bytes() + c->d_needfull.bytes() + c->d_doubt.bytes() + c->d_doubt_count.bytes() + c->d_pack.bytes();
+           c->LA64R.bytes() + c->LAQ16R.bytes() + c->d_qaux.bytes() + c->d_tie_list.bytes() + c->d_tie_count.bytes() + c->d_cut.bytes() + c->d_dupwin.bytes() + c->d_cand.bytes() + c->d_cand_count.bytes() + c->d_passL.bytes() + c->d_needfull.bytes() + c->d_seqof.bytes() + c->d_doubt.bytes() + c->d_doubt_count.bytes() + c->d_pack.bytes();
 }
 
 // ints in front of the answers in the result block: the counters (64-bit each), then the scores (one per sequence of a
 // batch decode) padded to a multiple of four
 inline size_t pack_head(int nscores) { return 2 * FV_NCOUNTERS + (size_t)std::max(4, round_up(nscores, 4)); }
 
+// result block + the staged observations
+size_t pack_ints(const fv_ctx *ctx, int T, int nscores) { return pack_head(nscores) + (size_t)T * std::max(1, ctx->nranks) + (size_t)T; }
+
 int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed, int nscores)
 {
     const size_t want_rows = rows_needed * 2 * (size_t)ctx->nrows;
-    // result block + the staged observations
-    const size_t want_pack = pack_head(nscores) + (size_t)T * std::max(1, ctx->nranks) + (size_t)T;
+    const size_t want_pack = pack_ints(ctx, T, nscores);
     if (nscores > 1) {
         // A batch's working set grows with the total length (arg rows: T * K int32): sized in 64 bits and compared with
         // what the device has free (plus what growing a buffer releases first) before anything is allocated.
@@ -197,10 +199,11 @@ int finish_decode(fv_ctx *ctx, const fv::Plan &plan, int T, int *path_out, float
     return FV_OK;
 }
 
-// Epilogue of fv_decode_full_batch: every sequence's answers, the nseq scores and the counters in one block, one
-// device-to-host copy, one sync; the scan for entries without a predecessor is per sequence.
+// Epilogue of fv_decode_full_batch / fv_decode_beam_batch: every sequence's answers, the nseq scores and the counters in
+// one block, one device-to-host copy, one sync; the scan for entries without a predecessor (beam: after a beam miss) is
+// per sequence.  Return: the most negative status, else the largest (FV_WARN_BEAM_MISS), else 0.
 int finish_decode_batch(fv_ctx *ctx, const long long *offsets, int nseq, int *path_out, float *score_out, int *status_out,
-                        clk::time_point t0, size_t nprof)
+                        clk::time_point t0, size_t nprof, bool beam)
 {
     const size_t nans = (size_t)offsets[nseq], head = pack_head(nseq), total = head + nans;
     FV_HIP(hipEventRecord(ctx->ev_stop, ctx->stream));
@@ -216,15 +219,16 @@ int finish_decode_batch(fv_ctx *ctx, const long long *offsets, int nseq, int *pa
     std::memcpy(path_out, ctx->h_pin + head, nans * sizeof(int));
     if (score_out) std::memcpy(score_out, ctx->h_pin + 2 * FV_NCOUNTERS, (size_t)nseq * sizeof(float));
     if (int rc = read_stats(ctx, counters, t0, nprof)) return rc;
-    int worst = FV_OK;
+    int worst = FV_OK, warn = FV_OK;
     for (int s = 0; s < nseq; ++s) {
         bool neg = false;
         for (long long j = offsets[s]; j < offsets[s + 1]; ++j) neg |= path_out[j] < 0;
-        const int st = neg ? FV_ERR_NO_PRED : FV_OK;
+        const int st = !neg ? FV_OK : beam ? FV_WARN_BEAM_MISS : FV_ERR_NO_PRED;
         if (status_out) status_out[s] = st;
         worst = std::min(worst, st);
+        warn = std::max(warn, st);
     }
-    return worst;
+    return worst < 0 ? worst : warn;
 }
 
 // A decode that fails after its first enqueue must not leave kernels running on ctx->stream: the next call
@@ -301,7 +305,7 @@ extern "C" void fv_destroy(fv_ctx *ctx)
     ctx->d_ob.release(); ctx->d_ans.release(); ctx->d_bp.release(); ctx->d_gather.release(); ctx->d_rows.release(); ctx->d_ckpt.release();
     ctx->d_score.release(); ctx->d_counters.release(); ctx->d_hval.release(); ctx->d_scores.release();
     ctx->d_hstate.release(); ctx->d_flags.release(); ctx->d_slot_val.release(); ctx->d_slot_state.release();
-    ctx->LA64R.release(); ctx->LAQ16R.release(); ctx->d_qaux.release(); ctx->d_tie_list.release(); ctx->d_tie_count.release(); ctx->d_cut.release(); ctx->d_dupwin.release(); ctx->d_cand.release(); ctx->d_cand_count.release(); ctx->d_passL.release(); ctx->d_needfull.release(); ctx->d_doubt.release(); ctx->d_doubt_count.release(); ctx->d_pack.release();
+    ctx->LA64R.release(); ctx->LAQ16R.release(); ctx->d_qaux.release(); ctx->d_tie_list.release(); ctx->d_tie_count.release(); ctx->d_cut.release(); ctx->d_dupwin.release(); ctx->d_cand.release(); ctx->d_cand_count.release(); ctx->d_passL.release(); ctx->d_needfull.release(); ctx->d_seqof.release(); ctx->d_doubt.release(); ctx->d_doubt_count.release(); ctx->d_pack.release();
     if (ctx->h_pin) { (void)hipHostFree(ctx->h_pin); ctx->h_pin = nullptr; ctx->h_pin_n = 0; }
     for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
@@ -564,7 +568,7 @@ extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
         // the timing build only (libflashvit_timing.so, tools/).  Every bit this library accepts is speed-only.
         if (value & FV_DEBUG_TIMING_ONLY) { ctx->detail = "FV_OPT_DEBUG: result-changing timing switches need the timing build"; return FV_ERR_ARG; }
 #endif
-        if (value < 0 || value >= (1ll << 29) || (value & (1ll << 27))) return FV_ERR_ARG;      // (bit 27 is not assigned)
+        if (value < 0 || value >= (1ll << 30) || (value & (1ll << 27))) return FV_ERR_ARG;      // (bit 27 is not assigned)
         ctx->opt_debug = (int)value; return FV_OK;
     default: return FV_ERR_ARG;
     }

@@ -101,7 +101,10 @@ struct fv_ctx {
     float opt_sel_margin = 0.3f; // FV_OPT_SEL_MARGIN (in 1/1000): starting margin of the predicted cut bound in beam spreads
     DevBuf<int> d_dupwin;        // [T]
     DevBuf<int> d_doubt, d_doubt_count;   // [T][DOUBT_CAP] columns of step j won by an undecided cut duplicate of step j - 1, [T] their number
-    DevBuf<int> d_needfull;      // [1] a pass's back-track met a tied cell: rebuild the layouts of the generation (beam_end_backtrack)
+    DevBuf<int> d_needfull;      // [sequences of the call] a pass's back-track met a tied cell: rebuild the layouts of its sequence's
+                                 // passes of the generation (beam_end_backtrack); one flag for fv_decode_beam
+    DevBuf<int> d_seqof;         // fv_decode_beam_batch: [total T] sequence of every absolute time (heap_build_all, tie_fixup)
+    std::vector<int> h_seqof;
     DevBuf<int> d_passL;         // first position of every pass of the generation in flight (beam decodes)
     std::vector<int> h_passL;
     DevBuf<unsigned int> d_tie_count;
@@ -167,11 +170,14 @@ int upload_tables(fv_ctx *ctx, const HostTables &h);
 size_t device_bytes(const fv_ctx *c);
 // (nscores > 1: a batch decode — room for that many scores, sizes checked against free device memory first)
 int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed, int nscores = 1);
+// ints of the result block (and of the pinned host block) a decode of T observations with nscores scores needs
+size_t pack_ints(const fv_ctx *ctx, int T, int nscores);
 // decode epilogue: (multi-rank: all-gather + merge,) path / score / counters to the host, one sync, statistics
 int finish_decode(fv_ctx *ctx, const fv::Plan &plan, int T, int *path_out, float *score_out, clk::time_point t0,
                   size_t nprof, bool beam);
+// (beam: a sequence whose path holds -1 reports FV_WARN_BEAM_MISS instead of FV_ERR_NO_PRED)
 int finish_decode_batch(fv_ctx *ctx, const long long *offsets, int nseq, int *path_out, float *score_out, int *status_out,
-                        clk::time_point t0, size_t nprof);
+                        clk::time_point t0, size_t nprof, bool beam = false);
 int drained(fv_ctx *ctx, int rc);
 // decode prologue: observation sequence to the device (through the pinned block), counters and answers cleared
 int begin_decode(fv_ctx *ctx, const int *ob, int T);

@@ -18,6 +18,7 @@ KERNEL_U16_REFINE = 6
 OPT_KERNEL, OPT_MAX_BATCH, OPT_PROFILE, OPT_SEL_MARGIN, OPT_DEBUG = 1, 2, 3, 4, 100
 DEBUG_TIMING_ONLY = (1 << 0) | (1 << 4) | (1 << 5) | (1 << 11) | (1 << 12)      # refused by the shipped library
 DEBUG_BATCH_GEN0_SERIAL = 1 << 28      # decode_full_batch: the whole-sequence passes on one stream (speed only)
+DEBUG_BEAM_BATCH_GEN0_OTHER = 1 << 29  # decode_beam_batch: the whole-sequence passes in the launch form that is not the default (speed only)
 WARN_BEAM_MISS = 1
 ERR_ARG, ERR_NOMEM, ERR_NO_PRED, ERR_DEVICE, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 UNIQUE_ID_BYTES = 128
@@ -53,7 +54,7 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_decode_vanilla", "fv_decode_checkpoint", "fv_checkpoint_memory_bytes",
            "fv_last_stats", "fv_strerror", "fv_last_error_detail", "fv_reference_memory_bytes",
            "fv_comm_unique_id", "fv_comm_init", "fv_plan_passes", "fv_merge_paths", "fv_set_partition",
-           "fv_create_multi", "fv_device_count", "fv_decode_full_batch", "fv_plan_passes_batch"]
+           "fv_create_multi", "fv_device_count", "fv_decode_full_batch", "fv_plan_passes_batch", "fv_decode_beam_batch"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step"]
 TIE_TAG = 1 << 30
@@ -93,6 +94,7 @@ def load_library():
     L.fv_decode_full.argtypes = [vp, vp, ci, ci, ci, vp, vp]
     L.fv_decode_beam.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
     L.fv_decode_full_batch.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
+    L.fv_decode_beam_batch.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]
     L.fv_plan_passes_batch.argtypes = [vp, ci, ci, ci, ctypes.POINTER(PassInfo), ci]
     L.fv_decode_vanilla.argtypes = [vp, vp, ci, vp, vp]
     L.fv_decode_checkpoint.argtypes = [vp, vp, ci, ci, vp, vp]
@@ -247,6 +249,23 @@ class FlashViterbi:
         score = ctypes.c_float(0)
         rc = self._check(self._L.fv_decode_beam(self._h, _p(ob), ob.size, n_split, beam, mode, _p(path), ctypes.byref(score)))
         return path, np.float32(score.value), rc
+
+    def decode_beam_batch(self, obs, n_split, beam, mode=MODE_REFERENCE):
+        """fv_decode_beam_batch: obs is a list of int sequences (lengths may differ) for the model of this context.
+        Returns (paths: list of int32 arrays, scores: float32 array, statuses: int32 array), per sequence what
+        decode_beam returns for it alone: a sequence with a beam miss reports WARN_BEAM_MISS in `statuses` and its path
+        holds the -1 entries.  Negative returns raise FlashVitError."""
+        seqs = [np.ascontiguousarray(o, dtype=np.int32).reshape(-1) for o in obs]
+        offsets = np.zeros(len(seqs) + 1, dtype=np.int64)
+        if seqs:
+            offsets[1:] = np.cumsum([o.size for o in seqs])
+        ob = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.int32)
+        path = np.empty(max(ob.size, 1), dtype=np.int32)
+        scores = np.zeros(len(seqs), dtype=np.float32)
+        statuses = np.zeros(len(seqs), dtype=np.int32)
+        self._check(self._L.fv_decode_beam_batch(self._h, _p(ob), _p(offsets), len(seqs), n_split, beam, mode, _p(path),
+                                                 _p(scores), _p(statuses)))
+        return [path[offsets[s]:offsets[s + 1]].copy() for s in range(len(seqs))], scores, statuses
 
     def decode_vanilla(self, ob):
         ob = np.ascontiguousarray(ob, dtype=np.int32)

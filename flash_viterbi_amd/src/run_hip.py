@@ -18,6 +18,8 @@ compiled from the reference's own sources — that checker lives outside this pa
                                           # (any length >= 2), and one `path: [...]` line per file is printed, in order,
                                           # after a `time:` line for the whole batch.  Exit status 3 if a decode failed;
                                           # a sequence without a finite predecessor prints its path with the -1 entries.
+  python3 run_hip.py --batch-bs OB_FILE...  # the same through FLASH-BS: ONE fv_decode_beam_batch call with parameters[0]'s
+                                          # BeamSearchWidth; a sequence with a beam miss prints its path with the -1 entries.
 """
 import csv
 import hashlib
@@ -112,8 +114,9 @@ def path_md5(path_tokens):
     return hashlib.md5((" ".join(str(x) for x in path_tokens)).encode()).hexdigest()
 
 
-def run_batch(files):
-    """--batch: the full-state FLASH decode of every file's sequence against parameters[0]'s model, one library call."""
+def run_batch(files, beam=False):
+    """--batch: the full-state FLASH decode of every file's sequence against parameters[0]'s model, one library call;
+    --batch-bs (beam): the FLASH-BS decode with parameters[0]'s BeamSearchWidth."""
     import time
 
     import numpy as np
@@ -132,10 +135,13 @@ def run_batch(files):
     try:
         fv.set_model(A, B, Pi)
         t0 = time.perf_counter()
-        paths, scores, statuses = fv.decode_full_batch(obs, p["MAX_THREADS"])
+        if beam:
+            paths, scores, statuses = fv.decode_beam_batch(obs, p["MAX_THREADS"], p["BeamSearchWidth"])
+        else:
+            paths, scores, statuses = fv.decode_full_batch(obs, p["MAX_THREADS"])
         dt = time.perf_counter() - t0
     except decoder.FlashVitError as e:
-        print(f"fv_decode_full_batch: {e}", file=sys.stderr)
+        print(f"{'fv_decode_beam_batch' if beam else 'fv_decode_full_batch'}: {e}", file=sys.stderr)
         return 3
     finally:
         fv.close()
@@ -148,15 +154,16 @@ def run_batch(files):
 
 
 def main():
-    if "--batch" in sys.argv:
-        i = sys.argv.index("--batch")
+    if "--batch" in sys.argv or "--batch-bs" in sys.argv:
+        flag = "--batch" if "--batch" in sys.argv else "--batch-bs"
+        i = sys.argv.index(flag)
         files = [a for a in sys.argv[i + 1:] if not a.startswith("--")]
         if not files:
-            print("--batch needs at least one observation file", file=sys.stderr)
+            print(f"{flag} needs at least one observation file", file=sys.stderr)
             sys.exit(2)
         fvbuild.build_host()
         fvbuild.build_hip()
-        sys.exit(run_batch(files))
+        sys.exit(run_batch(files, beam=flag == "--batch-bs"))
     os.makedirs(result_path, exist_ok=True)
     os.makedirs(data_path, exist_ok=True)
     fvbuild.build_host()

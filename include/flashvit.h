@@ -71,7 +71,8 @@ enum {
                                kernel for every batched launch, 18 right-hand generations on one stream, 21 F64 / F32 / F16 / Q16
                                kernels in three slabs of source rows (the route of K > 65536) at any size, 28 fv_decode_full_batch: the whole-sequence
                                passes (generation 0) in single-stream launches of up to FV_OPT_MAX_BATCH tasks instead of the
-                               three-stream, four-task form (bit 27 is not assigned and refused).  FLASH-BS: 7 the cut predictor uses the pass's own
+                               three-stream, four-task form (bit 27 is not assigned and refused).  FLASH-BS: 29 fv_decode_beam_batch: the whole-sequence passes
+                               (generation 0) in the launch form that is not the default (one stream / dealt to the four stream groups), 7 the cut predictor uses the pass's own
                                cuts only, 8 / 9
                                float64 / 16-bit step kernel always, 10 no candidate lists, 15 whole-workgroup select for short
                                lists too, 16 / 17 pass groups on one stream / on four streams whatever the size, 19 every heap
@@ -196,6 +197,22 @@ int fv_decode_full_batch(fv_ctx *ctx, const int *ob, const long long *offsets, i
  * BeamSearchWidth = beam_width (2 <= beam_width <= K). */
 int fv_decode_beam(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_width, int mode,
                    int *path_out, float *score_out);
+
+/* nseq observation sequences through FLASH-BS in one call: the layout contract of fv_decode_full_batch (sequences back
+ * to back, offsets[0] == 0, nseq + 1 non-decreasing entries, ragged lengths, the total below 2^31; score_out and
+ * status_out may be NULL).  Per sequence s exactly what fv_decode_beam(ctx, ob + offsets[s], T_s, n_split, beam_width,
+ * mode, ...) delivers: the path including the -1 entries after a beam miss, the float32 score, and in status_out[s] that
+ * call's return code (FV_OK or FV_WARN_BEAM_MISS).  Return: the most negative per-sequence status if any is negative,
+ * else FV_WARN_BEAM_MISS if any sequence has it, else 0.  The passes of all sequences run in lock-step and share the
+ * step and select launches; the "path met a tied cell" gate that triggers the exact heap rebuilds is per sequence.
+ * Refused before any device work, with the sequence index in fv_last_error_detail: T_s < 2, a symbol outside [0,M),
+ * T_s == 2*n_split with n_split > 2; also a beam_width fv_decode_beam refuses, bad pointers / offsets / mode, nseq < 1
+ * (FV_ERR_ARG), no model (FV_ERR_STATE), a context with a communicator, a partition or several devices
+ * (FV_ERR_UNSUPPORTED), and a working set beyond the free device memory (FV_ERR_NOMEM with the byte count; the
+ * per-step buffers grow with the total length: about 16 bytes per (observation, state) — DESIGN.md 5.4b).
+ * fv_last_stats reports the batch as one decode (counters are totals, `generations` the largest of any sequence). */
+int fv_decode_beam_batch(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split,
+                         int beam_width, int mode, int *path_out, float *score_out, int *status_out);
 
 /* GPU form of the reference's baseline programs Base_line/C implementations/vanilla Viterbi.c:125-173 and
  * checkpoint Viterbi.c (same recurrence, hence the same output): one forward pass with the BASELINE's
