@@ -276,6 +276,7 @@ extern "C" int fv_decode_beam(fv_ctx *ctx, const int *ob, int T, int n_split, in
                               int *path_out, float *score_out)
 {
     if (!ctx) return FV_ERR_ARG;
+    if (ctx->csr) { ctx->detail = "fv_decode_beam: not available on a model set by fv_set_model_sparse (the beam kernels gather dense rows)"; return FV_ERR_UNSUPPORTED; }
     if (ctx->group && ctx->group_rank == 0) {
         if (!path_out || T < 2) return FV_ERR_ARG;
         return fvi::group_run(ctx, T, path_out, score_out, [&](fv_ctx *m, int *path, float *score) {
@@ -506,6 +507,7 @@ extern "C" int fv_decode_beam_batch(fv_ctx *ctx, const int *ob, const long long 
                                     int mode, int *path_out, float *score_out, int *status_out)
 {
     if (!ctx) return FV_ERR_ARG;
+    if (ctx->csr) { ctx->detail = "fv_decode_beam_batch: not available on a model set by fv_set_model_sparse (the beam kernels gather dense rows)"; return FV_ERR_UNSUPPORTED; }
     if (ctx->group || ctx->comm || ctx->nranks > 1) {
         ctx->detail = "fv_decode_beam_batch: one device, no communicator and no partition (sequences are not dealt to ranks)";
         return FV_ERR_UNSUPPORTED;
@@ -618,6 +620,7 @@ extern "C" int fv_test_beam_step(fv_ctx *ctx, int beam, const fv_test_beam_set *
 {
     if (!ctx) return FV_ERR_ARG;
     if (fvi::group_size(ctx) > 1) { ctx->detail = "fv_test_beam_step: one device per context"; return FV_ERR_ARG; }
+    if (ctx->csr) { ctx->detail = "fv_test_beam_step: not available on a model set by fv_set_model_sparse"; return FV_ERR_UNSUPPORTED; }
     return fvi::drained(ctx, test_beam_step_impl(ctx, beam, sets, nsets, sym, speculative, theta, next_bound, cand_cap, scores_out,
                                                  bp_out, ties_out, tie_count_out, doubt_out, doubt_counts, cand_out, cand_counts,
                                                  variants_out));

@@ -32,7 +32,8 @@ size_t device_bytes(const fv_ctx *c)
            c->d_ob.bytes() + c->d_ans.bytes() + c->d_bp.bytes() + c->d_gather.bytes() + c->d_rows.bytes() + c->d_ckpt.bytes() +
            c->d_score.bytes() + c->d_counters.bytes() + c->d_hval.bytes() + c->d_scores.bytes() +
            c->d_hstate.bytes() + c->d_flags.bytes() + c->d_slot_val.bytes() + c->d_slot_state.bytes() +
-           c->LA64R.bytes() + c->LAQ16R.bytes() + c->d_qaux.bytes() + c->d_tie_list.bytes() + c->d_tie_count.bytes() + c->d_cut.bytes() + c->d_dupwin.bytes() + c->d_cand.bytes() + c->d_cand_count.bytes() + c->d_passL.bytes() + c->d_needfull.bytes() + c->d_seqof.bytes() + c->d_doubt.bytes() + c->d_doubt_count.bytes() + c->d_pack.bytes();
+           c->LA64R.bytes() + c->LAQ16R.bytes() + c->d_qaux.bytes() + c->d_tie_list.bytes() + c->d_tie_count.bytes() + c->d_cut.bytes() + c->d_dupwin.bytes() + c->d_cand.bytes() + c->d_cand_count.bytes() + c->d_passL.bytes() + c->d_needfull.bytes() + c->d_seqof.bytes() + c->d_doubt.bytes() + c->d_doubt_count.bytes() + c->d_pack.bytes() +
+           c->CSk.bytes() + c->CSq.bytes() + c->CS64.bytes() + c->CSoff.bytes() + c->CSnwb.bytes() + c->CRptr.bytes() + c->CRcol.bytes() + c->CRlog.bytes();
 }
 
 // ints in front of the answers in the result block: the counters (64-bit each), then the scores (one per sequence of a
@@ -306,6 +307,7 @@ extern "C" void fv_destroy(fv_ctx *ctx)
     ctx->d_score.release(); ctx->d_counters.release(); ctx->d_hval.release(); ctx->d_scores.release();
     ctx->d_hstate.release(); ctx->d_flags.release(); ctx->d_slot_val.release(); ctx->d_slot_state.release();
     ctx->LA64R.release(); ctx->LAQ16R.release(); ctx->d_qaux.release(); ctx->d_tie_list.release(); ctx->d_tie_count.release(); ctx->d_cut.release(); ctx->d_dupwin.release(); ctx->d_cand.release(); ctx->d_cand_count.release(); ctx->d_passL.release(); ctx->d_needfull.release(); ctx->d_seqof.release(); ctx->d_doubt.release(); ctx->d_doubt_count.release(); ctx->d_pack.release();
+    fvi::release_csr(ctx);
     if (ctx->h_pin) { (void)hipHostFree(ctx->h_pin); ctx->h_pin = nullptr; ctx->h_pin_n = 0; }
     for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
@@ -323,6 +325,26 @@ extern "C" void fv_destroy(fv_ctx *ctx)
 }
 
 namespace fvi {
+
+// log B (transposed: one row per symbol) and log Pi, with the value checks fv_set_model and fv_set_model_sparse share
+static void log_emissions(const float *B, const float *Pi, int K, int M, HostTables &h, bool &ok_range, bool &any_big)
+{
+    h.b64.assign((size_t)M * K, 0.0); h.pi64.assign(K, 0.0);
+    h.b32.assign((size_t)M * K, 0.0f);
+    for (int i = 0; i < K; ++i) {
+        for (int o = 0; o < M; ++o) {
+            const float x = B[(size_t)i * M + o];
+            if (!(x >= 0.0f) || std::isinf(x)) ok_range = false;
+            if (x > 1.0f) any_big = true;
+            const double l = std::log((double)x);
+            h.b64[(size_t)o * K + i] = l; h.b32[(size_t)o * K + i] = (float)l;
+        }
+        const float x = Pi[i];
+        if (!(x >= 0.0f) || std::isinf(x)) ok_range = false;
+        if (x > 1.0f) any_big = true;
+        h.pi64[i] = std::log((double)x);
+    }
+}
 
 // Host side of fv_set_model: log() of every entry in double with the host libm (the calls the reference makes per
 // cell, FLASH:142,150,167,170) and the table encodings.  Built once per model, uploaded to every device of a context.
@@ -372,22 +394,8 @@ int build_host_tables(const float *A, const float *B, const float *Pi, int K, in
             }
         }
     });
-    h.b64.assign((size_t)M * K, 0.0); h.pi64.assign(K, 0.0);
-    h.b32.assign((size_t)M * K, 0.0f);
-    for (int i = 0; i < K; ++i) {
-        for (int o = 0; o < M; ++o) {
-            const float x = B[(size_t)i * M + o];
-            if (!(x >= 0.0f) || std::isinf(x)) ok_range = false;
-            if (x > 1.0f) big[0] = 1;
-            const double l = std::log((double)x);
-            h.b64[(size_t)o * K + i] = l; h.b32[(size_t)o * K + i] = (float)l;
-        }
-        const float x = Pi[i];
-        if (!(x >= 0.0f) || std::isinf(x)) ok_range = false;
-        if (x > 1.0f) big[0] = 1;
-        h.pi64[i] = std::log((double)x);
-    }
     h.any_big = false;
+    log_emissions(B, Pi, K, M, h, ok_range, h.any_big);
     for (int k = 0; k < K; ++k) { if (bad[k]) ok_range = false; if (big[k]) h.any_big = true; }
     if (!ok_range) { detail = "model entries must be finite and >= 0"; return FV_ERR_ARG; }
 
@@ -484,6 +492,7 @@ int upload_tables(fv_ctx *ctx, const HostTables &h)
     (void)hipStreamSynchronize(ctx->stream);
     ctx->LA64R.release(); ctx->LAQ16R.release();
     ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release();
+    release_csr(ctx);
     ctx->window16 = h.window16; ctx->windowq = h.windowq; ctx->qscale = h.qscale; ctx->density = h.density;
     const size_t tab = h.tab;
     if (h.full_ok) {
@@ -524,6 +533,203 @@ int upload_tables(fv_ctx *ctx, const HostTables &h)
 
 }  // namespace fvi
 
+namespace fvi {
+
+void release_csr(fv_ctx *ctx)
+{
+    ctx->csr = false;
+    ctx->CSk.release(); ctx->CSq.release(); ctx->CS64.release(); ctx->CSoff.release(); ctx->CSnwb.release();
+    ctx->CRptr.release(); ctx->CRcol.release(); ctx->CRlog.release();
+}
+
+// what fv_set_model_sparse computes on the host: everything is O(nnz + K * M)
+struct HostCsr {
+    HostTables e;                        // K, M, nrows, ntiles, log B / log Pi, windowq, qscale, density, any_big
+    std::vector<uint4> ck;               // CSC-32 table (fv_kernels.hip.inc, trellis_step_csr)
+    std::vector<uint2> cq;
+    std::vector<double> c64;
+    std::vector<long long> off;
+    std::vector<int> nwb;
+    std::vector<double> rlog;            // log of every stored entry, in the caller's order
+};
+
+// Checks the CSR arrays, takes log((double)x) of every stored entry with the host libm (per entry the call fv_set_model
+// makes) and derives the Q16 step and window from the finite ones exactly as build_host_tables does from the dense
+// table's: the absent entries are its -inf cells, which take part in neither.
+int build_host_csr(const long long *row_ptr, const int *col, const float *val, const float *B, const float *Pi, int K, int M,
+                   HostCsr &h, std::string &detail)
+{
+    HostTables &e = h.e;
+    e.K = K; e.M = M;
+    e.nrows = round_up(K, fvk::ROW_ALIGN);
+    const int ntiles = e.ntiles = (K + fvk::TILE_W - 1) / fvk::TILE_W;
+    if (row_ptr[0] != 0) { detail = "fv_set_model_sparse: row_ptr[0] must be 0 (row 0)"; return FV_ERR_ARG; }
+    for (int k = 0; k < K; ++k)
+        if (row_ptr[k + 1] < row_ptr[k]) { detail = "fv_set_model_sparse: row_ptr decreases at row " + std::to_string(k); return FV_ERR_ARG; }
+    const long long nnz = row_ptr[K];
+    if (nnz > 0 && (!col || !val)) return FV_ERR_ARG;
+    // (a row holds at most K entries once its columns are strictly ascending, so nnz <= K * K without a check of its own)
+    std::vector<int> bad_row(K, 0);
+    std::vector<char> big(K, 0);
+    std::vector<double> lmax_row(K, 0.0);
+    try { h.rlog.resize((size_t)nnz); } catch (...) { return FV_ERR_NOMEM; }
+    parallel_rows(K, [&](int a, int b) {
+        for (int k = a; k < b; ++k) {
+            int prev = -1;
+            for (long long p = row_ptr[k]; p < row_ptr[k + 1]; ++p) {
+                const int i = col[p];
+                const float x = val[p];
+                if (i < 0 || i >= K) bad_row[k] |= 1;
+                else if (i <= prev) bad_row[k] |= 2;
+                prev = i;
+                if (!(x >= 0.0f) || std::isinf(x)) bad_row[k] |= 4;
+                if (x > 1.0f) big[k] = 1;
+                const double l = std::log((double)x);
+                h.rlog[(size_t)p] = l;
+                if (std::isfinite(l)) lmax_row[k] = std::max(lmax_row[k], -l);
+            }
+        }
+    });
+    for (int k = 0; k < K; ++k) {
+        if (bad_row[k] & 1) { detail = "fv_set_model_sparse: row " + std::to_string(k) + " holds a column outside [0, K)"; return FV_ERR_ARG; }
+        if (bad_row[k] & 2) { detail = "fv_set_model_sparse: the columns of row " + std::to_string(k) + " are not strictly ascending"; return FV_ERR_ARG; }
+    }
+    bool ok_range = true;
+    e.any_big = false;
+    log_emissions(B, Pi, K, M, e, ok_range, e.any_big);
+    for (int k = 0; k < K; ++k) {
+        if (bad_row[k] & 4) { detail = "model entries must be finite and >= 0 (row " + std::to_string(k) + ")"; return FV_ERR_ARG; }
+        if (big[k]) e.any_big = true;
+    }
+    if (!ok_range) { detail = "model entries must be finite and >= 0"; return FV_ERR_ARG; }
+
+    double lmax = 0.0;
+    for (int k = 0; k < K; ++k) lmax = std::max(lmax, lmax_row[k]);
+    const float stepf = lmax > 0.0 ? (float)(lmax / 65534.0) : 1.0f;
+    const double stepd = (double)stepf;
+    auto code_of = [&](double l) {
+        double q = std::nearbyint(-l / stepd);
+        if (q < 0) q = 0;
+        if (q > 65534.0) q = 65534.0;
+        return q;
+    };
+    // per destination column: the number of finite entries, then the tiles' extents (columns padded to the tile's
+    // longest, rounded up to a wave-block of 4 chunks x 4 entries)
+    std::vector<int> cnt((size_t)ntiles * fvk::TILE_W, 0);
+    long long nfin = 0;
+    double dqmax = 0.0;
+    for (long long p = 0; p < nnz; ++p) {
+        const double l = h.rlog[(size_t)p];
+        if (!std::isfinite(l)) continue;
+        ++cnt[(size_t)col[p]];
+        ++nfin;
+        dqmax = std::max(dqmax, std::fabs(-code_of(l) * stepd - l));
+    }
+    e.windowq = std::nextafter((float)(2.0 * dqmax), HUGE_VALF);
+    e.qscale = -stepf;
+    e.window16 = 0.0f;                   // (no binary16 table)
+    e.density = (double)nfin / ((double)K * K);
+    h.off.assign(ntiles, 0); h.nwb.assign(ntiles, 0);
+    long long total = 0;
+    for (int tl = 0; tl < ntiles; ++tl) {
+        int longest = 0;
+        for (int c = 0; c < fvk::TILE_W; ++c) longest = std::max(longest, cnt[(size_t)tl * fvk::TILE_W + c]);
+        h.nwb[tl] = (longest + 15) / 16;
+        h.off[tl] = total;
+        total += (long long)h.nwb[tl] * 4 * fvk::TILE_W;
+    }
+    try {
+        h.ck.assign((size_t)total, make_uint4(0u, 0u, 0u, 0u));
+        h.cq.assign((size_t)total, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
+        h.c64.assign((size_t)total * 4, -HUGE_VAL);
+    } catch (...) { return FV_ERR_NOMEM; }
+    // rows in ascending k: every column fills in ascending source state
+    std::fill(cnt.begin(), cnt.end(), 0);
+    unsigned int *kw = reinterpret_cast<unsigned int *>(h.ck.data());
+    unsigned short *qw = reinterpret_cast<unsigned short *>(h.cq.data());
+    for (int k = 0; k < K; ++k)
+        for (long long p = row_ptr[k]; p < row_ptr[k + 1]; ++p) {
+            const double l = h.rlog[(size_t)p];
+            if (!std::isfinite(l)) continue;
+            const int i = col[p], n = cnt[(size_t)i]++;
+            const size_t pos = 4 * ((size_t)h.off[i / fvk::TILE_W] + (size_t)(n >> 2) * fvk::TILE_W + (i % fvk::TILE_W)) + (n & 3);
+            kw[pos] = (unsigned int)k;
+            qw[pos] = (unsigned short)code_of(l);
+            h.c64[pos] = l;
+        }
+    return FV_OK;
+}
+
+// Device side of fv_set_model_sparse, once per device; as upload_tables, the context holds no model until every upload
+// has succeeded.  The dense tables of an earlier fv_set_model are released.
+int upload_csr(fv_ctx *ctx, const HostCsr &h, const long long *row_ptr, const int *col)
+{
+    const HostTables &e = h.e;
+    FV_HIP(hipSetDevice(ctx->device));
+    ctx->K = 0; ctx->M = 0; ctx->nrows = 0; ctx->full_ok = false; ctx->u16_ok = false; ctx->laq16_ready = false;
+    ctx->rowq_ready = false; ctx->beam_q16_ready = false;
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->LA64R.release(); ctx->LAQ16R.release();
+    ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release();
+    ctx->LA32.release(); ctx->LA16.release(); ctx->LAQ16.release(); ctx->LA64.release();
+    release_csr(ctx);
+    ctx->window16 = e.window16; ctx->windowq = e.windowq; ctx->qscale = e.qscale; ctx->density = e.density;
+    const size_t nnz = h.rlog.size(), nv = h.ck.size();
+    FV_HIP(ctx->CSk.ensure(std::max<size_t>(nv, 1)));
+    FV_HIP(ctx->CSq.ensure(std::max<size_t>(nv, 1)));
+    FV_HIP(ctx->CS64.ensure(std::max<size_t>(nv * 4, 1)));
+    FV_HIP(ctx->CSoff.ensure(e.ntiles));
+    FV_HIP(ctx->CSnwb.ensure(e.ntiles));
+    FV_HIP(ctx->CRptr.ensure((size_t)e.K + 1));
+    FV_HIP(ctx->CRcol.ensure(std::max<size_t>(nnz, 1)));
+    FV_HIP(ctx->CRlog.ensure(std::max<size_t>(nnz, 1)));
+    if (nv) {
+        FV_HIP(hipMemcpy(ctx->CSk.p, h.ck.data(), nv * sizeof(uint4), hipMemcpyHostToDevice));
+        FV_HIP(hipMemcpy(ctx->CSq.p, h.cq.data(), nv * sizeof(uint2), hipMemcpyHostToDevice));
+        FV_HIP(hipMemcpy(ctx->CS64.p, h.c64.data(), nv * 4 * sizeof(double), hipMemcpyHostToDevice));
+    }
+    FV_HIP(hipMemcpy(ctx->CSoff.p, h.off.data(), e.ntiles * sizeof(long long), hipMemcpyHostToDevice));
+    FV_HIP(hipMemcpy(ctx->CSnwb.p, h.nwb.data(), e.ntiles * sizeof(int), hipMemcpyHostToDevice));
+    FV_HIP(hipMemcpy(ctx->CRptr.p, row_ptr, ((size_t)e.K + 1) * sizeof(long long), hipMemcpyHostToDevice));
+    if (nnz) {
+        FV_HIP(hipMemcpy(ctx->CRcol.p, col, nnz * sizeof(int), hipMemcpyHostToDevice));
+        FV_HIP(hipMemcpy(ctx->CRlog.p, h.rlog.data(), nnz * sizeof(double), hipMemcpyHostToDevice));
+    }
+    FV_HIP(ctx->LB64T.ensure((size_t)e.M * e.K));
+    FV_HIP(ctx->LB32T.ensure((size_t)e.M * e.K));
+    FV_HIP(ctx->LPi64.ensure(e.K));
+    FV_HIP(hipMemcpy(ctx->LB64T.p, e.b64.data(), e.b64.size() * sizeof(double), hipMemcpyHostToDevice));
+    FV_HIP(hipMemcpy(ctx->LB32T.p, e.b32.data(), e.b32.size() * sizeof(float), hipMemcpyHostToDevice));
+    FV_HIP(hipMemcpy(ctx->LPi64.p, e.pi64.data(), e.pi64.size() * sizeof(double), hipMemcpyHostToDevice));
+    ctx->K = e.K; ctx->M = e.M; ctx->nrows = e.nrows;
+    ctx->csr = true;
+    ctx->logs_nonpositive = !e.any_big;
+    ctx->stats = fv_stats{};
+    ctx->stats.device_bytes = (long long)device_bytes(ctx);
+    ctx->stats.density = ctx->density;
+    return FV_OK;
+}
+
+}  // namespace fvi
+
+extern "C" int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const int *col, const float *val, const float *B,
+                                   const float *Pi, int K, int M)
+{
+    if (!ctx || !row_ptr || !B || !Pi || K < 1 || M < 1) return FV_ERR_ARG;
+    auto t0 = clk::now();
+    fvi::HostCsr h;
+    int rc = FV_OK;
+    try { rc = fvi::build_host_csr(row_ptr, col, val, B, Pi, K, M, h, ctx->detail); } catch (const std::bad_alloc &) { rc = FV_ERR_NOMEM; }
+    if (rc) return rc;
+    const int n = fvi::group_size(ctx);
+    for (int r = 0; r < n; ++r) {
+        fv_ctx *m = fvi::group_member(ctx, r);
+        if ((rc = fvi::upload_csr(m, h, row_ptr, col))) { if (m != ctx) ctx->detail = m->detail; return rc; }
+    }
+    ctx->stats.set_model_ms = ms_since(t0);
+    return FV_OK;
+}
+
 extern "C" int fv_set_model(fv_ctx *ctx, const float *A, const float *B, const float *Pi, int K, int M)
 {
     if (!ctx || !A || !B || !Pi || K < 1 || M < 1) return FV_ERR_ARG;
@@ -552,7 +758,7 @@ extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
     }
     switch (key) {
     case FV_OPT_KERNEL:
-        if (value < FV_KERNEL_AUTO || value > FV_KERNEL_U16_REFINE) return FV_ERR_ARG;
+        if (value < FV_KERNEL_AUTO || value > FV_KERNEL_U16_REFINE) return FV_ERR_ARG;      // (FV_KERNEL_SPARSE_CSR is reported, never chosen)
         ctx->opt_kernel = (int)value; return FV_OK;
     case FV_OPT_MAX_BATCH:
         if (value < 1 || value > fvk::MAX_BATCH) return FV_ERR_ARG;
@@ -568,8 +774,10 @@ extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
         // the timing build only (libflashvit_timing.so, tools/).  Every bit this library accepts is speed-only.
         if (value & FV_DEBUG_TIMING_ONLY) { ctx->detail = "FV_OPT_DEBUG: result-changing timing switches need the timing build"; return FV_ERR_ARG; }
 #endif
-        if (value < 0 || value >= (1ll << 30) || (value & (1ll << 27))) return FV_ERR_ARG;      // (bit 27 is not assigned)
-        ctx->opt_debug = (int)value; return FV_OK;
+        // (bits 27 and 30 are not assigned; bit 31 is kept apart from the int the kernels see)
+        if (value < 0 || value >= (1ll << 32) || (value & ((1ll << 27) | (1ll << 30)))) return FV_ERR_ARG;
+        ctx->opt_csr_mem = (int)((value >> 31) & 1);
+        ctx->opt_debug = (int)(value & 0x3fffffff); return FV_OK;
     default: return FV_ERR_ARG;
     }
 }

@@ -77,6 +77,17 @@ struct fv_ctx {
     bool laq16_ready = false; // LAQ16 holds this model's codes and windowq / qscale belong to it (host-built in fv_set_model, or
                               // built on the device by the first full-state decode of a model beyond the float32 kernels' limit)
     DevBuf<double> LA64, LB64T, LPi64;
+    // a model set by fv_set_model_sparse (csr): no dense table at all.  Per destination column the stored finite entries in
+    // ascending source state (fv_kernels.hip.inc, trellis_step_csr), and the caller's rows for init_rows
+    bool csr = false;
+    DevBuf<uint4> CSk;           // source states: a lane load holds 4 consecutive entries of one column
+    DevBuf<uint2> CSq;           // their Q16 codes (4 x 16 bit), same vector index
+    DevBuf<double> CS64;         // their float64 logs: entry q of vector v at 4 * v + q
+    DevBuf<long long> CSoff;     // [ntiles] first vector of each 16-column tile
+    DevBuf<int> CSnwb;           // [ntiles] wave-blocks (64 vectors) of each tile
+    DevBuf<long long> CRptr;     // [K + 1] rows by source state: log A[Ans[L-1]][*] of init_rows
+    DevBuf<int> CRcol;
+    DevBuf<double> CRlog;
 
     // workspace
     DevBuf<int> d_ob, d_ans, d_bp, d_gather;
@@ -114,6 +125,7 @@ struct fv_ctx {
     int opt_max_batch = fvk::MAX_BATCH;
     int opt_profile = 0;
     int vanilla = 0;         // set for the duration of fv_decode_vanilla
+    int opt_csr_mem = 0;     // FV_OPT_DEBUG bit 31: trellis_step_csr reads its score rows from memory at any K
     int opt_debug = 0;       // FV_OPT_DEBUG bits: 1 skip refine (timing only), 2 no reverse sweep, 4 alternate unroll, 8 full last step,
                              // 16 launch only / 32 no score-row staging (sparse walk), 64 hipGraph replay, 256 / 512 beam step kernel: float64 / 16-bit
     std::vector<hipEvent_t> prof_events;
@@ -166,6 +178,7 @@ struct HostTables {
 };
 int build_host_tables(const float *A, const float *B, const float *Pi, int K, int M, HostTables &h, std::string &detail);
 int upload_tables(fv_ctx *ctx, const HostTables &h);
+void release_csr(fv_ctx *ctx);           // drops the tables of a model set by fv_set_model_sparse
 
 size_t device_bytes(const fv_ctx *c);
 // (nscores > 1: a batch decode — room for that many scores, sizes checked against free device memory first)

@@ -149,7 +149,10 @@ __device__ __forceinline__ void load_t1(const float *T1s, int k, float (&v)[NB])
 
 // Stage NB score rows (global, 16-byte aligned, nrows floats each, pads zero) into T1s: one 16-byte
 // global load per task per thread, all issued before the first LDS write.
-template <int NB, int NTHREADS>
+// (DEAD_TO_INF, trellis_step_csr only: a score of -FLT_MAX — a state no finite entry reached — is staged as -inf, see there)
+__device__ __forceinline__ float dead_to_inf(float x) { return x > -FLT_MAX ? x : FV_NEG_INF; }
+
+template <int NB, int NTHREADS, bool DEAD_TO_INF = false>
 __device__ __forceinline__ void stage_rows(float *T1s, const TaskSlot (&slots)[NB], int nrows, int tid, int row_lo = 0)
 {
     const int nq4 = nrows >> 2;
@@ -157,8 +160,10 @@ __device__ __forceinline__ void stage_rows(float *T1s, const TaskSlot (&slots)[N
         const int q = q0 + tid;
         float4 v[NB];
 #pragma unroll
-        for (int t = 0; t < NB; ++t)
+        for (int t = 0; t < NB; ++t) {
             v[t] = q < nq4 ? reinterpret_cast<const float4 *>(slots[t].t1_in + row_lo)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (DEAD_TO_INF) v[t] = make_float4(dead_to_inf(v[t].x), dead_to_inf(v[t].y), dead_to_inf(v[t].z), dead_to_inf(v[t].w));
+        }
         if (q < nq4) {
             if constexpr (NB >= 4) {
                 float4 *dst = reinterpret_cast<float4 *>(T1s);
@@ -1239,6 +1244,218 @@ static inline size_t sparse_lds_bytes(int nrows)
     return (size_t)nrows * NB * 4 + (size_t)NB * SP_WAVES * TILE_W * 12;
 }
 
+// ---------------------------------------------------------------- models set in CSR form (fv_set_model_sparse)
+//
+// The same walk over the stored finite entries as trellis_step_sparse, for a model that never had a dense table.
+// Layout ("CSC-32"): 16-column tiles, per column the stored finite entries in ascending source state, 4 entries of
+// ONE column per lane load, one wave-wide load = 4 chunks (row groups) x 16 columns, columns padded to the tile's
+// longest column rounded up to a wave-block (16 entries) — three arrays addressed by the same vector index v:
+//     ck[v]  uint4  the 4 source states (32 bit each; pad: 0)
+//     cq[v]  uint2  their 4 Q16 codes (pad: 0xffff = -inf)
+//     c64[4 * v + q] double  log A of entry q (pad: -inf) — read by the refine only, never streamed
+// A step streams 6 bytes per (padded) entry.  tile_off is 64-bit: nothing here is indexed by K * K.
+// MEM = false: the NB score rows are staged into LDS as trellis_step_sparse does (nrows * NB * 4 bytes).
+// MEM = true: every score is read from the row in memory (a row of K = 262144 is 1 MB: it stays in the XCD's L2 for the
+// whole step) — the form of every K beyond the LDS limit, and of any K under FV_OPT_DEBUG bit 31.
+// Dead sources.  A state no finite entry reached carries the score -FLT_MAX (the reference's initial value).  With every
+// log <= 0 (the condition of every filter kernel) its cells evaluate to exact_cell(tmp, -FLT_MAX, L) <= -FLT_MAX, which
+// the strict '>' from -FLT_MAX can never take: they are read as -inf and drop out of the filter like absent entries.  It
+// matters here as it does not for the dense-set walk: a right-hand pass starts from ONE state, and at tens of edges per
+// state most of its first rows are dead; left at -FLT_MAX they would all lie inside each other's window (the float
+// spacing at 3e38 is 2e31) and every lane would re-walk its entries in float64 (measured at K = 262144: 20 ms per launch
+// instead of 0.1).
+// The running argmax keeps the entry's POSITION in the lane's share of the column (ascending with k), so that the
+// refine finds both the source state and the float64 log of its candidate at that position.
+template <int NB>
+struct CsrArgs {
+    const uint4 *ck;
+    const uint2 *cq;
+    const double *c64;
+    const long long *tile_off;   // [ntiles] first vector of each tile
+    const int *tile_nwb;         // [ntiles] wave-blocks (64 vectors) in each tile
+    unsigned long long *counters;
+    int K, nrows, ntiles, tiles_per_xcd, nb, debug;
+    float window, qscale;
+    TaskSlot t[NB];
+};
+
+template <int NB, bool MEM>
+__global__ __launch_bounds__(SP_BLOCK) void trellis_step_csr(const CsrArgs<NB> args)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int nrows = args.nrows;
+    float *T1s = reinterpret_cast<float *>(smem);              // [nrows][NB] (MEM: absent)
+    float *redV = T1s + (MEM ? (size_t)0 : (size_t)nrows * NB);  // [NB][TILE_W][SP_WAVES]
+    float *redR = redV + NB * SP_WAVES * TILE_W;
+    int *redK = reinterpret_cast<int *>(redR + NB * SP_WAVES * TILE_W);
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane & (TILE_W - 1), rg = lane >> 4;
+    const int tile = (blockIdx.x & 7) * args.tiles_per_xcd + (blockIdx.x >> 3);
+    if (tile >= args.ntiles) return;
+    const int col = tile * TILE_W + c;
+    const int K = args.K;
+    const size_t v0 = (size_t)args.tile_off[tile] + rg * TILE_W + c;      // this lane's vector of wave-block 0
+    const uint4 *kb = args.ck + v0;
+    const uint2 *qb = args.cq + v0;
+    const int nwb = args.tile_nwb[tile];
+    const int nj = nwb > w ? (nwb - w + SP_WAVES - 1) / SP_WAVES : 0;     // wave-blocks of this wave
+    auto vec = [&](int j) { return (size_t)(w + SP_WAVES * j) * (4 * TILE_W); };
+    constexpr int U = 4;
+    uint4 curk[U];
+    uint2 curq[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        if (u < nj) { curk[u] = kb[vec(u)]; curq[u] = qb[vec(u)]; }
+
+    float tmp[NB];
+    if constexpr (!MEM) stage_rows<NB, SP_BLOCK, true>(T1s, args.t, nrows, tid);
+#pragma unroll
+    for (int t = 0; t < NB; ++t) tmp[t] = (t < args.nb && col < K) ? args.t[t].tmp_row[col] : 0.0f;
+    __syncthreads();
+
+    auto scores = [&](int k, float (&tv)[NB]) {
+        if constexpr (MEM) {
+#pragma unroll
+            for (int t = 0; t < NB; ++t) tv[t] = dead_to_inf(args.t[t].t1_in[k]);
+        } else {
+            load_t1<NB>(T1s, k, tv);
+        }
+    };
+    auto score1 = [&](int k, int t) -> float {
+        if constexpr (MEM) return dead_to_inf(args.t[t].t1_in[k]);
+        else return t1_at<NB>(T1s, k, t);
+    };
+
+    float m1[NB], m2[NB];
+    int e1[NB];                      // position of the lane's best entry: 4 * (its wave-block j) + q
+#pragma unroll
+    for (int t = 0; t < NB; ++t) { m1[t] = FV_NEG_INF; m2[t] = FV_NEG_INF; e1[t] = -1; }
+
+    auto visit = [&](unsigned int k, unsigned int code, int id) {
+        const float qf = q2f(code);
+        float tv[NB];
+        scores((int)k, tv);
+#pragma unroll
+        for (int t = 0; t < NB; ++t) {
+            const float y = __builtin_fmaf(qf, args.qscale, tmp[t] + tv[t]);
+            const bool gt = y > m1[t];
+            m2[t] = __builtin_amdgcn_fmed3f(y, m1[t], m2[t]);
+            m1[t] = gt ? y : m1[t];
+            e1[t] = gt ? id : e1[t];
+        }
+    };
+    for (int p0 = 0; p0 < nj; p0 += U) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (p0 + u < nj) {
+                const uint4 k4 = curk[u];
+                const uint2 q2 = curq[u];
+                const int id = 4 * (p0 + u);
+                visit(k4.x, q2.x & 0xffffu, id); visit(k4.y, q2.x >> 16, id + 1);
+                visit(k4.z, q2.y & 0xffffu, id + 2); visit(k4.w, q2.y >> 16, id + 3);
+            }
+        }
+        if (p0 + U < nj) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (p0 + U + u < nj) { curk[u] = kb[vec(p0 + U + u)]; curq[u] = qb[vec(p0 + U + u)]; }
+        }
+    }
+
+    // column maxima over 4 row groups x SP_WAVES waves
+    float M1v[NB];
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        float v = m1[t];
+        v = fmaxf(v, __shfl_xor(v, 16));
+        v = fmaxf(v, __shfl_xor(v, 32));
+        if (lane < TILE_W) redV[(t * TILE_W + c) * SP_WAVES + w] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        const float4 *q = reinterpret_cast<const float4 *>(redV + (t * TILE_W + c) * SP_WAVES);
+        const float4 f0 = q[0], f1 = q[1];
+        M1v[t] = fmaxf(fmaxf(fmaxf(f0.x, f0.y), fmaxf(f0.z, f0.w)), fmaxf(fmaxf(f1.x, f1.y), fmaxf(f1.z, f1.w)));
+    }
+
+    // refine: the window and the float64 re-evaluation of the other filter kernels; source state and float64 log of a
+    // candidate are read at its position in the table
+    const unsigned int *kw = reinterpret_cast<const unsigned int *>(args.ck);
+    float rr[NB];
+    int rk[NB];
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        const float M1 = M1v[t];
+        float r = FV_NEG_INF;
+        int kbest = INT_MAX;
+        if (t < args.nb && M1 > FV_NEG_INF && col < K) {
+            const float thr = refine_threshold(M1, args.window);
+            if (m2[t] >= thr && m2[t] > FV_NEG_INF) {
+                // two candidates in this lane: it owns only a handful of entries, re-walk them (ascending k)
+                for (int j = 0; j < nj; ++j) {
+                    const size_t v = v0 + vec(j);
+                    const uint4 k4 = args.ck[v];
+                    const uint2 q2 = args.cq[v];
+                    const unsigned int ks[4] = { k4.x, k4.y, k4.z, k4.w };
+                    const unsigned int cs[4] = { q2.x & 0xffffu, q2.x >> 16, q2.y & 0xffffu, q2.y >> 16 };
+                    for (int q = 0; q < 4; ++q) {
+                        const int k = (int)ks[q];
+                        const float t1 = score1(k, t);
+                        const float y = __builtin_fmaf(q2f(cs[q]), args.qscale, tmp[t] + t1);
+                        if (y >= thr && y > FV_NEG_INF) {
+                            const float x = exact_cell(tmp[t], t1, args.c64[4 * v + q]);
+                            if (better(x, k, r, kbest)) { r = x; kbest = k; }
+                        }
+                    }
+                }
+                atomicAdd(&args.counters[1], 1ull);
+            } else if (m1[t] >= thr && e1[t] >= 0) {
+                const size_t pos = 4 * (v0 + vec(e1[t] >> 2)) + (e1[t] & 3);
+                const int k = (int)kw[pos];
+                r = exact_cell(tmp[t], score1(k, t), args.c64[pos]);
+                kbest = k;
+                if (m1[t] != M1) atomicAdd(&args.counters[0], 1ull);
+            }
+        }
+        rr[t] = r; rk[t] = kbest;
+    }
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        float r = rr[t];
+        int kbest = rk[t];
+        wave_best(r, kbest);
+        if (lane < TILE_W) { redR[(t * TILE_W + c) * SP_WAVES + w] = r; redK[(t * TILE_W + c) * SP_WAVES + w] = kbest; }
+    }
+    __syncthreads();
+    if (w < NB && w < args.nb) {
+        // 8 wave results per column: lanes (c, rg<2) read 4 each
+        float r = FV_NEG_INF;
+        int kbest = INT_MAX;
+        if (rg < 2) {
+            const float4 fv = *reinterpret_cast<const float4 *>(redR + (w * TILE_W + c) * SP_WAVES + rg * 4);
+            const int4 fk = *reinterpret_cast<const int4 *>(redK + (w * TILE_W + c) * SP_WAVES + rg * 4);
+            r = fv.x; kbest = fk.x;
+            if (better(fv.y, fk.y, r, kbest)) { r = fv.y; kbest = fk.y; }
+            if (better(fv.z, fk.z, r, kbest)) { r = fv.z; kbest = fk.z; }
+            if (better(fv.w, fk.w, r, kbest)) { r = fv.w; kbest = fk.w; }
+        }
+        wave_best(r, kbest);
+        if (lane < TILE_W && col < K) {
+            const bool any = r > -FLT_MAX;
+            args.t[w].t1_out[col] = any ? r : -FLT_MAX;
+            args.t[w].bp_out[col] = any ? kbest : -1;
+        }
+    }
+}
+
+template <int NB>
+static inline size_t csr_lds_bytes(int nrows, bool mem)
+{
+    return (mem ? (size_t)0 : (size_t)nrows * NB * 4) + (size_t)NB * SP_WAVES * TILE_W * 12;
+}
+
 // ---------------------------------------------------------------- small kernels
 
 
@@ -1357,6 +1574,87 @@ __global__ __launch_bounds__(256) void last_column(const ColArgs args)
             if (k < args.K) {
                 const float y = exact_cell(tmp, t1[u], L[u]);
                 if (y > best) { best = y; arg = k; }       // k ascending per thread
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const float ov = __shfl_xor(best, m);
+        const int ok = __shfl_xor(arg, m);
+        if (better(ov, ok, best, arg)) { best = ov; arg = ok; }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { sv[w] = best; sk[w] = arg; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < 4; ++q)
+            if (better(sv[q], sk[q], best, arg)) { best = sv[q]; arg = sk[q]; }
+        job.bp_row[i] = best > -FLT_MAX ? arg : -1;
+    }
+}
+
+// init_rows for a CSR-set model: row Ans[L-1] of log A is the caller's CSR row scattered into a -inf row — column i
+// looks itself up in the row's ascending column list (a row holds tens of entries: a handful of probes).
+__global__ void init_rows_csr(const PassChunk ch, const long long *rptr, const int *rcol, const double *rlog,
+                              const double *LB64T, const double *LPi64, const int *ob, const int *ans, float *rows, int K)
+{
+    const PassDesc p = ch.p[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= K) return;
+    const int st = p.from_pi ? -1 : ans[p.L - 1];
+    double x;
+    if (st < 0) {
+        x = LPi64[i];
+    } else {
+        long long lo = rptr[st], hi = rptr[st + 1];         // first entry with column >= i
+        const long long end = hi;
+        while (lo < hi) {
+            const long long mid = lo + (hi - lo) / 2;
+            if (rcol[mid] < i) lo = mid + 1; else hi = mid;
+        }
+        x = (lo < end && rcol[lo] == i) ? rlog[lo] : -__builtin_huge_val();
+    }
+    rows[p.row_off + i] = (float)(x + LB64T[(size_t)ob[p.L] * K + i]);
+}
+
+// last_column for a CSR-set model: the one destination column is a column of the CSC-32 table (ascending source
+// states, then pads of -inf), evaluated with the reference expression from its float64 logs.
+struct CsrColArgs {
+    const uint4 *ck; const double *c64; const long long *tile_off; const int *tile_nwb;
+    const int *ans; int K, n; ColJob p[COL_CHUNK];
+};
+
+__global__ __launch_bounds__(256) void last_column_csr(const CsrColArgs args)
+{
+    __shared__ float sv[4];
+    __shared__ int sk[4];
+    const ColJob job = args.p[blockIdx.x];
+    const int i = args.ans[job.R];
+    if (i < 0 || i >= args.K) return;                  // workgroup-uniform
+    const float tmp = job.tmp_row[i];
+    const int tile = i >> 4, c = i & 15;
+    const size_t v0 = (size_t)args.tile_off[tile] + c;
+    const int nent = args.tile_nwb[tile] * 16;         // (padded) entries of the column
+    const unsigned int *kw = reinterpret_cast<const unsigned int *>(args.ck);
+    float best = FV_NEG_INF;
+    int arg = INT_MAX;
+    for (int n0 = threadIdx.x; n0 < nent; n0 += 256 * 4) {           // four gathers in flight per thread
+        float t1[4];
+        double L[4];
+        int ks[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int n = n0 + 256 * u, ns = n < nent ? n : 0;
+            const size_t pos = 4 * (v0 + (size_t)(ns >> 2) * TILE_W) + (ns & 3);
+            ks[u] = (int)kw[pos];
+            L[u] = args.c64[pos];
+            t1[u] = job.t1_in[ks[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (n0 + 256 * u < nent) {
+                const float y = exact_cell(tmp, t1[u], L[u]);
+                if (y > best) { best = y; arg = ks[u]; }       // k ascending per thread (pads are -inf: never taken)
             }
         }
     }

@@ -15,10 +15,12 @@ MODE_REFERENCE = 0
 MODE_SINGLE_PASS = 1
 KERNEL_AUTO, KERNEL_F64_STREAM, KERNEL_F32_REFINE, KERNEL_F16_REFINE, KERNEL_Q16_REFINE, KERNEL_SPARSE_Q16 = 0, 1, 2, 3, 4, 5
 KERNEL_U16_REFINE = 6
+KERNEL_SPARSE_CSR = 7                  # reported by stats()["kernel"] for a model set by set_model_sparse; never chosen
 OPT_KERNEL, OPT_MAX_BATCH, OPT_PROFILE, OPT_SEL_MARGIN, OPT_DEBUG = 1, 2, 3, 4, 100
 DEBUG_TIMING_ONLY = (1 << 0) | (1 << 4) | (1 << 5) | (1 << 11) | (1 << 12)      # refused by the shipped library
 DEBUG_BATCH_GEN0_SERIAL = 1 << 28      # decode_full_batch: the whole-sequence passes on one stream (speed only)
 DEBUG_BEAM_BATCH_GEN0_OTHER = 1 << 29  # decode_beam_batch: the whole-sequence passes in the launch form that is not the default (speed only)
+DEBUG_CSR_ROWS_IN_MEMORY = 1 << 31     # sparse-set models: the step kernel reads its score rows from memory at any K (speed only)
 WARN_BEAM_MISS = 1
 ERR_ARG, ERR_NOMEM, ERR_NO_PRED, ERR_DEVICE, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 UNIQUE_ID_BYTES = 128
@@ -54,7 +56,8 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_decode_vanilla", "fv_decode_checkpoint", "fv_checkpoint_memory_bytes",
            "fv_last_stats", "fv_strerror", "fv_last_error_detail", "fv_reference_memory_bytes",
            "fv_comm_unique_id", "fv_comm_init", "fv_plan_passes", "fv_merge_paths", "fv_set_partition",
-           "fv_create_multi", "fv_device_count", "fv_decode_full_batch", "fv_plan_passes_batch", "fv_decode_beam_batch"]
+           "fv_create_multi", "fv_device_count", "fv_decode_full_batch", "fv_plan_passes_batch", "fv_decode_beam_batch",
+           "fv_set_model_sparse"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step"]
 TIE_TAG = 1 << 30
@@ -90,6 +93,7 @@ def load_library():
     L.fv_destroy.argtypes = [vp]
     L.fv_destroy.restype = None
     L.fv_set_model.argtypes = [vp, vp, vp, vp, ci, ci]
+    L.fv_set_model_sparse.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci]
     L.fv_set_option.argtypes = [vp, ci, cll]
     L.fv_decode_full.argtypes = [vp, vp, ci, ci, ci, vp, vp]
     L.fv_decode_beam.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
@@ -173,6 +177,17 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def dense_to_csr(A):
+    """(indptr int64[K + 1], indices int32[nnz], data float32[nnz]) of a dense K x K matrix, by row with ascending
+    columns: what set_model_sparse takes.  Entries equal to 0 are left out (NaN is kept, so that the library sees it)."""
+    A = np.ascontiguousarray(A, dtype=np.float32)
+    assert A.ndim == 2 and A.shape[0] == A.shape[1]
+    rows, cols = np.nonzero(A != 0)              # row-major order: ascending columns inside a row
+    indptr = np.zeros(A.shape[0] + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=A.shape[0]), out=indptr[1:])
+    return indptr, cols.astype(np.int32), A[rows, cols]
+
+
 class FlashViterbi:
     """One decoder context on one GPU.  Mirrors the reference program's life cycle:
     create_vit() -> calc() -> printAns() becomes set_model() -> decode_*() -> returned path."""
@@ -215,6 +230,21 @@ class FlashViterbi:
         K, M = B.shape
         assert A.shape == (K, K) and Pi.shape == (K,)
         self._check(self._L.fv_set_model(self._h, _p(A), _p(B), _p(Pi), K, M))
+        self.K, self.M = K, M
+
+    def set_model_sparse(self, indptr, indices, data, B, Pi):
+        """fv_set_model_sparse: the transition matrix in CSR form by source state (indptr[K + 1], ascending column
+        indices per row, values; dense_to_csr makes them from a dense matrix).  No K x K array exists on this path."""
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        B = np.ascontiguousarray(B, dtype=np.float32)
+        Pi = np.ascontiguousarray(Pi, dtype=np.float32)
+        K, M = B.shape
+        assert indptr.shape == (K + 1,) and Pi.shape == (K,) and indices.shape == data.shape and indices.ndim == 1
+        # (the array lengths are the wrapper's to check: the library reads row_ptr[K] entries of both)
+        assert indptr[-1] <= indices.size, "indptr[K] exceeds the number of stored entries"
+        self._check(self._L.fv_set_model_sparse(self._h, _p(indptr), _p(indices), _p(data), _p(B), _p(Pi), K, M))
         self.K, self.M = K, M
 
     def decode_full(self, ob, n_split=1, mode=MODE_REFERENCE):

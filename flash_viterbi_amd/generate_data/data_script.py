@@ -150,6 +150,45 @@ def make_model32_fast(K, n_ob, seed, prob, block=256, workers=None):
     return A, hostio.quantize_text16(B), hostio.quantize_text16(np.full(K, 1 / K))
 
 
+def make_model_csr(K, n_ob, seed, in_degree_or_prob, block=4096):
+    """A model of the make_model32_fast distributions emitted in CSR form, never as a dense array: (indptr int64[K + 1],
+    indices int32[nnz], data float32[nnz], B, Pi), what FlashViterbi.set_model_sparse takes — so that a model of
+    K = 262144 states can be made at all.  in_degree_or_prob >= 1 is the mean number of edges per state (edge probability
+    d / K), below 1 the edge probability itself.  Per source state Binomial(K, p) out-edges at distinct uniformly random
+    places (a state that draws none gets one), weights U(0.01, 1), rows normalised, B U(0.1, 1) row-normalised,
+    Pi = 1/K, every value through the '%.16f' text quantisation.  Same distributions as generate_data and
+    make_model32_fast, NOT their random streams: neither the md5s of SURVEY App. C nor make_model32_fast's arrays apply.
+    Memory is O(nnz + K * n_ob)."""
+    from flash_viterbi_amd import hostio
+    p = in_degree_or_prob / K if in_degree_or_prob >= 1 else float(in_degree_or_prob)
+    p = min(p, 1.0)
+    counts_all, keys_all, data_all = [], [], []
+    for r0 in range(0, K, block):
+        n = min(block, K - r0)
+        g = np.random.Generator(np.random.PCG64(np.random.SeedSequence([seed, r0, 7])))
+        counts = np.maximum(g.binomial(K, p, n), 1).astype(np.int64)
+        rows = np.repeat(np.arange(n, dtype=np.int64), counts)
+        keys = np.unique(rows * K + g.integers(0, K, rows.size))             # (row, column) pairs, sorted, distinct
+        while True:                                                          # top up what the duplicates took
+            lack = counts - np.bincount(keys // K, minlength=n)
+            if not lack.any():
+                break
+            rows = np.repeat(np.arange(n, dtype=np.int64), lack)
+            keys = np.union1d(keys, rows * K + g.integers(0, K, rows.size))
+        w = g.uniform(0.01, 1.0, keys.size)
+        w /= np.repeat(np.bincount(keys // K, weights=w, minlength=n), counts)
+        counts_all.append(counts)
+        keys_all.append((keys % K).astype(np.int32))
+        data_all.append(hostio.quantize_text16(w))
+    indptr = np.zeros(K + 1, dtype=np.int64)
+    np.cumsum(np.concatenate(counts_all), out=indptr[1:])
+    g = np.random.Generator(np.random.PCG64(np.random.SeedSequence([seed, K, n_ob])))
+    B = g.uniform(0.1, 1.0, (K, n_ob))
+    B /= B.sum(axis=1)[:, None]
+    return (indptr, np.concatenate(keys_all), np.concatenate(data_all).astype(np.float32), hostio.quantize_text16(B),
+            hostio.quantize_text16(np.full(K, 1 / K)))
+
+
 def file_stem(kind, K, T, prob):
     return f"{kind}_K{K}_T{T}_prob{prob}"
 

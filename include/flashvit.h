@@ -80,7 +80,9 @@ enum {
                                step replays its heap at once (no speculative member lists), 22 every selection in the memory-resident
                                form (the route of K > 65536), 23 runs of undecided steps always decided in full, 24 four-wave select also on steps that may have to be resolved,
                                25 / 26 the 16-bit step kernel in 16-wave / 8-wave workgroups whatever the launch size (25 also: the float64
-                               step kernel in 16-wave workgroups for small beams too) */
+                               step kernel in 16-wave workgroups for small beams too).  Models set by fv_set_model_sparse: 31 the
+                               step kernel reads its score rows from memory at any K (the form of K beyond one LDS row); bit 30
+                               is not assigned and refused */
 };
 #define FV_DEBUG_TIMING_ONLY ((1 << 0) | (1 << 4) | (1 << 5) | (1 << 11) | (1 << 12))
 enum {
@@ -104,6 +106,9 @@ enum {
     FV_KERNEL_SPARSE_Q16 = 5,  /* the Q16 codes of the NON-ZERO transitions only (per destination column, ascending
                                   source state): log 0 = -inf can never win (FLASH:171), so skipping those cells
                                   changes no bit; 7.6 MB instead of 31.5 MB at K=3965, p=0.112 */
+    FV_KERNEL_SPARSE_CSR = 7,  /* REPORTED ONLY (fv_stats.kernel; fv_set_option answers FV_ERR_ARG to it): the walk over the
+                                  stored transitions of a model set by fv_set_model_sparse — the scheme of SPARSE_Q16 with
+                                  32-bit source states, no dense table behind it */
 };
 
 typedef struct {
@@ -168,6 +173,29 @@ int fv_device_count(void);
  * log() of every entry in double with the host libm (the calls the reference makes per
  * cell, :142,150,167,170) and ships the tables; the caller keeps ownership of A/B/Pi. */
 int fv_set_model(fv_ctx *ctx, const float *A, const float *B, const float *Pi, int K, int M);
+
+/* The same model given by its non-zero transitions only, in compressed sparse row form by SOURCE state: row k is
+ * A[k][col[e]] = val[e] for e in [row_ptr[k], row_ptr[k+1]).  row_ptr has K + 1 non-decreasing entries, row_ptr[0] == 0;
+ * the columns of a row are strictly ascending (no duplicates) and lie in [0, K); every transition not stored is 0, and a
+ * stored 0 is the same as an absent entry (log 0 = -inf can never win, FLASH:171).  B and Pi as in fv_set_model.  Value
+ * rules and errors are fv_set_model's (finite, >= 0); a malformed CSR answers FV_ERR_ARG with the offending row in
+ * fv_last_error_detail.  An argument error leaves the previous model in place; a failure during the upload leaves the
+ * context with no model.  log((double)x) is taken per stored entry with the host libm, and the Q16 step and refine
+ * window come from the finite entries alone, so a decode delivers bit for bit what the same model gives through
+ * fv_set_model.  Host and device memory are O(nnz + K*M): no K*K table exists on this path (about 30 bytes of device
+ * memory per stored entry), so K is bounded by the number of transitions, not by 8*K^2.
+ * The context remembers how its model was set; a later fv_set_model replaces a sparse-set model and the other way round.
+ * On a sparse-set model:
+ *   - fv_decode_full, fv_decode_full_batch, fv_set_partition, fv_create_multi contexts and fv_test_forward work as on
+ *     any model; fv_stats.kernel reports FV_KERNEL_SPARSE_CSR.  FV_OPT_KERNEL values FV_KERNEL_AUTO and
+ *     FV_KERNEL_SPARSE_Q16 select that walk; any other (a kernel that streams a dense table) answers FV_ERR_UNSUPPORTED
+ *     at decode.
+ *   - A model with an entry above 1 is accepted here, as by fv_set_model, but its decode answers FV_ERR_UNSUPPORTED: the
+ *     walk is a filter kernel (its error bracket needs every log <= 0) and there is no float64 table to fall back to.
+ *   - fv_decode_beam, fv_decode_beam_batch, fv_decode_vanilla and fv_decode_checkpoint answer FV_ERR_UNSUPPORTED before
+ *     any device work: their kernels gather rows of the dense table. */
+int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const int *col, const float *val,
+                        const float *B, const float *Pi, int K, int M);
 
 int fv_set_option(fv_ctx *ctx, int key, long long value);
 

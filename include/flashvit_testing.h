@@ -117,6 +117,17 @@ int fv_test_beam_step(fv_ctx *ctx, int beam, const fv_test_beam_set *sets, int n
 #define FV_TV_BEAM_W16       (1ull << 47)   /* beam_step<16> */
 #define FV_TV_BEAM_Q16_W8    (1ull << 48)   /* beam_step_q16<8> */
 #define FV_TV_BEAM_Q16_W16   (1ull << 49)   /* beam_step_q16<16> */
+/* Models set by fv_set_model_sparse: trellis_step_csr<NB, MEM> (MEM: score rows read from memory instead of LDS — K beyond
+ * one LDS row, a batch whose NB rows do not fit, or FV_OPT_DEBUG bit 31).  No dense-set model launches them. */
+#define FV_TV_CSR_SHIFT      50
+#define FV_TV_CSR_LDS_NB1    (1ull << (FV_TV_CSR_SHIFT + 0))   /* trellis_step_csr<1, false> */
+#define FV_TV_CSR_LDS_NB2    (1ull << (FV_TV_CSR_SHIFT + 1))   /* trellis_step_csr<2, false> */
+#define FV_TV_CSR_LDS_NB4    (1ull << (FV_TV_CSR_SHIFT + 2))   /* trellis_step_csr<4, false> */
+#define FV_TV_CSR_LDS_NB8    (1ull << (FV_TV_CSR_SHIFT + 3))   /* trellis_step_csr<8, false> */
+#define FV_TV_CSR_MEM_NB1    (1ull << (FV_TV_CSR_SHIFT + 4))   /* trellis_step_csr<1, true> */
+#define FV_TV_CSR_MEM_NB2    (1ull << (FV_TV_CSR_SHIFT + 5))   /* trellis_step_csr<2, true> */
+#define FV_TV_CSR_MEM_NB4    (1ull << (FV_TV_CSR_SHIFT + 6))   /* trellis_step_csr<4, true> */
+#define FV_TV_CSR_MEM_NB8    (1ull << (FV_TV_CSR_SHIFT + 7))   /* trellis_step_csr<8, true> */
 
 #ifdef __cplusplus
 }
