@@ -83,6 +83,61 @@ int launch_beam_step(fv_ctx *ctx, const fvb::BeamStepArgs &a, hipStream_t st)
     return 0;
 }
 
+// Capacity of a step's candidate list under the current options (0: no lists).  FV_OPT_DEBUG bit 10: never a list.
+inline int beam_cand_cap(const fv_ctx *ctx, int K, int beam) { return (ctx->opt_debug & 1024) ? 0 : fvb::cand_cap_for(K, beam); }
+
+// FV_TS_* bit of a select-kernel instantiation (test hooks only)
+unsigned long long select_variant(fvb::SelKernel k)
+{
+    const struct { fvb::SelKernel k; unsigned long long bit; } tab[] = {
+        { fvb::topb_select<4, true>, FV_TS_SEL4_LISTED }, { fvb::topb_select<4, false>, FV_TS_SEL4_DERIVED },
+        { fvb::topb_select<16, true>, FV_TS_SEL16_LISTED }, { fvb::topb_select<16, false>, FV_TS_SEL16_DERIVED },
+        { fvb::topb_select<fvb::SEL_MAX_ROUNDS, true>, FV_TS_SEL64_LISTED }, { fvb::topb_select<fvb::SEL_MAX_ROUNDS, false>, FV_TS_SEL64_DERIVED },
+        { fvb::topb_select_cand<8, true>, FV_TS_CAND8_LISTED }, { fvb::topb_select_cand<8, false>, FV_TS_CAND8_DERIVED },
+        { fvb::topb_select_cand<16, true>, FV_TS_CAND16_LISTED }, { fvb::topb_select_cand<16, false>, FV_TS_CAND16_DERIVED } };
+    for (const auto &e : tab) if (e.k == k) return e.bit;
+    return 0;
+}
+
+// The select of one lock-step — the members of the heaps of `count` passes at lock-step s, one launch: the one rule
+// run_generation_beam and fv_test_beam_select share.  K: states per score row; T: entries of the per-step buffers (which are
+// the context's, indexed by absolute time); rcx.b.passL is ignored: passL[q] (device) and first_of(q) (host) both give the
+// first position of pass q of the launch.
+template <class FirstOf>
+int launch_beam_select(fv_ctx *ctx, int K, int beam, int T, const fvb::ResolveCtx &rcx, const int *passL, int count, int s,
+                       FirstOf &&first_of, hipStream_t st)
+{
+    const int cand_cap = beam_cand_cap(ctx, K, beam), BP = fvb::beam_pitch(beam);
+    fvb::SelArgs a;
+    a.counters = ctx->d_counters.p; a.K = K; a.beam = beam; a.s = s;
+    a.no_wave = (ctx->opt_debug & 32768) ? 1 : 0;
+    a.eager = (ctx->opt_debug & 1048576) ? 1 : 0;             // FV_OPT_DEBUG bit 20: replay every duplicate step at once
+    a.quad_dirty = (ctx->opt_debug & 16777216) ? 1 : 0;
+    a.sb_rounds = (ctx->opt_debug & (1 << 22)) ? 2 : fvb::SEL_MAX_ROUNDS;
+    a.T = T; a.own_pred = (ctx->opt_debug & (1 << 7)) ? 1 : 0;
+    a.margin = ctx->opt_sel_margin; a.cand_cap = cand_cap;
+    a.cand = ctx->d_cand.p; a.cand_count = ctx->d_cand_count.p; a.rc = rcx;
+    a.rc.b.passL = passL;
+    const bool listed = count <= fvb::BEAM_CHUNK;
+    for (int q = 0; listed && q < count; ++q) {
+        const int L = first_of(q), j = L + s;
+        a.p[q] = fvb::SelJob{ ctx->d_scores.p + (size_t)j * K, ctx->d_hval.p + (size_t)j * BP, ctx->d_hstate.p + (size_t)j * BP,
+                              ctx->d_cut.p + (size_t)j * fvb::CUT_W, s >= 1 ? ctx->d_cut.p + (size_t)(j - 1) * fvb::CUT_W : nullptr,
+                              (cand_cap && s >= 1) ? ctx->d_cand.p + (size_t)j * cand_cap : nullptr, ctx->d_cand_count.p + j,
+                              j, L };
+    }
+    // steps >= 2 of a pass have a candidate list (the predictor needs two cut values)
+    // K > 65536 (FV_OPT_DEBUG bit 22: any K): beyond the 64 rounds the register kernels hold, every selection runs in the
+    // lean kernel — on the candidate list where there is one, otherwise over the K scores in memory
+    const bool many = K > fvb::SEL_MAX_ROUNDS * fvb::SEL_BLOCK || (ctx->opt_debug & (1 << 22));
+    fvb::SelKernel lean = (s >= 2 || many) ? fvb::sel_cand_kernel_for(K, cand_cap, listed, many) : nullptr;
+    const fvb::SelKernel kernel = lean ? lean : fvb::sel_kernel_for(K, listed);
+    if (ctx->test_record) ctx->test_selects |= select_variant(kernel);
+    hipLaunchKernelGGL(kernel, dim3(count), dim3(fvb::SEL_BLOCK), fvb::sel_lds(beam), st, a);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
 // T: length of the time axis (a batch: all sequences end to end); ng: stream groups the passes were ordered for;
 // nseq / seq_of: fv_decode_beam_batch — the tie gates are per sequence (seq_of: the device's time -> sequence map).
 int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t pass_off, int beam, int T, int ng,
@@ -91,7 +146,7 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
     const int K = ctx->K, np = (int)passes.size();
     if (np == 0) return 0;
     FV_HIP(hipMemsetAsync(ctx->d_tie_count.p, 0, sizeof(unsigned int), ctx->stream));
-    const int cand_cap = (ctx->opt_debug & 1024) ? 0 : fvb::cand_cap_for(K, beam);     // FV_OPT_DEBUG bit 10: no candidate lists
+    const int cand_cap = beam_cand_cap(ctx, K, beam);
     // passes arrive group by group (decode_beam_impl), longest first inside a group; their first positions are in
     // d_passL[pass_off ..] in the same order
     const int BP = fvb::beam_pitch(beam);
@@ -105,32 +160,8 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
     rcx.b.cut = ctx->d_cut.p; rcx.b.passL = ctx->d_passL.p + pass_off;
     // members of the heaps of passes [first, first + count) at lock-step s: one launch
     auto select = [&](int first, int count, int s, hipStream_t st) -> int {
-        fvb::SelArgs a;
-        a.counters = ctx->d_counters.p; a.K = K; a.beam = beam; a.s = s;
-        a.no_wave = (ctx->opt_debug & 32768) ? 1 : 0;
-        a.eager = (ctx->opt_debug & 1048576) ? 1 : 0;             // FV_OPT_DEBUG bit 20: replay every duplicate step at once
-        a.quad_dirty = (ctx->opt_debug & 16777216) ? 1 : 0;
-        a.sb_rounds = (ctx->opt_debug & (1 << 22)) ? 2 : fvb::SEL_MAX_ROUNDS;
-        a.T = T; a.own_pred = (ctx->opt_debug & (1 << 7)) ? 1 : 0;
-        a.margin = ctx->opt_sel_margin; a.cand_cap = cand_cap;
-        a.cand = ctx->d_cand.p; a.cand_count = ctx->d_cand_count.p; a.rc = rcx;
-        a.rc.b.passL = rcx.b.passL + first;
-        const bool listed = count <= fvb::BEAM_CHUNK;
-        for (int q = 0; listed && q < count; ++q) {
-            const int j = passes[first + q].L + s;
-            a.p[q] = fvb::SelJob{ ctx->d_scores.p + (size_t)j * K, ctx->d_hval.p + (size_t)j * BP, ctx->d_hstate.p + (size_t)j * BP,
-                                  ctx->d_cut.p + (size_t)j * fvb::CUT_W, s >= 1 ? ctx->d_cut.p + (size_t)(j - 1) * fvb::CUT_W : nullptr,
-                                  (cand_cap && s >= 1) ? ctx->d_cand.p + (size_t)j * cand_cap : nullptr, ctx->d_cand_count.p + j,
-                                  j, passes[first + q].L };
-        }
-        // steps >= 2 of a pass have a candidate list (the predictor needs two cut values)
-        // K > 65536 (FV_OPT_DEBUG bit 22: any K): beyond the 64 rounds the register kernels hold, every selection runs in the
-        // lean kernel — on the candidate list where there is one, otherwise over the K scores in memory
-        const bool many = K > fvb::SEL_MAX_ROUNDS * fvb::SEL_BLOCK || (ctx->opt_debug & (1 << 22));
-        fvb::SelKernel lean = (s >= 2 || many) ? fvb::sel_cand_kernel_for(K, cand_cap, listed, many) : nullptr;
-        hipLaunchKernelGGL(lean ? lean : fvb::sel_kernel_for(K, listed), dim3(count), dim3(fvb::SEL_BLOCK), fvb::sel_lds(beam), st, a);
-        FV_HIP(hipGetLastError());
-        return 0;
+        return launch_beam_select(ctx, K, beam, T, rcx, rcx.b.passL + first, count, s,
+                                  [&](int q) { return passes[first + q].L; }, st);
     };
     // init scores (the same rows the full variant starts from, FLASH_BS:407-427)
     int rc0 = 0;
@@ -287,15 +318,16 @@ extern "C" int fv_decode_beam(fv_ctx *ctx, const int *ob, int T, int n_split, in
 }
 
 namespace {
-// Beam widths the beam path takes: the admission fv_decode_beam and fv_test_beam_step share.
-int beam_admit(fv_ctx *ctx, int beam)
+// Beam widths the beam path takes over K states: the admission fv_decode_beam and the test hooks share.
+int beam_admit_k(int K, int beam)
 {
     // beam > K reads uninitialised heap slots in the reference
-    if (beam < 2 || beam > ctx->K) return FV_ERR_ARG;
+    if (beam < 2 || beam > K) return FV_ERR_ARG;
     if (fvb::beam_step_lds(beam) > 150 * 1024 || fvb::beam_step_q16_lds(beam) > 150 * 1024 ||
         fvb::heap_lds(beam) > 150 * 1024) return FV_ERR_UNSUPPORTED;
     return 0;
 }
+int beam_admit(fv_ctx *ctx, int beam) { return beam_admit_k(ctx->K, beam); }
 
 // The row-major tables of the beam step kernels (float64 LA64R, 16-bit LAQ16R and its parameters qpar), built on the
 // device by the first beam decode or test-hook call of a model.
@@ -624,6 +656,127 @@ extern "C" int fv_test_beam_step(fv_ctx *ctx, int beam, const fv_test_beam_set *
     return fvi::drained(ctx, test_beam_step_impl(ctx, beam, sets, nsets, sym, speculative, theta, next_bound, cand_cap, scores_out,
                                                  bp_out, ties_out, tie_count_out, doubt_out, doubt_counts, cand_out, cand_counts,
                                                  variants_out));
+}
+
+namespace {
+// fv_test_beam_select (include/flashvit_testing.h): one select launch over caller-given score rows.  Row q plays time
+// j = 3 q + 2 of a pass that began at j - s: its own records, the previous cut (j - 1) and the slot the seeded predictor
+// reads (j + 1) are no other row's.
+int test_beam_select_impl(fv_ctx *ctx, int K, int beam, int s, const fv_test_select_set *sets, int nsets, float prev_theta,
+                          float prev_margin, const float *seed, int want_layout, int *cand_cap_out, float *cut_out,
+                          float *member_val_out, int *member_state_out, unsigned long long *counters_out, float *slot_val_out,
+                          int *slot_state_out, unsigned long long *selects_out)
+{
+    constexpr int MAX_SETS = 64;
+    static_assert(MAX_SETS <= fvb::HEAP_CHUNK, "one heap_build_all launch");
+    if (!cand_cap_out || s < 0 || s > 2 || nsets < 0 || nsets > MAX_SETS) return FV_ERR_ARG;
+    int rc = beam_admit_k(K, beam);
+    if (rc) return rc;
+    const int cap = beam_cand_cap(ctx, K, beam), BP = fvb::beam_pitch(beam), Tn = 3 * nsets + 3;
+    *cand_cap_out = cap;
+    if (nsets == 0) return FV_OK;
+    if (!sets || !cut_out || !member_val_out || !member_state_out || !counters_out ||
+        (want_layout && (!slot_val_out || !slot_state_out))) return FV_ERR_ARG;
+    for (int q = 0; q < nsets; ++q) {
+        const fv_test_select_set &st = sets[q];
+        if (!st.scores) return FV_ERR_ARG;
+        if (!st.cand) continue;
+        if (cap == 0 || s == 0 || st.cand_count < 0) { ctx->detail = "fv_test_beam_select: a decode has no candidate list here"; return FV_ERR_ARG; }
+        for (int e = 0; e < std::min(st.cand_count, cap); ++e)
+            if (st.cand[e].state < 0 || st.cand[e].state >= K) return FV_ERR_ARG;
+    }
+    FV_HIP(hipSetDevice(ctx->device));
+    auto slot = [](int q) { return (size_t)(3 * q + 2); };
+    FV_HIP(ctx->d_scores.ensure((size_t)Tn * K));
+    FV_HIP(ctx->d_hval.ensure((size_t)Tn * BP));
+    FV_HIP(ctx->d_hstate.ensure((size_t)Tn * BP));
+    FV_HIP(ctx->d_cut.ensure((size_t)Tn * fvb::CUT_W));
+    FV_HIP(ctx->d_doubt_count.ensure(Tn));
+    FV_HIP(ctx->d_cand_count.ensure(Tn));
+    if (cap) FV_HIP(ctx->d_cand.ensure((size_t)Tn * cap));
+    FV_HIP(ctx->d_counters.ensure(FV_NCOUNTERS));
+    FV_HIP(ctx->d_passL.ensure(nsets));
+    if (want_layout) { FV_HIP(ctx->d_slot_val.ensure((size_t)Tn * beam)); FV_HIP(ctx->d_slot_state.ensure((size_t)Tn * beam)); }
+    std::vector<float> cut((size_t)Tn * fvb::CUT_W, std::nanf(""));
+    std::vector<int> counts((size_t)Tn, 0), first((size_t)nsets);
+    static_assert(sizeof(fv_test_cand) == sizeof(fvb::HNode), "fv_test_cand mirrors HNode");
+    for (int q = 0; q < nsets; ++q) {
+        const size_t j = slot(q);
+        first[(size_t)q] = (int)j - s;
+        if (seed) { cut[j * fvb::CUT_W + fvb::CUT_THETA] = seed[0]; cut[(j + 1) * fvb::CUT_W + fvb::CUT_THETA] = seed[1]; }
+        if (s >= 1) {
+            float *c = cut.data() + (j - 1) * fvb::CUT_W;
+            std::fill(c, c + fvb::CUT_W, 0.0f);
+            c[fvb::CUT_THETA] = prev_theta; c[fvb::CUT_STATE] = 0.0f; c[fvb::CUT_NEXT] = HUGE_VALF;
+            c[fvb::CUT_N] = (float)beam; c[fvb::CUT_MARGIN] = prev_margin;
+        }
+        FV_HIP(hipMemcpyAsync(ctx->d_scores.p + j * K, sets[q].scores, (size_t)K * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        if (sets[q].cand) {
+            counts[j] = sets[q].cand_count;
+            FV_HIP(hipMemcpyAsync(ctx->d_cand.p + j * cap, sets[q].cand, (size_t)std::min(sets[q].cand_count, cap) * sizeof(fvb::HNode),
+                                  hipMemcpyHostToDevice, ctx->stream));
+        }
+    }
+    FV_HIP(hipMemcpyAsync(ctx->d_cut.p, cut.data(), cut.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    FV_HIP(hipMemcpyAsync(ctx->d_cand_count.p, counts.data(), counts.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    FV_HIP(hipMemcpyAsync(ctx->d_passL.p, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_hval.p, 0xFF, (size_t)Tn * BP * sizeof(float), ctx->stream));       // NaN / -1: not written
+    FV_HIP(hipMemsetAsync(ctx->d_hstate.p, 0xFF, (size_t)Tn * BP * sizeof(int), ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_doubt_count.p, 0, (size_t)Tn * sizeof(int), ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_counters.p, 0, FV_NCOUNTERS * sizeof(unsigned long long), ctx->stream));
+    fvb::ResolveCtx rcx;        // what only the resolve code reads stays null: no row is a dirty step
+    rcx.counters = ctx->d_counters.p; rcx.K = K; rcx.beam = beam; rcx.no_cut = 0;
+    rcx.LA64R = nullptr; rcx.ld = beam_ld(K); rcx.LB32T = nullptr; rcx.ob = nullptr; rcx.bp = nullptr;
+    rcx.doubt = nullptr; rcx.doubt_count = ctx->d_doubt_count.p;
+    rcx.b.scores_all = ctx->d_scores.p; rcx.b.hval = ctx->d_hval.p; rcx.b.hstate = ctx->d_hstate.p;
+    rcx.b.cut = ctx->d_cut.p; rcx.b.passL = ctx->d_passL.p;
+    struct Restore { fv_ctx *c; ~Restore() { c->test_record = false; } } restore{ ctx };
+    ctx->test_record = true;
+    ctx->test_selects = 0;
+    if ((rc = launch_beam_select(ctx, K, beam, Tn, rcx, ctx->d_passL.p, nsets, s, [&](int q) { return first[(size_t)q]; }, ctx->stream)))
+        return rc;
+    if (want_layout) {
+        fvb::HeapAllArgs h;
+        h.scores_all = ctx->d_scores.p; h.slot_val = ctx->d_slot_val.p; h.slot_state = ctx->d_slot_state.p;
+        h.err_counter = ctx->d_counters.p + 5; h.gate = nullptr; h.seq_of = nullptr;
+        h.K = K; h.beam = beam; h.n = nsets;
+        for (int q = 0; q < nsets; ++q) h.p[q] = fvb::HeapRange{ (int)slot(q), (int)slot(q) };
+        ctx->test_selects |= FV_TS_HEAP_BUILD_ALL;
+        hipLaunchKernelGGL(fvb::heap_build_all, dim3(1, nsets), dim3(128), fvb::heap_lds(beam), ctx->stream, h);
+        FV_HIP(hipGetLastError());
+    }
+    unsigned long long cnt[FV_NCOUNTERS];
+    FV_HIP(hipMemcpyAsync(cut.data(), ctx->d_cut.p, cut.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    FV_HIP(hipMemcpyAsync(cnt, ctx->d_counters.p, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+    for (int q = 0; q < nsets; ++q) {
+        const size_t j = slot(q);
+        FV_HIP(hipMemcpyAsync(member_val_out + (size_t)q * BP, ctx->d_hval.p + j * BP, (size_t)BP * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        FV_HIP(hipMemcpyAsync(member_state_out + (size_t)q * BP, ctx->d_hstate.p + j * BP, (size_t)BP * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        if (want_layout) {
+            FV_HIP(hipMemcpyAsync(slot_val_out + (size_t)q * beam, ctx->d_slot_val.p + j * beam, (size_t)beam * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            FV_HIP(hipMemcpyAsync(slot_state_out + (size_t)q * beam, ctx->d_slot_state.p + j * beam, (size_t)beam * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    FV_HIP(hipStreamSynchronize(ctx->stream));
+    for (int q = 0; q < nsets; ++q)
+        std::copy(cut.begin() + slot(q) * fvb::CUT_W, cut.begin() + (slot(q) + 1) * fvb::CUT_W, cut_out + (size_t)q * fvb::CUT_W);
+    const int which[8] = { 2, 5, 7, 9, 10, 11, 12, 13 };
+    for (int i = 0; i < 8; ++i) counters_out[i] = cnt[which[i]];
+    if (selects_out) *selects_out = ctx->test_selects;
+    return FV_OK;
+}
+}  // namespace
+
+extern "C" int fv_test_beam_select(fv_ctx *ctx, int K, int beam, int s, const fv_test_select_set *sets, int nsets, float prev_theta,
+                                   float prev_margin, const float *seed, int want_layout, int *cand_cap_out, float *cut_out,
+                                   float *member_val_out, int *member_state_out, unsigned long long *counters_out,
+                                   float *slot_val_out, int *slot_state_out, unsigned long long *selects_out)
+{
+    if (!ctx) return FV_ERR_ARG;
+    if (fvi::group_size(ctx) > 1) { ctx->detail = "fv_test_beam_select: one device per context"; return FV_ERR_ARG; }
+    return fvi::drained(ctx, test_beam_select_impl(ctx, K, beam, s, sets, nsets, prev_theta, prev_margin, seed, want_layout, cand_cap_out,
+                                                   cut_out, member_val_out, member_state_out, counters_out, slot_val_out,
+                                                   slot_state_out, selects_out));
 }
 
 #ifdef FV_REPLAY_PROF

@@ -135,6 +135,7 @@ struct fv_ctx {
     // step-kernel instantiation they launch into test_variants (a host branch; nothing else runs on a decode)
     bool test_record = false;
     unsigned long long test_variants = 0;
+    unsigned long long test_selects = 0;     // the same for the select kernels: FV_TS_* bits
 
     // comm
     ncclComm_t comm = nullptr;

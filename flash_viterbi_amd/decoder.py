@@ -59,13 +59,27 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_create_multi", "fv_device_count", "fv_decode_full_batch", "fv_plan_passes_batch", "fv_decode_beam_batch",
            "fv_set_model_sparse"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
-TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step"]
+TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select"]
 TIE_TAG = 1 << 30
+# FV_TS_*: select-kernel instantiations reported by test_beam_select
+TS_BITS = {"topb_select<4,listed>": 1 << 0, "topb_select<4,derived>": 1 << 1, "topb_select<16,listed>": 1 << 2,
+           "topb_select<16,derived>": 1 << 3, "topb_select<64,listed>": 1 << 4, "topb_select<64,derived>": 1 << 5,
+           "topb_select_cand<8,listed>": 1 << 6, "topb_select_cand<8,derived>": 1 << 7, "topb_select_cand<16,listed>": 1 << 8,
+           "topb_select_cand<16,derived>": 1 << 9, "heap_build_all": 1 << 10}
+TS_ALL = (1 << 11) - 1
+CUT_THETA, CUT_STATE, CUT_NEXT, CUT_LIST, CUT_N, CUT_MARGIN, CUT_W = 0, 1, 2, 3, 4, 5, 8
+BEAM_EXTRA = 32                        # entries beyond B a speculative member list can hold
+SELECT_COUNTERS = (2, 5, 7, 9, 10, 11, 12, 13)
 
 
 class ForwardPass(ctypes.Structure):
     """fv_test_pass: steps L+1 .. R from Pi (init_state < 0, L = 0) or from state init_state at time L - 1."""
     _fields_ = [("L", ctypes.c_int), ("R", ctypes.c_int), ("init_state", ctypes.c_int)]
+
+
+class SelectSet(ctypes.Structure):
+    """fv_test_select_set: one score row and, optionally, its candidate list."""
+    _fields_ = [("scores", ctypes.c_void_p), ("cand", ctypes.c_void_p), ("cand_count", ctypes.c_int)]
 
 
 class BeamSet(ctypes.Structure):
@@ -120,6 +134,8 @@ def load_library():
     cf = ctypes.c_float
     L.fv_test_beam_step.argtypes = [vp, ci, ctypes.POINTER(BeamSet), ci, vp, ci, cf, cf, ci, vp, vp, vp, ctypes.POINTER(ci),
                                     vp, vp, vp, vp, ctypes.POINTER(ctypes.c_ulonglong)]
+    L.fv_test_beam_select.argtypes = [vp, ci, ci, ci, ctypes.POINTER(SelectSet), ci, cf, cf, vp, ci, ctypes.POINTER(ci), vp,
+                                      vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_ulonglong)]
     _lib = L
     return L
 
@@ -355,6 +371,60 @@ class FlashViterbi:
         return dict(scores=scores, bp=bp, ties={(int(a), int(b)) for a, b in ties[:nties.value]},
                     doubt=[(int(doubt_counts[q]), doubt[q, :min(int(doubt_counts[q]), 1024)].tolist()) for q in range(n)],
                     cand=out_cand, variants=int(variants.value))
+
+    def select_cand_cap(self, K, beam):
+        """Capacity of the candidate list a decode's select has at (K, beam) under the current options (0: no lists)."""
+        cap = ctypes.c_int(-1)
+        self._check(self._L.fv_test_beam_select(self._h, int(K), int(beam), 0, None, 0, 0.0, 0.0, None, 0, ctypes.byref(cap),
+                                                None, None, None, None, None, None, None))
+        return int(cap.value)
+
+    def test_beam_select(self, beam, rows, s=0, lists=None, prev_theta=0.0, prev_margin=0.0, seed=None, want_layout=True):
+        """fv_test_beam_select: one select launch at lock-step s over rows[nsets, K] (K is the rows' width, not the
+        model's; no model is needed).  lists: None, or per row None / (count, values, states) — a candidate list of `count`
+        entries of which min(count, capacity) are given.  seed: None or (cut left here, cut left at the next time).
+        Returns a dict: cut[nsets, 8] float32, members = per row (values, states) of the CUT_N entries in the order
+        written, raw_val / raw_state[nsets, beam + 32] (NaN / -1 where nothing was written), counters = {index: total}
+        for SELECT_COUNTERS, slot_val / slot_state[nsets, beam] (want_layout), selects = FV_TS_* bits, cand_cap."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        n, K = rows.shape
+        BP = beam + BEAM_EXTRA
+        keep = []
+        arr = (SelectSet * n)()
+        for q in range(n):
+            arr[q].scores = rows[q:q + 1].ctypes.data
+            if lists is not None and lists[q] is not None:
+                count, vals, states = lists[q]
+                rec = np.empty((len(vals), 2), dtype=np.int32)
+                rec[:, 0] = np.ascontiguousarray(vals, dtype=np.float32).view(np.int32)
+                rec[:, 1] = states
+                keep.append(rec)
+                arr[q].cand = rec.ctypes.data
+                arr[q].cand_count = int(count)
+        cap = ctypes.c_int(-1)
+        cut = np.empty((n, CUT_W), dtype=np.float32)
+        mval = np.empty((n, BP), dtype=np.float32)
+        mstate = np.empty((n, BP), dtype=np.int32)
+        counters = np.zeros(len(SELECT_COUNTERS), dtype=np.uint64)
+        sval = np.empty((n, beam), dtype=np.float32)
+        sstate = np.empty((n, beam), dtype=np.int32)
+        selects = ctypes.c_ulonglong(0)
+        sd = None if seed is None else np.ascontiguousarray(seed, dtype=np.float32)
+        self._check(self._L.fv_test_beam_select(self._h, K, int(beam), int(s), arr, n, float(prev_theta), float(prev_margin),
+                                                None if sd is None else _p(sd), 1 if want_layout else 0, ctypes.byref(cap),
+                                                _p(cut), _p(mval), _p(mstate), _p(counters), _p(sval), _p(sstate),
+                                                ctypes.byref(selects)))
+        members = []
+        for q in range(n):
+            cn = int(cut[q, CUT_N]) if np.isfinite(cut[q, CUT_N]) else 0
+            cn = max(0, min(cn, BP))
+            members.append((mval[q, :cn].copy(), mstate[q, :cn].copy()))
+        out = dict(cut=cut, members=members, raw_val=mval, raw_state=mstate,
+                   counters={c: int(v) for c, v in zip(SELECT_COUNTERS, counters)}, selects=int(selects.value),
+                   cand_cap=int(cap.value))
+        if want_layout:
+            out["slot_val"], out["slot_state"] = sval, sstate
+        return out
 
     def stats(self):
         s = Stats()

@@ -1,8 +1,8 @@
 /*
  * flashvit_testing.h — test hooks of libflashvit.so.  NOT part of the drop-in ABI of flashvit.h: no host program
  * or driver calls them, and they may change with the kernels they expose.  They exist so that the test suite can
- * compare whole step outputs (every column of every score and back-pointer row) with a restatement of the
- * recurrence, instead of the T entries of a decoded path.
+ * compare whole step outputs (every column of every score and back-pointer row, every member and slot of a step's
+ * heap) with a restatement of the recurrence, instead of the T entries of a decoded path.
  *
  * The hooks add no work to a decode: what they need on the decode path is a host-side branch on a flag that only
  * a hook call sets (the launch helpers record which step-kernel instantiation they launched).
@@ -60,6 +60,61 @@ int fv_test_beam_step(fv_ctx *ctx, int beam, const fv_test_beam_set *sets, int n
                       float theta, float next_bound, int cand_cap, float *scores_out, int *bp_out, int *ties_out,
                       int *tie_count_out, int *doubt_out, int *doubt_counts, fv_test_cand *cand_out, int *cand_counts,
                       unsigned long long *variants_out);
+
+/* One row of a select launch: K scores and, optionally, the candidate list beam_step's epilogue would have left for the
+ * step — cand_count entries {value, state} in any order, states in [0, K).  cand_count may exceed the list capacity
+ * (*cand_cap_out): cand then holds capacity entries, as an overflowed list does.  cand = NULL: no list. */
+typedef struct { const float *scores; const fv_test_cand *cand; int cand_count; } fv_test_select_set;
+
+/* One select launch of a FLASH-BS lock-step — everything between "a step's K scores are finished" and "the next step's slot
+ * set is staged" — over nsets (1 .. 64) caller-given score rows of K states each, through the launch rule fv_decode_beam
+ * uses (launch_beam_select: kernel family and instantiation by K, beam, s, the number of rows and the list capacity;
+ * FV_OPT_DEBUG bits 7, 10, 15, 20, 22, 24; FV_OPT_SEL_MARGIN) and the admission of `beam` it uses, with the hook's K in
+ * place of the model's.  The context needs no model: a selection reads no table.  More than 24 rows take the form whose
+ * jobs are derived on the device from the pass list.
+ *   s            lock-step of the launch: 0 no previous cut; 1 a previous cut, the predictor's margin not carried; 2 as a
+ *                decode's steps >= 2 (list kernels, margin carried, lists counted as short / long);
+ *   prev_theta, prev_margin   (s >= 1) the previous step's cut record, always non-speculative, CUT_N = beam;
+ *   seed         NULL, or {the cut an earlier generation's pass left at this time, the one it left at the next time}: what
+ *                the seeded predictor reads.  NULL leaves both NaN, as the whole-sequence pass finds them.
+ * Every row is a clean step (no doubtful columns, the previous step decided), at a time slot of its own in the context's
+ * per-step buffers such that no row's records — its cut, the previous one, the next slot the predictor reads — are another's.
+ * Lists are taken only where a decode has one: *cand_cap_out > 0 (cand_cap_for(K, beam), 0 under FV_OPT_DEBUG bit 10) and
+ * s >= 1.  nsets = 0 makes no launch and reports *cand_cap_out only.
+ * Outputs (P = beam + 32, the pitch of a member list):
+ *   cut_out[nsets*8]            the cut record: [0] theta, [1] state (0 exact / 1 speculative / 2 exact, replayed: slot
+ *                               order), [2] the bound predicted for the next cut, [3] list length seen, [4] N, [5] margin;
+ *   member_val_out[nsets*P], member_state_out[nsets*P]   the N member entries in the order written; the rest NaN / -1;
+ *   counters_out[8]             totals of the device counters 2 (exact replays), 5 (broken hand-shakes), 7 (selects on a list),
+ *                               9 (speculative steps), 10 (reach events), 11 / 12 (lists too short / overflowed), 13 (list entries);
+ *   slot_val_out[nsets*beam], slot_state_out[nsets*beam]   (want_layout) the exact heap layout of every row, slot order:
+ *                               heap_build_all over the same rows with no gate;
+ *   selects_out                 (may be NULL) the FV_TS_* bits of the kernels that launched.
+ * FV_ERR_ARG / FV_ERR_UNSUPPORTED before any device work: beam < 2, beam > K, a beam the beam path does not admit, s
+ * outside 0 .. 2, nsets outside 0 .. 64, a list where a decode has none, a negative count, a list state outside [0, K), a
+ * multi-device context.
+ * Out of scope (they need real consecutive steps of a model and stay covered by the decode-level suites): dirty steps,
+ * doubtful_reach, resolve_upto, patch_doubtful, beam_resolve, tie_fixup, beam_end_backtrack.
+ * Overwrites the decode's per-step beam buffers and statistics counters. */
+int fv_test_beam_select(fv_ctx *ctx, int K, int beam, int s, const fv_test_select_set *sets, int nsets, float prev_theta,
+                        float prev_margin, const float *seed, int want_layout, int *cand_cap_out, float *cut_out,
+                        float *member_val_out, int *member_state_out, unsigned long long *counters_out, float *slot_val_out,
+                        int *slot_state_out, unsigned long long *selects_out);
+
+/* Select-kernel instantiations (selects_out): recorded on the host, only during a hook call.  R = rounds of 1024 keys held in
+ * registers; LISTED: job descriptors in the kernel arguments (<= 24 rows), DERIVED: from the pass list on the device. */
+#define FV_TS_SEL4_LISTED     (1ull << 0)    /* topb_select<4, true>: K <= 4096 */
+#define FV_TS_SEL4_DERIVED    (1ull << 1)    /* topb_select<4, false> */
+#define FV_TS_SEL16_LISTED    (1ull << 2)    /* topb_select<16, true>: K <= 16384 */
+#define FV_TS_SEL16_DERIVED   (1ull << 3)    /* topb_select<16, false> */
+#define FV_TS_SEL64_LISTED    (1ull << 4)    /* topb_select<64, true>: K <= 65536, steps without a list */
+#define FV_TS_SEL64_DERIVED   (1ull << 5)    /* topb_select<64, false> */
+#define FV_TS_CAND8_LISTED    (1ull << 6)    /* topb_select_cand<8, true>: K > 16384 at s >= 2, any step at K > 65536 or under bit 22 */
+#define FV_TS_CAND8_DERIVED   (1ull << 7)    /* topb_select_cand<8, false> */
+#define FV_TS_CAND16_LISTED   (1ull << 8)    /* topb_select_cand<16, true>: the same with a list capacity above 8192 (beam > 1024) */
+#define FV_TS_CAND16_DERIVED  (1ull << 9)    /* topb_select_cand<16, false> */
+#define FV_TS_HEAP_BUILD_ALL  (1ull << 10)   /* heap_build_all (want_layout) */
+#define FV_TS_ALL             ((1ull << 11) - 1)
 
 /* Step-kernel instantiations (variants_out).  U = 16-byte loads per lane and chunk, DB = double-buffered in
  * registers (else the whole tile is requested up front), NWV = waves per workgroup.  Every one is reachable on an

@@ -610,6 +610,19 @@ int fvo_beam_step_probe(const fvo_model *m, const float *hval, const int *hstate
     return 0;
 }
 
+/* Test hook: the heap generate_state_heap leaves for one row of scores, slots 1..beam in slot order. */
+int fvo_state_heap_probe(const float *scores, int K, int beam, float *hval_out, int *hstate_out)
+{
+    if (!scores || !hval_out || !hstate_out || K < 1 || beam < 1 || beam > K) return FVO_ERR_ARG;
+    hnode *h = (hnode *)malloc(sizeof(hnode) * ((size_t)beam + 1));
+    if (!h) return FVO_ERR_NOMEM;
+    heap_reset(h);
+    for (int i = 0; i < K; ++i) heap_offer(h, beam, scores[i], i, -1);
+    for (int k = 0; k < beam; ++k) { hval_out[k] = h[k + 1].value; hstate_out[k] = h[k + 1].state; }
+    free(h);
+    return 0;
+}
+
 /* The whole-sequence end pick, FLASH_BS:456-461 / :376-381: slot 1, then slots
  * beam/2+2 .. beam; leaf slot beam/2+1 is never looked at. */
 static int beam_final_slot(const hnode *h, int beam, float *score_out)

@@ -52,6 +52,10 @@ int fvo_beam_decode(const fvo_model *m, const int *ob, int T, int n_split, int b
 int fvo_beam_step_probe(const fvo_model *m, const float *hval, const int *hstate, int beam, int o, int blocked,
                         float *scr, int *argv);
 
+/* Test hook: generate_state_heap (FLASH_BS:167-211) over one row of K scores, no model: heap_reset, then
+ * heap_offer(h, beam, scores[i], i, -1) for i = 0 .. K-1.  Slots 1..beam in slot order (1 <= beam <= K). */
+int fvo_state_heap_probe(const float *scores, int K, int beam, float *hval_out, int *hstate_out);
+
 /* viterbi() of the reference's baseline Base_line/C implementations/vanilla Viterbi.c:125-173 (also the
  * output of its checkpoint Viterbi.c: same recurrence, different memory schedule). */
 int fvo_vanilla_decode(const fvo_model *m, const int *ob, int T, int *path, float *score);

@@ -51,6 +51,7 @@ def lib():
         L.fvo_checkpoint_memory_bytes.argtypes = [ci, ci, ci]
         L.fvo_checkpoint_memory_bytes.restype = ctypes.c_longlong
         L.fvo_beam_step_probe.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
+        L.fvo_state_heap_probe.argtypes = [vp, ci, ci, vp, vp]
         L.fvo_set_threads.argtypes = [ci]
         L.fvo_full_memory_bytes.restype = ctypes.c_longlong
         L.fvo_full_memory_bytes.argtypes = [ci, ci, ci]
@@ -154,6 +155,18 @@ class OracleModel:
         if rc:
             raise OracleError(rc)
         return row, args
+
+
+def state_heap(scores, beam):
+    """The heap generate_state_heap leaves for one row of scores (no model): (values float32[beam], states
+    int32[beam]), slots 1..beam in slot order."""
+    scores = np.ascontiguousarray(scores, dtype=np.float32).reshape(-1)
+    hval = np.empty(int(beam), dtype=np.float32)
+    hstate = np.empty(int(beam), dtype=np.int32)
+    rc = lib().fvo_state_heap_probe(_p(scores), scores.size, int(beam), _p(hval), _p(hstate))
+    if rc:
+        raise OracleError(rc)
+    return hval, hstate
 
 
 def checkpoint_memory_bytes(K, T, step=0):
