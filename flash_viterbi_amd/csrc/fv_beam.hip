@@ -55,7 +55,8 @@ int launch_beam_step(fv_ctx *ctx, const fvb::BeamStepArgs &a, hipStream_t st)
     // float64 refine): measured at K = 16384, B = 256 it takes 13.7 us + 2.6 us per extra pass of the
     // launch against 10.6 + 5.0 for the float64 kernel, so it is used from ~80 MB of float64 rows per
     // launch on (cfg5: 537 MB per pass).  FV_OPT_DEBUG bit 8: never, bit 9: always.
-    const bool use_q16 = ctx->beam_q16_ready && !(ctx->opt_debug & 256) &&
+    // (emission scores above 0, fv_set_emissions: the float64 kernel, as for a model with an entry above 1)
+    const bool use_q16 = ctx->beam_q16_ready && ctx->view.logs_nonpositive && !(ctx->opt_debug & 256) &&
                          ((ctx->opt_debug & 512) || (double)a.n * beam * K * 8.0 >= 80e6);
     // 8-wave workgroups once the launch has more 16-wave workgroups than fit the chip together (two per CU);
     // FV_OPT_DEBUG bit 25: never, bit 26: always
@@ -154,7 +155,7 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
     fvb::ResolveCtx rcx;
     rcx.counters = ctx->d_counters.p; rcx.K = K; rcx.beam = beam;
     rcx.no_cut = (ctx->opt_debug & (1 << 23)) ? 1 : 0;
-    rcx.LA64R = ctx->LA64R.p; rcx.ld = beam_ld(K); rcx.LB32T = ctx->LB32T.p; rcx.ob = ctx->d_ob.p;
+    rcx.LA64R = ctx->LA64R.p; rcx.ld = beam_ld(K); rcx.LB32T = ctx->view.lb32; rcx.ob = ctx->d_ob.p;
     rcx.bp = ctx->d_bp.p; rcx.doubt = ctx->d_doubt.p; rcx.doubt_count = ctx->d_doubt_count.p;
     rcx.b.scores_all = ctx->d_scores.p; rcx.b.hval = ctx->d_hval.p; rcx.b.hstate = ctx->d_hstate.p;
     rcx.b.cut = ctx->d_cut.p; rcx.b.passL = ctx->d_passL.p + pass_off;
@@ -205,7 +206,7 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
                     a.p[q].doubt_count = ctx->d_doubt_count.p + j;
                     a.p[q].scores = ctx->d_scores.p + (size_t)j * K;
                     a.p[q].bp_row = ctx->d_bp.p + (size_t)j * K;
-                    a.p[q].tmp_row = ctx->LB32T.p + (size_t)ctx->h_ob[j] * K;
+                    a.p[q].tmp_row = ctx->view.lb32 + (size_t)ctx->h_ob[j] * K;
                     a.p[q].j = j;
                     a.p[q].cut = ctx->d_cut.p + (size_t)(j - 1) * fvb::CUT_W;
                     a.p[q].dupwin = ctx->d_dupwin.p + j;
@@ -288,7 +289,7 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
     if ((rc = layouts(false, ctx->d_needfull.p))) return rc;
     {
         fvb::FixArgs f;
-        f.LA64R = ctx->LA64R.p; f.LB32T = ctx->LB32T.p; f.ob = ctx->d_ob.p;
+        f.LA64R = ctx->LA64R.p; f.LB32T = ctx->view.lb32; f.ob = ctx->d_ob.p;
         f.tie_count = ctx->d_tie_count.p; f.tie_list = ctx->d_tie_list.p; f.tie_cap = (unsigned int)ctx->d_tie_list.n;
         f.slot_val = ctx->d_slot_val.p; f.slot_state = ctx->d_slot_state.p; f.bp = ctx->d_bp.p;
         f.K = K; f.ld = beam_ld(K); f.beam = beam; f.total = ctx->d_counters.p + 6; f.gate = ctx->d_needfull.p;
@@ -441,11 +442,12 @@ int run_beam_generations(fv_ctx *ctx, std::vector<std::vector<fv::Pass>> &gens, 
 
 int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_width, int mode, int *path_out, float *score_out)
 {
-    if (!ctx || !ob || !path_out || T < 2 || n_split < 1) return FV_ERR_ARG;
-    if (ctx->K == 0) return FV_ERR_STATE;
-    int rc = beam_admit(ctx, beam_width);
+    if (!ctx || !path_out || T < 2 || n_split < 1) return FV_ERR_ARG;
+    int rc = fvi::emission_view(ctx, ob, T);
     if (rc) return rc;
-    for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->M) return FV_ERR_ARG;
+    if (ctx->K == 0) return FV_ERR_STATE;
+    if ((rc = beam_admit(ctx, beam_width))) return rc;
+    for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
     auto t0 = clk::now();
     FV_HIP(hipSetDevice(ctx->device));
     fv::Plan plan;
@@ -460,9 +462,7 @@ int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_wi
     if ((rc = beam_workspace(ctx, T, beam_width, 0))) return rc;
     if ((rc = beam_tables(ctx))) return rc;
 
-    const double keep_model_ms = ctx->stats.set_model_ms;
-    ctx->stats = fv_stats{};
-    ctx->stats.set_model_ms = keep_model_ms;
+    ctx->fresh_stats();
     ctx->stats.kernel = FV_KERNEL_F64_STREAM;
     ctx->stats.generations = plan.generations();
     ctx->stats.table_bytes_per_step = (long long)beam_width * ctx->K * 8;
@@ -480,7 +480,7 @@ int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_wi
 int decode_beam_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split, int beam_width, int mode,
                            int *path_out, float *score_out, int *status_out)
 {
-    if (!ob || !offsets || !path_out || nseq < 1 || n_split < 1) return FV_ERR_ARG;
+    if (!offsets || !path_out || nseq < 1 || n_split < 1) return FV_ERR_ARG;
     if (mode != FV_MODE_REFERENCE && mode != FV_MODE_SINGLE_PASS) return FV_ERR_ARG;
     if (offsets[0] != 0) { ctx->detail = "fv_decode_beam_batch: offsets[0] must be 0"; return FV_ERR_ARG; }
     std::vector<int> lengths((size_t)nseq);
@@ -491,12 +491,13 @@ int decode_beam_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets,
         if (offsets[s + 1] > 0x7fffffffLL) { ctx->detail = "fv_decode_beam_batch: more than 2^31 - 1 observations in all (at sequence " + std::to_string(s) + ")"; return FV_ERR_ARG; }
         lengths[(size_t)s] = (int)len;
     }
-    if (ctx->K == 0) return FV_ERR_STATE;
-    int rc = beam_admit(ctx, beam_width);
+    int rc = fvi::emission_view(ctx, ob, offsets[nseq]);       // (ob == NULL: sequence s on staged rows offsets[s] ..)
     if (rc) return rc;
+    if (ctx->K == 0) return FV_ERR_STATE;
+    if ((rc = beam_admit(ctx, beam_width))) return rc;
     for (int s = 0; s < nseq; ++s)
         for (long long j = offsets[s]; j < offsets[s + 1]; ++j)
-            if (ob[j] < 0 || ob[j] >= ctx->M) {
+            if (ob[j] < 0 || ob[j] >= ctx->view.nsym) {
                 ctx->detail = "fv_decode_beam_batch: sequence " + std::to_string(s) + " holds a symbol outside [0, M) at position " + std::to_string(j - offsets[s]);
                 return FV_ERR_ARG;
             }
@@ -516,9 +517,7 @@ int decode_beam_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets,
     if ((rc = fvi::ensure_workspace(ctx, sumT, 1, std::max(nseq, 2)))) return rc;
     if ((rc = beam_tables(ctx))) return rc;
 
-    const double keep_model_ms = ctx->stats.set_model_ms;
-    ctx->stats = fv_stats{};
-    ctx->stats.set_model_ms = keep_model_ms;
+    ctx->fresh_stats();
     ctx->stats.kernel = FV_KERNEL_F64_STREAM;
     ctx->stats.generations = plan.generations();
     ctx->stats.table_bytes_per_step = (long long)beam_width * ctx->K * 8;
@@ -561,6 +560,10 @@ int test_beam_step_impl(fv_ctx *ctx, int beam, const fv_test_beam_set *sets, int
     if (ctx->K == 0) return FV_ERR_STATE;
     int rc = beam_admit(ctx, beam);
     if (rc) return rc;
+    {   // model symbols only: the launch rule reads the view of the model's log B
+        const int *model_ob = sym;
+        if ((rc = fvi::emission_view(ctx, model_ob, nsets))) return rc;
+    }
     const int K = ctx->K, BP = fvb::beam_pitch(beam);
     // the kernels stage beam_pitch(beam) entries of every set, whatever its length: the rest is padding
     std::vector<float> hv((size_t)nsets * BP, -HUGE_VALF), cut((size_t)nsets * fvb::CUT_W, 0.0f);

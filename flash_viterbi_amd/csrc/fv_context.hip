@@ -1,6 +1,7 @@
 // fv_context.hip — context life cycle, model upload, options, workspace and the decode epilogue of libflashvit.so.
 // No kernels of its own: the full-state ones live in fv_full.hip, the FLASH-BS ones in fv_beam.hip.
 #include "fv_internal.h"
+#include "flashvit_testing.h"
 
 namespace {
 
@@ -33,7 +34,8 @@ size_t device_bytes(const fv_ctx *c)
            c->d_score.bytes() + c->d_counters.bytes() + c->d_hval.bytes() + c->d_scores.bytes() +
            c->d_hstate.bytes() + c->d_flags.bytes() + c->d_slot_val.bytes() + c->d_slot_state.bytes() +
            c->LA64R.bytes() + c->LAQ16R.bytes() + c->d_qaux.bytes() + c->d_tie_list.bytes() + c->d_tie_count.bytes() + c->d_cut.bytes() + c->d_dupwin.bytes() + c->d_cand.bytes() + c->d_cand_count.bytes() + c->d_passL.bytes() + c->d_needfull.bytes() + c->d_seqof.bytes() + c->d_doubt.bytes() + c->d_doubt_count.bytes() + c->d_pack.bytes() +
-           c->CSk.bytes() + c->CSq.bytes() + c->CS64.bytes() + c->CSoff.bytes() + c->CSnwb.bytes() + c->CRptr.bytes() + c->CRcol.bytes() + c->CRlog.bytes();
+           c->CSk.bytes() + c->CSq.bytes() + c->CS64.bytes() + c->CSoff.bytes() + c->CSnwb.bytes() + c->CRptr.bytes() + c->CRcol.bytes() + c->CRlog.bytes() +
+           c->E32.bytes() + c->E64.bytes() + c->d_emflags.bytes();
 }
 
 // ints in front of the answers in the result block: the counters (64-bit each), then the scores (one per sequence of a
@@ -113,6 +115,28 @@ __global__ void clear_outputs(unsigned long long *counters, int *ans, int T)
     const int tid = blockIdx.x * blockDim.x + threadIdx.x;
     if (tid < FV_NCOUNTERS) counters[tid] = 0ull;
     for (int i = tid; i < T; i += gridDim.x * blockDim.x) ans[i] = 0;
+}
+
+int emission_view(fv_ctx *ctx, const int *&ob, long long T)
+{
+    if (ob) {
+        ctx->view.lb32 = ctx->LB32T.p; ctx->view.lb64 = ctx->LB64T.p; ctx->view.nsym = ctx->M;
+        ctx->view.logs_nonpositive = ctx->logs_nonpositive;
+        return 0;
+    }
+    // (a context without a model has nothing staged: fv_set_emissions needs K, the model setters drop the rows)
+    if (ctx->emis_rows == 0) { ctx->detail = "ob == NULL: no emission scores are staged (fv_set_emissions)"; return FV_ERR_ARG; }
+    if (T < 1 || T > ctx->emis_rows) {
+        ctx->detail = "ob == NULL: " + std::to_string(T) + " times asked for, " + std::to_string(ctx->emis_rows) + " rows of emission scores staged";
+        return FV_ERR_ARG;
+    }
+    try {
+        for (size_t j = ctx->h_iota.size(); j < (size_t)T; ++j) ctx->h_iota.push_back((int)j);
+    } catch (const std::bad_alloc &) { return FV_ERR_NOMEM; }
+    ob = ctx->h_iota.data();
+    ctx->view.lb32 = ctx->E32.p; ctx->view.lb64 = ctx->E64.p; ctx->view.nsym = (int)ctx->emis_rows;
+    ctx->view.logs_nonpositive = ctx->logs_nonpositive && !ctx->emis_positive;
+    return 0;
 }
 
 int begin_decode(fv_ctx *ctx, const int *ob, int T)
@@ -308,6 +332,7 @@ extern "C" void fv_destroy(fv_ctx *ctx)
     ctx->d_hstate.release(); ctx->d_flags.release(); ctx->d_slot_val.release(); ctx->d_slot_state.release();
     ctx->LA64R.release(); ctx->LAQ16R.release(); ctx->d_qaux.release(); ctx->d_tie_list.release(); ctx->d_tie_count.release(); ctx->d_cut.release(); ctx->d_dupwin.release(); ctx->d_cand.release(); ctx->d_cand_count.release(); ctx->d_passL.release(); ctx->d_needfull.release(); ctx->d_seqof.release(); ctx->d_doubt.release(); ctx->d_doubt_count.release(); ctx->d_pack.release();
     fvi::release_csr(ctx);
+    ctx->E32.release(); ctx->E64.release(); ctx->d_emflags.release();
     if (ctx->h_pin) { (void)hipHostFree(ctx->h_pin); ctx->h_pin = nullptr; ctx->h_pin_n = 0; }
     for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
@@ -489,6 +514,7 @@ int upload_tables(fv_ctx *ctx, const HostTables &h)
     FV_HIP(hipSetDevice(ctx->device));
     ctx->K = 0; ctx->M = 0; ctx->nrows = 0; ctx->full_ok = false; ctx->u16_ok = false; ctx->laq16_ready = false;
     ctx->rowq_ready = false; ctx->beam_q16_ready = false;
+    ctx->emis_rows = 0; ctx->emis_positive = false;      // staged emission scores belong to the model they were staged under
     (void)hipStreamSynchronize(ctx->stream);
     ctx->LA64R.release(); ctx->LAQ16R.release();
     ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release();
@@ -668,6 +694,7 @@ int upload_csr(fv_ctx *ctx, const HostCsr &h, const long long *row_ptr, const in
     FV_HIP(hipSetDevice(ctx->device));
     ctx->K = 0; ctx->M = 0; ctx->nrows = 0; ctx->full_ok = false; ctx->u16_ok = false; ctx->laq16_ready = false;
     ctx->rowq_ready = false; ctx->beam_q16_ready = false;
+    ctx->emis_rows = 0; ctx->emis_positive = false;      // staged emission scores belong to the model they were staged under
     (void)hipStreamSynchronize(ctx->stream);
     ctx->LA64R.release(); ctx->LAQ16R.release();
     ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release();
@@ -744,6 +771,169 @@ extern "C" int fv_set_model(fv_ctx *ctx, const float *A, const float *B, const f
         if ((rc = fvi::upload_tables(m, h))) { if (m != ctx) ctx->detail = m->detail; return rc; }
     }
     ctx->stats.set_model_ms = ms_since(t0);
+    return FV_OK;
+}
+
+namespace fvi {
+
+// fv_set_emissions on one device.  A block the kernel cannot read where it lies (host memory; a multi-device context,
+// whose members each take a copy) goes into a raw device buffer first, released before the call returns.
+static int stage_emissions_on(fv_ctx *ctx, const void *scores, int dtype, int T, long long ld, bool in_place)
+{
+    FV_HIP(hipSetDevice(ctx->device));
+    const size_t K = (size_t)ctx->K, esz = dtype == FV_EMIS_LOG_F64 ? 8 : 4, cells = (size_t)T * K;
+    const size_t raw_bytes = in_place ? 0 : ((size_t)(T - 1) * (size_t)ld + K) * esz;      // (the last row ends at its K-th element)
+    {   // sized in 64 bits and compared with the free device memory before anything is allocated
+        unsigned long long grow = raw_bytes, released = 0;
+        if (cells > ctx->E32.n) { grow += 4ull * cells; released += ctx->E32.bytes(); }
+        if (cells > ctx->E64.n) { grow += 8ull * cells; released += ctx->E64.bytes(); }
+        size_t free_b = 0, total_b = 0;
+        FV_HIP(hipMemGetInfo(&free_b, &total_b));
+        if (grow > (unsigned long long)free_b + released) {
+            ctx->detail = "fv_set_emissions: " + std::to_string(grow) + " bytes needed (tables " + std::to_string(12ull * cells) +
+                          ", raw copy " + std::to_string((unsigned long long)raw_bytes) + "), " +
+                          std::to_string((unsigned long long)free_b + released) + " bytes of device memory free";
+            return FV_ERR_NOMEM;
+        }
+    }
+    FV_HIP(ctx->E32.ensure(cells));
+    FV_HIP(ctx->E64.ensure(cells));
+    FV_HIP(ctx->d_emflags.ensure(2));
+    DevBuf<unsigned char> raw;
+    struct Free { DevBuf<unsigned char> &b; ~Free() { b.release(); } } free_raw{ raw };
+    const void *src = scores;
+    if (!in_place) {
+        FV_HIP(raw.ensure(raw_bytes));
+        FV_HIP(hipMemcpyAsync(raw.p, scores, raw_bytes, hipMemcpyDefault, ctx->stream));
+        src = raw.p;
+    }
+    unsigned long long got[2] = { 0ull, ~0ull };
+    FV_HIP(hipMemsetAsync(ctx->d_emflags.p, 0, sizeof(unsigned long long), ctx->stream));               // no flag
+    FV_HIP(hipMemsetAsync(ctx->d_emflags.p + 1, 0xFF, sizeof(unsigned long long), ctx->stream));        // no refused index
+    if (int rc = launch_stage_emissions(ctx, src, dtype, ld, T)) return rc;
+    FV_HIP(hipMemcpyAsync(got, ctx->d_emflags.p, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
+    FV_HIP(hipStreamSynchronize(ctx->stream));              // the one sync of the call: copies and kernel are done, `raw` can go
+    if (got[0] & FV_EMIS_BAD) {
+        ctx->detail = "fv_set_emissions: the score at (t = " + std::to_string(got[1] / K) + ", state = " + std::to_string(got[1] % K) +
+                      ") is NaN, +inf or beyond the float32 range; scores are finite or -inf";
+        return FV_ERR_ARG;
+    }
+    ctx->emis_positive = (got[0] & FV_EMIS_POSITIVE) != 0;
+    ctx->emis_rows = T;
+    return FV_OK;
+}
+
+}  // namespace fvi
+
+extern "C" int fv_set_emissions(fv_ctx *ctx, const void *scores, int dtype, int T, long long ld)
+{
+    if (!ctx) return FV_ERR_ARG;
+    const int n = fvi::group_size(ctx);
+    for (int r = 0; r < n; ++r) {                // whatever happens next, the rows staged before are gone
+        fv_ctx *m = fvi::group_member(ctx, r);
+        m->emis_rows = 0; m->emis_positive = false;
+    }
+    ctx->stats.emission_rows = 0;
+    ctx->stats.set_emissions_ms = 0.0;           // (a refused call staged nothing: no time to report)
+    if (ctx->K == 0) { ctx->detail = "fv_set_emissions: no model (the row length K is the model's)"; return FV_ERR_STATE; }
+    if (!scores || T < 1 || ld < ctx->K || ld > (1ll << 59) / T || (dtype != FV_EMIS_LOG_F32 && dtype != FV_EMIS_LOG_F64)) {
+        ctx->detail = "fv_set_emissions: scores != NULL, T >= 1, ld >= K and dtype FV_EMIS_LOG_F32 or FV_EMIS_LOG_F64";
+        return FV_ERR_ARG;
+    }
+    auto t0 = clk::now();
+    // where the block lies: a pointer the runtime does not know (plain malloc) makes the query fail — that is host memory
+    hipPointerAttribute_t at{};
+    bool on_device = false;
+    if (hipPointerGetAttributes(&at, scores) == hipSuccess) on_device = at.type == hipMemoryTypeDevice;
+    else (void)hipGetLastError();
+    for (int r = 0; r < n; ++r) {
+        fv_ctx *m = fvi::group_member(ctx, r);
+        const bool in_place = on_device && n == 1 && at.device == m->device;
+        const int rc = fvi::drained(m, fvi::stage_emissions_on(m, scores, dtype, T, ld, in_place));
+        if (rc) {
+            if (m != ctx) ctx->detail = m->detail;
+            for (int q = 0; q < n; ++q) fvi::group_member(ctx, q)->emis_rows = 0;
+            ctx->stats.device_bytes = (long long)fvi::device_bytes(ctx);      // the tables may have grown before the refusal
+            return rc;
+        }
+    }
+    ctx->stats.set_emissions_ms = ms_since(t0);
+    ctx->stats.emission_rows = T;
+    ctx->stats.device_bytes = (long long)fvi::device_bytes(ctx);
+    return FV_OK;
+}
+
+extern "C" int fv_clear_emissions(fv_ctx *ctx)
+{
+    if (!ctx) return FV_ERR_ARG;
+    const int n = fvi::group_size(ctx);
+    for (int r = 0; r < n; ++r) {
+        fv_ctx *m = fvi::group_member(ctx, r);
+        (void)hipSetDevice(m->device);
+        m->emis_rows = 0; m->emis_positive = false;
+        m->E32.release(); m->E64.release();
+    }
+    ctx->stats.emission_rows = 0;
+    ctx->stats.device_bytes = (long long)fvi::device_bytes(ctx);
+    return FV_OK;
+}
+
+// include/flashvit_testing.h: device memory for a test that has no HIP runtime of its own
+extern "C" int fv_test_device_alloc(fv_ctx *ctx, size_t bytes, const void *host_src, void **out)
+{
+    if (!ctx || !out || bytes == 0) return FV_ERR_ARG;
+    *out = nullptr;
+    FV_HIP(hipSetDevice(ctx->device));
+    void *p = nullptr;
+    FV_HIP(hipMalloc(&p, bytes));
+    if (host_src) {
+        hipError_t e = hipMemcpy(p, host_src, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(p); FV_HIP(e); }
+    }
+    *out = p;
+    return FV_OK;
+}
+
+extern "C" int fv_test_device_free(fv_ctx *ctx, void *p)
+{
+    if (!ctx) return FV_ERR_ARG;
+    FV_HIP(hipSetDevice(ctx->device));
+    if (p) FV_HIP(hipFree(p));
+    return FV_OK;
+}
+
+// include/flashvit_testing.h: the staging kernel alone between two device events, reps launches back to back
+extern "C" int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, int dtype, int T, long long ld, int reps, float *ms_out)
+{
+    if (!ctx || !ms_out || !dev_scores || T < 1 || reps < 1 || ctx->K == 0 || ld < ctx->K || ld > (1ll << 59) / T ||
+        (dtype != FV_EMIS_LOG_F32 && dtype != FV_EMIS_LOG_F64) || ctx->group)
+        return FV_ERR_ARG;
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, dev_scores) != hipSuccess) { (void)hipGetLastError(); return FV_ERR_ARG; }
+    if (at.type != hipMemoryTypeDevice || at.device != ctx->device) return FV_ERR_ARG;
+    FV_HIP(hipSetDevice(ctx->device));
+    ctx->emis_rows = 0; ctx->emis_positive = false;         // the tables are overwritten: nothing stays staged
+    ctx->stats.emission_rows = 0;
+    const size_t cells = (size_t)T * (size_t)ctx->K;
+    FV_HIP(ctx->E32.ensure(cells));
+    FV_HIP(ctx->E64.ensure(cells));
+    FV_HIP(ctx->d_emflags.ensure(2));
+    FV_HIP(hipMemsetAsync(ctx->d_emflags.p, 0, sizeof(unsigned long long), ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_emflags.p + 1, 0xFF, sizeof(unsigned long long), ctx->stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    struct Ev { hipEvent_t &a, &b; ~Ev() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev{ e0, e1 };
+    FV_HIP(hipEventCreate(&e0));
+    FV_HIP(hipEventCreate(&e1));
+    if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T)) return fvi::drained(ctx, rc);      // warm
+    FV_HIP(hipEventRecord(e0, ctx->stream));
+    for (int r = 0; r < reps; ++r)
+        if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T)) return fvi::drained(ctx, rc);
+    FV_HIP(hipEventRecord(e1, ctx->stream));
+    FV_HIP(hipStreamSynchronize(ctx->stream));
+    float ms = 0.0f;
+    FV_HIP(hipEventElapsedTime(&ms, e0, e1));
+    *ms_out = ms / (float)reps;
+    ctx->stats.device_bytes = (long long)fvi::device_bytes(ctx);
     return FV_OK;
 }
 

@@ -14,7 +14,7 @@ int pick_kernel(const fv_ctx *ctx)
 {
     if (ctx->opt_kernel == FV_KERNEL_F64_STREAM) return FV_KERNEL_F64_STREAM;
     // the filter kernels' error bracket needs every log <= 0 (no cancellation between score and log A)
-    if (!ctx->logs_nonpositive) return FV_KERNEL_F64_STREAM;
+    if (!ctx->view.logs_nonpositive) return FV_KERNEL_F64_STREAM;
     // Measured at K=3965 (us per step of the whole-sequence pass): q16 9.5, f32 11.1, f16 12.8, f64 20.7.
     // binary16's 2^-11 relative spacing makes its window ~0.008 wide (~430 extra candidates and ~7 lane
     // rescans per step); 16-bit fixed point has a window of ~3e-4 (~21 and 0.4) at the same 2 B/cell.
@@ -356,10 +356,10 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
         }
         if (ctx->csr)
             hipLaunchKernelGGL(fvk::init_rows_csr, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->CRptr.p,
-                               ctx->CRcol.p, ctx->CRlog.p, ctx->LB64T.p, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, ctx->d_rows.p, K);
+                               ctx->CRcol.p, ctx->CRlog.p, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, ctx->d_rows.p, K);
         else
         hipLaunchKernelGGL(fvk::init_rows, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch,
-                           ctx->LA64.p, ctx->nrows, ctx->LB64T.p, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p,
+                           ctx->LA64.p, ctx->nrows, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p,
                            ctx->d_rows.p, K);
         FV_HIP(hipGetLastError());
     }
@@ -434,8 +434,8 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
                 const fv::Pass &p = passes[base + q];
                 slots[q].t1_in = row(base + q, (s - 1) & 1);
                 slots[q].t1_out = row(base + q, s & 1);
-                slots[q].tmp_row = ctx->LB32T.p + (size_t)ctx->h_ob[p.L + s] * K;
-                slots[q].tmp64_row = ctx->LB64T.p + (size_t)ctx->h_ob[p.L + s] * K;
+                slots[q].tmp_row = ctx->view.lb32 + (size_t)ctx->h_ob[p.L + s] * K;
+                slots[q].tmp64_row = ctx->view.lb64 + (size_t)ctx->h_ob[p.L + s] * K;
                 slots[q].bp_out = ctx->d_bp.p + (size_t)(p.L + s) * K;
             }
             hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -481,7 +481,7 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
                 const int owner = (two && s > 1) ? (q / cap) % nstreams : 0;
                 if (owner != sid) continue;
                 const fv::Pass &p = passes[q];
-                c.p[c.n++] = fvk::ColJob{ row(q, (s - 1) & 1), ctx->LB32T.p + (size_t)ctx->h_ob[p.R] * K, ctx->d_bp.p + (size_t)p.R * K, p.R };
+                c.p[c.n++] = fvk::ColJob{ row(q, (s - 1) & 1), ctx->view.lb32 + (size_t)ctx->h_ob[p.R] * K, ctx->d_bp.p + (size_t)p.R * K, p.R };
                 if (c.n == fvk::COL_CHUNK) { int rc = flush(); if (rc) return rc; }
             }
             int rc = flush();
@@ -579,7 +579,22 @@ int full_setup(fv_ctx *ctx)
 int launch_init_rows(fv_ctx *ctx, const fvk::PassChunk &ch, float *rows)
 {
     hipLaunchKernelGGL(fvk::init_rows, dim3((ctx->K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch,
-                       ctx->LA64.p, ctx->nrows, ctx->LB64T.p, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, rows, ctx->K);
+                       ctx->LA64.p, ctx->nrows, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, rows, ctx->K);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+// Workgroups of EMIS_BLOCK states by rows, about 2048 in all (eight per CU); the kernel strides over the rest.
+int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T)
+{
+    const int K = ctx->K;
+    const int gx = std::min((K + fvk::EMIS_BLOCK - 1) / fvk::EMIS_BLOCK, 2048), gy = std::max(1, std::min(T, 2048 / gx));
+    if (dtype == FV_EMIS_LOG_F64)
+        hipLaunchKernelGGL(fvk::stage_emissions<double>, dim3(gx, gy), dim3(fvk::EMIS_BLOCK), 0, ctx->stream,
+                           static_cast<const double *>(src), ld, T, K, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p);
+    else
+        hipLaunchKernelGGL(fvk::stage_emissions<float>, dim3(gx, gy), dim3(fvk::EMIS_BLOCK), 0, ctx->stream,
+                           static_cast<const float *>(src), ld, T, K, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -638,29 +653,29 @@ int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &ker
             ctx->detail = "a model set by fv_set_model_sparse has no dense table: FV_KERNEL_AUTO or FV_KERNEL_SPARSE_Q16";
             return FV_ERR_UNSUPPORTED;
         }
-        if (!ctx->logs_nonpositive) {
+        if (!ctx->view.logs_nonpositive) {
             ctx->detail = "fv_set_model_sparse: the walk over the stored entries is a filter kernel and needs every model entry in [0,1]";
             return FV_ERR_UNSUPPORTED;
         }
-        for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->M) return FV_ERR_ARG;
+        for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
         FV_HIP(hipSetDevice(ctx->device));
         kernel = FV_KERNEL_SPARSE_CSR;
         return fvi::ensure_workspace(ctx, T, rows_needed, nscores);
     }
     const bool wide = !ctx->full_ok;
-    const bool big = wide && ctx->u16_ok && ctx->logs_nonpositive && !ctx->vanilla &&
+    const bool big = wide && ctx->u16_ok && ctx->view.logs_nonpositive && !ctx->vanilla &&
                      (ctx->opt_kernel == FV_KERNEL_AUTO || ctx->opt_kernel == FV_KERNEL_U16_REFINE);
     // ... and the same slabs for the f32 filter on the 16-bit table (2 B per cell; model entries in [0,1]): what AUTO takes
     // beyond K = 65536
-    const bool wide_q16 = wide && !big && ctx->logs_nonpositive && !ctx->vanilla &&
+    const bool wide_q16 = wide && !big && ctx->view.logs_nonpositive && !ctx->vanilla &&
                           (ctx->opt_kernel == FV_KERNEL_AUTO || ctx->opt_kernel == FV_KERNEL_Q16_REFINE);
     if (wide && !big && !wide_q16 && !(ctx->opt_kernel == FV_KERNEL_AUTO || ctx->opt_kernel == FV_KERNEL_F64_STREAM)) {
         ctx->detail = "full-state decode of K > ~40100: FV_KERNEL_AUTO, FV_KERNEL_U16_REFINE (K <= 65536), FV_KERNEL_Q16_REFINE (both: model entries in [0,1]) or FV_KERNEL_F64_STREAM";
         return FV_ERR_UNSUPPORTED;
     }
-    for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->M) return FV_ERR_ARG;
-    if (ctx->opt_kernel >= FV_KERNEL_F32_REFINE && !ctx->logs_nonpositive) {
-        ctx->detail = "the filter+refine kernels need every model entry in [0,1]";
+    for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
+    if (ctx->opt_kernel >= FV_KERNEL_F32_REFINE && !ctx->view.logs_nonpositive) {
+        ctx->detail = "the filter+refine kernels need every model entry in [0,1] (and every staged emission score <= 0)";
         return FV_ERR_UNSUPPORTED;
     }
     FV_HIP(hipSetDevice(ctx->device));
@@ -690,9 +705,7 @@ int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &ker
 
 void reset_stats(fv_ctx *ctx, int kernel, int generations)
 {
-    const double keep_model_ms = ctx->stats.set_model_ms;
-    ctx->stats = fv_stats{};
-    ctx->stats.set_model_ms = keep_model_ms;
+    ctx->fresh_stats();
     ctx->stats.kernel = kernel;
     ctx->stats.generations = generations;
     ctx->stats.table_bytes_per_step = (long long)((ctx->K + fvk::TILE_W - 1) / fvk::TILE_W) * ctx->nrows * fvk::TILE_W * (kernel == FV_KERNEL_F64_STREAM ? 8 : kernel == FV_KERNEL_F32_REFINE ? 4 : 2);
@@ -703,11 +716,13 @@ void reset_stats(fv_ctx *ctx, int kernel, int generations)
 
 int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, int *path_out, float *score_out)
 {
-    if (!ctx || !ob || !path_out || T < 2 || n_split < 1) return FV_ERR_ARG;
+    if (!ctx || !path_out || T < 2 || n_split < 1) return FV_ERR_ARG;
+    int rc = fvi::emission_view(ctx, ob, T);
+    if (rc) return rc;
     if (ctx->K == 0) return FV_ERR_STATE;
     auto t0 = clk::now();
     fv::Plan plan;
-    int rc = fv::build_plan(T, n_split, mode, ctx->nranks, plan);
+    rc = fv::build_plan(T, n_split, mode, ctx->nranks, plan);
     if (rc) return rc;
     // generations of passes this rank runs
     std::vector<std::vector<fv::Pass>> gens(plan.generations());
@@ -740,7 +755,7 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
 int decode_full_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split, int mode, int *path_out,
                            float *score_out, int *status_out)
 {
-    if (!ob || !offsets || !path_out || nseq < 1 || n_split < 1) return FV_ERR_ARG;
+    if (!offsets || !path_out || nseq < 1 || n_split < 1) return FV_ERR_ARG;
     if (mode != FV_MODE_REFERENCE && mode != FV_MODE_SINGLE_PASS) return FV_ERR_ARG;
     if (offsets[0] != 0) { ctx->detail = "fv_decode_full_batch: offsets[0] must be 0"; return FV_ERR_ARG; }
     std::vector<int> lengths((size_t)nseq);
@@ -751,10 +766,11 @@ int decode_full_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets,
         if (offsets[s + 1] > 0x7fffffffLL) { ctx->detail = "fv_decode_full_batch: more than 2^31 - 1 observations in all (at sequence " + std::to_string(s) + ")"; return FV_ERR_ARG; }
         lengths[(size_t)s] = (int)len;
     }
+    if (int rv = fvi::emission_view(ctx, ob, offsets[nseq])) return rv;       // (ob == NULL: sequence s on staged rows offsets[s] ..)
     if (ctx->K == 0) return FV_ERR_STATE;
     for (int s = 0; s < nseq; ++s)
         for (long long j = offsets[s]; j < offsets[s + 1]; ++j)
-            if (ob[j] < 0 || ob[j] >= ctx->M) {
+            if (ob[j] < 0 || ob[j] >= ctx->view.nsym) {
                 ctx->detail = "fv_decode_full_batch: sequence " + std::to_string(s) + " holds a symbol outside [0, M) at position " + std::to_string(j - offsets[s]);
                 return FV_ERR_ARG;
             }
@@ -798,7 +814,8 @@ int decode_full_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets,
 int test_forward_impl(fv_ctx *ctx, const int *ob, int T, const fv_test_pass *tp, int np, float *rows_out, int *bp_out,
                       unsigned long long *variants_out)
 {
-    if (!ob || !tp || np < 1 || !rows_out || !bp_out || T < 2) return FV_ERR_ARG;
+    if (!tp || np < 1 || !rows_out || !bp_out || T < 2) return FV_ERR_ARG;
+    if (int rv = fvi::emission_view(ctx, ob, T)) return rv;
     if (ctx->K == 0) return FV_ERR_STATE;
     const int K = ctx->K;
     std::vector<fv::Pass> gen((size_t)np);
@@ -893,9 +910,10 @@ extern "C" int fv_decode_checkpoint(fv_ctx *ctx, const int *ob, int T, int step,
 namespace {
 int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *path_out, float *score_out)
 {
-    if (!ctx || !ob || !path_out || T < 2) return FV_ERR_ARG;
+    if (!ctx || !path_out || T < 2) return FV_ERR_ARG;
+    if (int rv = fvi::emission_view(ctx, ob, T)) return rv;
     if (ctx->K == 0) return FV_ERR_STATE;
-    for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->M) return FV_ERR_ARG;
+    for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
     if (step <= 0) step = (int)std::floor(std::sqrt(1.0 * T));        // checkpoint Viterbi.c:179-180
     auto t0 = clk::now();
     FV_HIP(hipSetDevice(ctx->device));
@@ -909,9 +927,7 @@ int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *pat
         FV_HIP(ctx->d_ckpt.ensure((size_t)nck * nrows));
         FV_HIP(hipMemsetAsync(ctx->d_ckpt.p, 0, (size_t)nck * nrows * sizeof(float), ctx->stream));   // row pads stay zero
     }
-    const double keep_model_ms = ctx->stats.set_model_ms;
-    ctx->stats = fv_stats{};
-    ctx->stats.set_model_ms = keep_model_ms;
+    ctx->fresh_stats();
     ctx->stats.kernel = FV_KERNEL_F64_STREAM;
     ctx->stats.generations = 2;
     ctx->stats.passes = 1 + nck;
@@ -927,8 +943,8 @@ int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *pat
     auto slot_for = [&](const float *in, float *out, int j) {
         fvk::TaskSlot sl;
         sl.t1_in = in; sl.t1_out = out;
-        sl.tmp_row = ctx->LB32T.p + (size_t)ctx->h_ob[j] * K;
-        sl.tmp64_row = ctx->LB64T.p + (size_t)ctx->h_ob[j] * K;
+        sl.tmp_row = ctx->view.lb32 + (size_t)ctx->h_ob[j] * K;
+        sl.tmp64_row = ctx->view.lb64 + (size_t)ctx->h_ob[j] * K;
         sl.bp_out = ctx->d_bp.p + (size_t)j * K;
         return sl;
     };
@@ -937,7 +953,7 @@ int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *pat
         ch.n = 1;
         ch.p[0] = fvk::PassDesc{ 0, T - 1, 1, 1, 0 };
         hipLaunchKernelGGL(fvk::init_rows, dim3((K + 255) / 256, 1), dim3(256), 0, ctx->stream, ch, ctx->LA64.p, nrows,
-                           ctx->LB64T.p, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, ctx->d_ckpt.p, K);
+                           ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, ctx->d_ckpt.p, K);
         FV_HIP(hipGetLastError());
     }
     // first pass (:213-232)

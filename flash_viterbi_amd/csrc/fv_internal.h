@@ -88,6 +88,22 @@ struct fv_ctx {
     DevBuf<long long> CRptr;     // [K + 1] rows by source state: log A[Ans[L-1]][*] of init_rows
     DevBuf<int> CRcol;
     DevBuf<double> CRlog;
+    // per-time emission scores staged by fv_set_emissions: row t holds the K log scores of time t, in the
+    // two precisions of LB32T / LB64T, so that "symbol of time t = t" makes every kernel read them as it reads log B
+    DevBuf<float> E32;
+    DevBuf<double> E64;
+    DevBuf<unsigned long long> d_emflags;    // [0] FV_EMIS_BAD / FV_EMIS_POSITIVE bits, [1] lowest t * K + i of a refused value
+    long long emis_rows = 0;     // staged rows (0: none)
+    bool emis_positive = false;  // a staged score is above 0
+    std::vector<int> h_iota;     // 0, 1, 2, ...: the observation sequence of a decode given ob == NULL
+    // What the decode in flight reads its emission term from (fvi::emission_view sets it first thing in every decode):
+    // log B of the model by symbol, or the staged rows by time.
+    struct EmisView {
+        const float *lb32 = nullptr;
+        const double *lb64 = nullptr;
+        int nsym = 0;                    // rows of lb32 / lb64: the bound of an observation
+        bool logs_nonpositive = false;   // every log of the model and of these rows is <= 0 (the filter kernels' condition)
+    } view;
 
     // workspace
     DevBuf<int> d_ob, d_ans, d_bp, d_gather;
@@ -146,6 +162,14 @@ struct fv_ctx {
     int group_rank = 0;
 
     fv_stats stats{};
+    // statistics of a decode about to start: everything cleared but what the model and the staged emissions own
+    void fresh_stats()
+    {
+        const double model_ms = stats.set_model_ms, emis_ms = stats.set_emissions_ms;
+        const long long rows = stats.emission_rows;
+        stats = fv_stats{};
+        stats.set_model_ms = model_ms; stats.set_emissions_ms = emis_ms; stats.emission_rows = rows;
+    }
 };
 
 #define FV_HIP(call)                                                                          \
@@ -193,6 +217,13 @@ int finish_decode(fv_ctx *ctx, const fv::Plan &plan, int T, int *path_out, float
 int finish_decode_batch(fv_ctx *ctx, const long long *offsets, int nseq, int *path_out, float *score_out, int *status_out,
                         clk::time_point t0, size_t nprof, bool beam = false);
 int drained(fv_ctx *ctx, int rc);
+// decode prologue, before any admission check: chooses what the decode reads its emission term from.  ob != NULL: the
+// model's log B.  ob == NULL: the T rows fv_set_emissions staged (FV_ERR_ARG if there are fewer), and ob is pointed at
+// 0 .. T-1, which the rest of the decode handles as any observation sequence.
+int emission_view(fv_ctx *ctx, const int *&ob, long long T);
+// fvk::stage_emissions lives with the full-state kernels (fv_full.hip); fv_set_emissions launches it through here
+enum { FV_EMIS_BAD = 1, FV_EMIS_POSITIVE = 2 };
+int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T);
 // decode prologue: observation sequence to the device (through the pinned block), counters and answers cleared
 int begin_decode(fv_ctx *ctx, const int *ob, int T);
 // big-LDS attributes of the kernels each translation unit owns

@@ -1720,4 +1720,44 @@ __global__ __launch_bounds__(64) void backtrack(const PassChunk ch, const int *b
     }
 }
 
+// fv_set_emissions: the caller's T x K block of log scores (row pitch ld elements, float or double) into the two
+// per-time tables the step kernels read in place of log B: E32[t][i] = (float)x, E64[t][i] = (double)x.  Workgroups
+// stride over rows (y) and over states (x), lanes along the state index: coalesced loads and stores, nothing beyond
+// column K - 1 of a row is read.  flags[0] collects FV_EMIS_BAD (1: NaN, +inf, or a finite value whose float is
+// infinite) and FV_EMIS_POSITIVE (2: above 0); flags[1] the lowest t * K + i of a refused value.  One atomic pair per
+// workgroup that saw anything, through LDS.
+constexpr int EMIS_BLOCK = 256;
+template <typename TIN>
+__global__ __launch_bounds__(EMIS_BLOCK) void stage_emissions(const TIN *src, long long ld, int T, int K, float *E32,
+                                                              double *E64, unsigned long long *flags)
+{
+    __shared__ unsigned int s_flags;
+    __shared__ unsigned long long s_bad;
+    if (threadIdx.x == 0) { s_flags = 0u; s_bad = ~0ull; }
+    __syncthreads();
+    unsigned int f = 0u;
+    unsigned long long bad = ~0ull;
+    for (int t = blockIdx.y; t < T; t += gridDim.y) {
+        const TIN *row = src + (size_t)t * (size_t)ld;
+        for (int i = blockIdx.x * EMIS_BLOCK + threadIdx.x; i < K; i += gridDim.x * EMIS_BLOCK) {
+            const double x = (double)row[i];
+            const float xf = (float)x;
+            const size_t e = (size_t)t * K + i;
+            // accepted: -inf and every value whose float is finite (NaN fails both comparisons)
+            const bool ok = xf < HUGE_VALF && (xf > -HUGE_VALF || x == -HUGE_VAL);
+            if (!ok) { f |= 1u; bad = min(bad, (unsigned long long)e); }
+            if (x > 0.0) f |= 2u;
+            E32[e] = xf;
+            E64[e] = x;
+        }
+    }
+    if (f) atomicOr(&s_flags, f);
+    if (bad != ~0ull) atomicMin(&s_bad, bad);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_flags) atomicOr(&flags[0], (unsigned long long)s_flags);
+        if (s_bad != ~0ull) atomicMin(&flags[1], s_bad);
+    }
+}
+
 }  // namespace fvk

@@ -24,6 +24,7 @@ DEBUG_CSR_ROWS_IN_MEMORY = 1 << 31     # sparse-set models: the step kernel read
 WARN_BEAM_MISS = 1
 ERR_ARG, ERR_NOMEM, ERR_NO_PRED, ERR_DEVICE, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 UNIQUE_ID_BYTES = 128
+EMIS_LOG_F32, EMIS_LOG_F64 = 0, 1     # dtype of fv_set_emissions
 
 
 class Stats(ctypes.Structure):
@@ -42,7 +43,8 @@ class Stats(ctypes.Structure):
                 ("ranks", ctypes.c_int), ("refine_saturated", ctypes.c_longlong),
                 ("beam_spec_steps", ctypes.c_longlong), ("beam_reach_events", ctypes.c_longlong),
                 ("beam_list_short", ctypes.c_longlong), ("beam_list_long", ctypes.c_longlong), ("beam_list_entries", ctypes.c_longlong),
-                ("beam_chain_cuts", ctypes.c_longlong)]
+                ("beam_chain_cuts", ctypes.c_longlong),
+                ("set_emissions_ms", ctypes.c_double), ("emission_rows", ctypes.c_longlong)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -57,9 +59,10 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_last_stats", "fv_strerror", "fv_last_error_detail", "fv_reference_memory_bytes",
            "fv_comm_unique_id", "fv_comm_init", "fv_plan_passes", "fv_merge_paths", "fv_set_partition",
            "fv_create_multi", "fv_device_count", "fv_decode_full_batch", "fv_plan_passes_batch", "fv_decode_beam_batch",
-           "fv_set_model_sparse"]
+           "fv_set_model_sparse", "fv_set_emissions", "fv_clear_emissions"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
-TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select"]
+TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select", "fv_test_device_alloc", "fv_test_device_free",
+                "fv_test_stage_emissions_ms"]
 TIE_TAG = 1 << 30
 # FV_TS_*: select-kernel instantiations reported by test_beam_select
 TS_BITS = {"topb_select<4,listed>": 1 << 0, "topb_select<4,derived>": 1 << 1, "topb_select<16,listed>": 1 << 2,
@@ -109,6 +112,11 @@ def load_library():
     L.fv_set_model.argtypes = [vp, vp, vp, vp, ci, ci]
     L.fv_set_model_sparse.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci]
     L.fv_set_option.argtypes = [vp, ci, cll]
+    L.fv_set_emissions.argtypes = [vp, vp, ci, ci, cll]
+    L.fv_clear_emissions.argtypes = [vp]
+    L.fv_test_device_alloc.argtypes = [vp, ctypes.c_size_t, vp, ctypes.POINTER(vp)]
+    L.fv_test_device_free.argtypes = [vp, vp]
+    L.fv_test_stage_emissions_ms.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
     L.fv_decode_full.argtypes = [vp, vp, ci, ci, ci, vp, vp]
     L.fv_decode_beam.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
     L.fv_decode_full_batch.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
@@ -193,6 +201,39 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _ob_arg(ob, T):
+    """(keep-alive array, pointer, length) of a decode's observations: an int sequence, or None with T = the number of staged emission
+    rows to decode (fv_set_emissions)."""
+    if ob is None:
+        if T is None:
+            raise ValueError("ob=None decodes the staged emission scores: give T, the number of times")
+        return None, None, int(T)
+    ob = np.ascontiguousarray(ob, dtype=np.int32)
+    if T is not None and int(T) != ob.size:
+        raise ValueError("T differs from the length of ob")
+    return ob, _p(ob), ob.size
+
+
+def _batch_arg(obs, lengths):
+    """(keep-alive array, pointer, offsets) of a batch decode's observations: a list of int sequences, or None with
+    lengths = the number of staged emission rows of every sequence (laid end to end in the staged block)."""
+    if obs is None:
+        if lengths is None:
+            raise ValueError("obs=None decodes the staged emission scores: give lengths")
+        sizes, ob, ptr = [int(n) for n in lengths], None, None
+    else:
+        if lengths is not None:
+            raise ValueError("lengths goes with obs=None")
+        seqs = [np.ascontiguousarray(o, dtype=np.int32).reshape(-1) for o in obs]
+        sizes = [o.size for o in seqs]
+        ob = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.int32)
+        ptr = _p(ob)
+    offsets = np.zeros(len(sizes) + 1, dtype=np.int64)
+    if sizes:
+        offsets[1:] = np.cumsum(sizes)
+    return ob, ptr, offsets
+
+
 def dense_to_csr(A):
     """(indptr int64[K + 1], indices int32[nnz], data float32[nnz]) of a dense K x K matrix, by row with ascending
     columns: what set_model_sparse takes.  Entries equal to 0 are left out (NaN is kept, so that the library sees it)."""
@@ -263,81 +304,123 @@ class FlashViterbi:
         self._check(self._L.fv_set_model_sparse(self._h, _p(indptr), _p(indices), _p(data), _p(B), _p(Pi), K, M))
         self.K, self.M = K, M
 
-    def decode_full(self, ob, n_split=1, mode=MODE_REFERENCE):
-        ob = np.ascontiguousarray(ob, dtype=np.int32)
-        path = np.empty(ob.size, dtype=np.int32)
+    def set_emissions(self, scores, ld=None):
+        """fv_set_emissions: per-time log emission scores, row t = the K scores of time t.  `scores` is a 2-D float32
+        or float64 numpy array [T, >= K] (ld: its row pitch in elements, default its width; columns beyond K are not
+        interpreted), or a tuple (device_pointer:int, dtype, T, ld) for a block already on this context's GPU (dtype:
+        np.float32 / np.float64 or EMIS_LOG_F32 / EMIS_LOG_F64; its producer must have finished).  Afterwards every
+        decode_* and test_forward takes ob=None.  There is no torch path: pass tensor.data_ptr() in the tuple form."""
+        if isinstance(scores, tuple):
+            ptr, dtype, T, pitch = scores
+            if ld is not None:
+                pitch = ld
+            if isinstance(dtype, (type, np.dtype, str)):
+                dtype = {np.dtype(np.float32): EMIS_LOG_F32, np.dtype(np.float64): EMIS_LOG_F64}.get(np.dtype(dtype), -1)
+            self._check(self._L.fv_set_emissions(self._h, ctypes.c_void_p(int(ptr)), int(dtype), int(T), int(pitch)))
+            return
+        a = np.asarray(scores)
+        if a.ndim != 2 or a.dtype not in (np.float32, np.float64):
+            raise TypeError("set_emissions: a 2-D float32 or float64 array, or (device_pointer, dtype, T, ld)")
+        a = np.ascontiguousarray(a)
+        pitch = a.shape[1] if ld is None else int(ld)
+        if pitch > a.shape[1] and a.shape[0] > 1:
+            raise ValueError("set_emissions: ld exceeds the row length of the array")
+        dtype = EMIS_LOG_F32 if a.dtype == np.float32 else EMIS_LOG_F64
+        self._check(self._L.fv_set_emissions(self._h, _p(a), dtype, a.shape[0], pitch))
+
+    def clear_emissions(self):
+        self._check(self._L.fv_clear_emissions(self._h))
+
+    def decode_full(self, ob, n_split=1, mode=MODE_REFERENCE, T=None):
+        """ob=None with T=...: decode the first T rows staged by set_emissions (so for every decode_* below)."""
+        ob, ptr, T = _ob_arg(ob, T)
+        path = np.empty(T, dtype=np.int32)
         score = ctypes.c_float(0)
-        rc = self._check(self._L.fv_decode_full(self._h, _p(ob), ob.size, n_split, mode, _p(path), ctypes.byref(score)))
+        rc = self._check(self._L.fv_decode_full(self._h, ptr, T, n_split, mode, _p(path), ctypes.byref(score)))
         return path, np.float32(score.value), rc
 
-    def decode_full_batch(self, obs, n_split=1, mode=MODE_REFERENCE):
+    def decode_full_batch(self, obs, n_split=1, mode=MODE_REFERENCE, lengths=None):
         """fv_decode_full_batch: obs is a list of int sequences (lengths may differ) for the model of this context.
         Returns (paths: list of int32 arrays, scores: float32 array, statuses: int32 array), per sequence what
         decode_full returns for it alone.  A sequence whose path has an entry without a finite predecessor reports
         ERR_NO_PRED in `statuses` (its path holds the -1 entries) and does not raise: the other sequences' results
-        stand.  Every other negative return raises FlashVitError."""
-        seqs = [np.ascontiguousarray(o, dtype=np.int32).reshape(-1) for o in obs]
-        offsets = np.zeros(len(seqs) + 1, dtype=np.int64)
-        if seqs:
-            offsets[1:] = np.cumsum([o.size for o in seqs])
-        ob = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.int32)
-        path = np.empty(max(ob.size, 1), dtype=np.int32)
-        scores = np.zeros(len(seqs), dtype=np.float32)
-        statuses = np.zeros(len(seqs), dtype=np.int32)
-        rc = self._L.fv_decode_full_batch(self._h, _p(ob), _p(offsets), len(seqs), n_split, mode, _p(path), _p(scores), _p(statuses))
+        stand.  Every other negative return raises FlashVitError.  obs=None with lengths=[...]: sequence s is the next
+        lengths[s] rows of the block staged by set_emissions."""
+        ob, ptr, offsets = _batch_arg(obs, lengths)
+        nseq = offsets.size - 1
+        path = np.empty(max(int(offsets[-1]), 1), dtype=np.int32)
+        scores = np.zeros(nseq, dtype=np.float32)
+        statuses = np.zeros(nseq, dtype=np.int32)
+        rc = self._L.fv_decode_full_batch(self._h, ptr, _p(offsets), nseq, n_split, mode, _p(path), _p(scores), _p(statuses))
         if rc != ERR_NO_PRED:
             self._check(rc)
-        return [path[offsets[s]:offsets[s + 1]].copy() for s in range(len(seqs))], scores, statuses
+        return [path[offsets[s]:offsets[s + 1]].copy() for s in range(nseq)], scores, statuses
 
-    def decode_beam(self, ob, n_split, beam, mode=MODE_REFERENCE):
-        ob = np.ascontiguousarray(ob, dtype=np.int32)
-        path = np.empty(ob.size, dtype=np.int32)
+    def decode_beam(self, ob, n_split, beam, mode=MODE_REFERENCE, T=None):
+        ob, ptr, T = _ob_arg(ob, T)
+        path = np.empty(T, dtype=np.int32)
         score = ctypes.c_float(0)
-        rc = self._check(self._L.fv_decode_beam(self._h, _p(ob), ob.size, n_split, beam, mode, _p(path), ctypes.byref(score)))
+        rc = self._check(self._L.fv_decode_beam(self._h, ptr, T, n_split, beam, mode, _p(path), ctypes.byref(score)))
         return path, np.float32(score.value), rc
 
-    def decode_beam_batch(self, obs, n_split, beam, mode=MODE_REFERENCE):
+    def decode_beam_batch(self, obs, n_split, beam, mode=MODE_REFERENCE, lengths=None):
         """fv_decode_beam_batch: obs is a list of int sequences (lengths may differ) for the model of this context.
         Returns (paths: list of int32 arrays, scores: float32 array, statuses: int32 array), per sequence what
         decode_beam returns for it alone: a sequence with a beam miss reports WARN_BEAM_MISS in `statuses` and its path
-        holds the -1 entries.  Negative returns raise FlashVitError."""
-        seqs = [np.ascontiguousarray(o, dtype=np.int32).reshape(-1) for o in obs]
-        offsets = np.zeros(len(seqs) + 1, dtype=np.int64)
-        if seqs:
-            offsets[1:] = np.cumsum([o.size for o in seqs])
-        ob = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.int32)
-        path = np.empty(max(ob.size, 1), dtype=np.int32)
-        scores = np.zeros(len(seqs), dtype=np.float32)
-        statuses = np.zeros(len(seqs), dtype=np.int32)
-        self._check(self._L.fv_decode_beam_batch(self._h, _p(ob), _p(offsets), len(seqs), n_split, beam, mode, _p(path),
+        holds the -1 entries.  Negative returns raise FlashVitError.  obs=None with lengths=[...]: as decode_full_batch."""
+        ob, ptr, offsets = _batch_arg(obs, lengths)
+        nseq = offsets.size - 1
+        path = np.empty(max(int(offsets[-1]), 1), dtype=np.int32)
+        scores = np.zeros(nseq, dtype=np.float32)
+        statuses = np.zeros(nseq, dtype=np.int32)
+        self._check(self._L.fv_decode_beam_batch(self._h, ptr, _p(offsets), nseq, n_split, beam, mode, _p(path),
                                                  _p(scores), _p(statuses)))
-        return [path[offsets[s]:offsets[s + 1]].copy() for s in range(len(seqs))], scores, statuses
+        return [path[offsets[s]:offsets[s + 1]].copy() for s in range(nseq)], scores, statuses
 
-    def decode_vanilla(self, ob):
-        ob = np.ascontiguousarray(ob, dtype=np.int32)
-        path = np.empty(ob.size, dtype=np.int32)
+    def decode_vanilla(self, ob, T=None):
+        ob, ptr, T = _ob_arg(ob, T)
+        path = np.empty(T, dtype=np.int32)
         score = ctypes.c_float(0)
-        rc = self._check(self._L.fv_decode_vanilla(self._h, _p(ob), ob.size, _p(path), ctypes.byref(score)))
+        rc = self._check(self._L.fv_decode_vanilla(self._h, ptr, T, _p(path), ctypes.byref(score)))
         return path, np.float32(score.value), rc
 
-    def decode_checkpoint(self, ob, step=0):
-        ob = np.ascontiguousarray(ob, dtype=np.int32)
-        path = np.empty(ob.size, dtype=np.int32)
+    def decode_checkpoint(self, ob, step=0, T=None):
+        ob, ptr, T = _ob_arg(ob, T)
+        path = np.empty(T, dtype=np.int32)
         score = ctypes.c_float(0)
-        rc = self._check(self._L.fv_decode_checkpoint(self._h, _p(ob), ob.size, step, _p(path), ctypes.byref(score)))
+        rc = self._check(self._L.fv_decode_checkpoint(self._h, ptr, T, step, _p(path), ctypes.byref(score)))
         return path, np.float32(score.value), rc
 
-    def test_forward(self, ob, passes, bp_fill=-2):
+    def test_device_alloc(self, host_array):
+        """fv_test_device_alloc: a device copy of a numpy array on this context's GPU; returns the pointer as an int
+        (release it with test_device_free)."""
+        a = np.ascontiguousarray(host_array)
+        out = ctypes.c_void_p()
+        self._check(self._L.fv_test_device_alloc(self._h, a.nbytes, _p(a), ctypes.byref(out)))
+        return int(out.value)
+
+    def test_device_free(self, ptr):
+        self._check(self._L.fv_test_device_free(self._h, ctypes.c_void_p(int(ptr))))
+
+    def test_stage_emissions_ms(self, ptr, dtype, T, ld, reps):
+        """fv_test_stage_emissions_ms: mean milliseconds per launch of the staging kernel over the device block at ptr
+        (device events around reps launches back to back).  Nothing is staged afterwards."""
+        ms = ctypes.c_float(0)
+        code = EMIS_LOG_F64 if np.dtype(dtype) == np.float64 else EMIS_LOG_F32
+        self._check(self._L.fv_test_stage_emissions_ms(self._h, ctypes.c_void_p(int(ptr)), code, int(T), int(ld), int(reps), ctypes.byref(ms)))
+        return float(ms.value)
+
+    def test_forward(self, ob, passes, bp_fill=-2, T=None):
         """fv_test_forward: passes = [(L, R, init_state)], run as one generation of full-state passes.  Returns
         (rows[npasses, K] float32, bp[T, K] int32, variants): the final score row of each pass, the back-pointer
         rows L+1 .. R of each pass at their absolute times (every other row keeps bp_fill) and the FV_TV_* bits of
-        the step-kernel instantiations that ran."""
-        ob = np.ascontiguousarray(ob, dtype=np.int32)
+        the step-kernel instantiations that ran.  ob=None with T=...: on the rows staged by set_emissions."""
+        ob, ptr, T = _ob_arg(ob, T)
         pa = (ForwardPass * len(passes))(*[ForwardPass(int(L), int(R), int(s)) for L, R, s in passes])
         rows = np.empty((len(passes), self.K), dtype=np.float32)
-        bp = np.full((ob.size, self.K), bp_fill, dtype=np.int32)
+        bp = np.full((T, self.K), bp_fill, dtype=np.int32)
         variants = ctypes.c_ulonglong(0)
-        self._check(self._L.fv_test_forward(self._h, _p(ob), ob.size, pa, len(passes), _p(rows), _p(bp), ctypes.byref(variants)))
+        self._check(self._L.fv_test_forward(self._h, ptr, T, pa, len(passes), _p(rows), _p(bp), ctypes.byref(variants)))
         return rows, bp, int(variants.value)
 
     def test_beam_step(self, beam, sets, syms, speculative=False, theta=0.0, next_bound=float("inf"), cand_cap=0):

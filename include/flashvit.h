@@ -149,6 +149,8 @@ typedef struct {
     long long beam_list_entries;/* FLASH-BS: total length of the candidate lists the selects ran on (beam_cand_selects of them) */
     long long beam_chain_cuts;  /* FLASH-BS: runs of undecided steps that were decided only back to a step whose replay provably does not
                                    depend on the undecided columns (instead of back to the last step with exact scores) */
+    double set_emissions_ms;    /* host wall time of the last fv_set_emissions (copy, staging kernel, its one sync), 0 after a refused one; kept across decodes */
+    long long emission_rows;    /* rows staged by fv_set_emissions (0: none); kept across decodes */
 } fv_stats;
 
 /* Device + stream + workspace owner.  Replaces `vit = create_vit()`'s allocation role
@@ -196,6 +198,34 @@ int fv_set_model(fv_ctx *ctx, const float *A, const float *B, const float *Pi, i
  *     any device work: their kernels gather rows of the dense table. */
 int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const int *col, const float *val,
                         const float *B, const float *Pi, int K, int M);
+
+/* Per-time emission scores in place of observation symbols: for continuous-observation HMMs, neural acoustic / alignment
+ * models and profile HMMs, which hold one log score per (time, state) and have no symbol alphabet.  `scores` is T rows of
+ * K log scores (K is the model's), row t, state i at scores[t * ld + i], ld >= K in elements; what lies beyond K in a row
+ * is never interpreted (a host block is copied as one piece up to the last row's K-th element, pads included).  dtype is
+ * FV_EMIS_LOG_F32 (float) or FV_EMIS_LOG_F64 (double).  `scores` may be a host pointer or a device pointer
+ * (hipPointerGetAttributes decides); work producing a device block must be complete before the call; the call returns
+ * after staging, so the caller may free `scores` at once.
+ *   The library keeps two device tables, E32[t][i] = (float)x in the part of (float)log(B[i][o]) (FLASH:167) and
+ * E64[t][i] = (double)x in the part of log((double)B[i][o]) (init rows, vanilla / checkpoint arithmetic): for
+ * FV_EMIS_LOG_F64 input of log((double)b) values exactly the tables fv_set_model builds from b.  FV_EMIS_LOG_F32 is
+ * the same as passing (double)x.
+ *   Values: finite or -inf.  A NaN, a +inf or a finite double whose float conversion is infinite answers FV_ERR_ARG, with
+ * the lowest offending (t, state) in fv_last_error_detail.  A score above 0 (a density above 1) is accepted and handled
+ * as a B entry above 1: decodes on these emissions take FV_KERNEL_F64_STREAM under AUTO, answer FV_ERR_UNSUPPORTED to a
+ * forced filter kernel and on a model set by fv_set_model_sparse, and the beam path takes its float64 step kernel.
+ *   Returns FV_ERR_STATE without a model, FV_ERR_ARG for T < 1, ld < K, a bad dtype or a NULL pointer, FV_ERR_NOMEM (the
+ * byte count in the detail, before anything is allocated) when 12 * T * K bytes plus the raw copy exceed the free device
+ * memory.  A failed call leaves the context with no staged emissions.
+ *   Use: every decode call — and fv_test_forward — given ob == NULL reads row t for time t.  The single decodes need
+ * T <= staged rows; the batch decodes put sequence s on rows offsets[s] .. offsets[s+1]) and need offsets[nseq] <= staged
+ * rows.  The symbol-range check does not apply; every other admission rule does.  ob == NULL with nothing staged is
+ * FV_ERR_ARG.  A call with ob != NULL ignores the staged rows and decodes symbols through the model's B.
+ * fv_set_model and fv_set_model_sparse drop the staged emissions; fv_clear_emissions drops them and frees the tables.
+ * A fv_create_multi context stages on every member; with fv_set_partition / fv_comm_init every rank stages its own copy. */
+enum { FV_EMIS_LOG_F32 = 0, FV_EMIS_LOG_F64 = 1 };
+int fv_set_emissions(fv_ctx *ctx, const void *scores, int dtype, int T, long long ld);
+int fv_clear_emissions(fv_ctx *ctx);
 
 int fv_set_option(fv_ctx *ctx, int key, long long value);
 

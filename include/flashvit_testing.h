@@ -35,6 +35,20 @@ typedef struct { int L, R, init_state; } fv_test_pass;
  * afterwards describes this call (kernel, passes, step launches; no timings), not a decode. */
 int fv_test_forward(fv_ctx *ctx, const int *ob, int T, const fv_test_pass *passes, int npasses,
                     float *rows_out, int *bp_out, unsigned long long *variants_out);
+/* (ob == NULL: the passes read the rows staged by fv_set_emissions, row t for time t, as the decodes do; T <= staged rows.) */
+
+/* Device memory for tests of the calls that take a device pointer (fv_set_emissions): the test process has no HIP
+ * runtime of its own to allocate with.  `bytes` of device memory on the context's GPU in *out, filled from host_src
+ * unless that is NULL; the copy is complete on return.  The free hook waits for nothing but the device. */
+int fv_test_device_alloc(fv_ctx *ctx, size_t bytes, const void *host_src, void **out);
+int fv_test_device_free(fv_ctx *ctx, void *p);
+
+/* The staging kernel of fv_set_emissions alone, timed on the device: one warm launch, then `reps` launches back to back
+ * of stage_emissions<TIN> between two events on the context's stream, over the T x K block at dev_scores (a device
+ * pointer on the context's GPU, row pitch ld, dtype as for fv_set_emissions); *ms_out is the mean per launch, dispatch
+ * gaps included.  Nothing is staged afterwards (the tables are overwritten and the values are not judged).  FV_ERR_ARG: no
+ * model, a host pointer, T < 1, ld < K, reps < 1, a bad dtype, a multi-device context.  For tools/bench_emissions.py. */
+int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, int dtype, int T, long long ld, int reps, float *ms_out);
 
 /* One slot set of a beam step: n entries {val[e], state[e]} (states in [0, K)), beam <= n <= beam + 32. */
 typedef struct { const float *val; const int *state; int n; } fv_test_beam_set;
