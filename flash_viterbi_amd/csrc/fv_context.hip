@@ -948,7 +948,8 @@ extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
     }
     switch (key) {
     case FV_OPT_KERNEL:
-        if (value < FV_KERNEL_AUTO || value > FV_KERNEL_U16_REFINE) return FV_ERR_ARG;      // (FV_KERNEL_SPARSE_CSR is reported, never chosen)
+        // (FV_KERNEL_SPARSE_CSR is reported, never chosen)
+        if ((value < FV_KERNEL_AUTO || value > FV_KERNEL_U16_REFINE) && value != FV_KERNEL_CSR_F64) return FV_ERR_ARG;
         ctx->opt_kernel = (int)value; return FV_OK;
     case FV_OPT_MAX_BATCH:
         if (value < 1 || value > fvk::MAX_BATCH) return FV_ERR_ARG;

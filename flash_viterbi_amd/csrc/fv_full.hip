@@ -52,11 +52,14 @@ template <int NB, bool DB, int NWV> constexpr unsigned long long u16_variant()
 }
 template <int NB> constexpr unsigned long long sparse_variant() { return 1ull << (42 + nb_slot(NB)); }
 template <int NB, bool MEM> constexpr unsigned long long csr_variant() { return 1ull << (FV_TV_CSR_SHIFT + (MEM ? 4 : 0) + nb_slot(NB)); }
+// (the float64 walk: one bit per NB and one, set in addition, for the launches that read their score rows from memory)
+template <int NB, bool MEM> constexpr unsigned long long csr_f64_variant() { return (1ull << (FV_TV_CSR64_SHIFT + nb_slot(NB))) | (MEM ? 1ull << (FV_TV_CSR64_SHIFT + 4) : 0ull); }
 static_assert(step_variant<double, 8, true>() == FV_TV_F64_NB8 && step_variant<float, 2, false>() == FV_TV_F32_UP_NB2 &&
               step_variant<fvk::half_t, 1, true>() == FV_TV_F16_NB1 && step_variant<fvk::q16_t, 2, false>() == FV_TV_Q16_UP_NB2 &&
               slab_variant<fvk::q16_t>() == FV_TV_SLAB_Q16 && u16_variant<1, false, 16>() == FV_TV_U16_W16_UP_NB1 &&
               u16_variant<8, true, 8>() == FV_TV_U16_W8_NB8 && sparse_variant<8>() == FV_TV_SPARSE_NB8 &&
-              csr_variant<1, false>() == FV_TV_CSR_LDS_NB1 && csr_variant<8, true>() == FV_TV_CSR_MEM_NB8,
+              csr_variant<1, false>() == FV_TV_CSR_LDS_NB1 && csr_variant<8, true>() == FV_TV_CSR_MEM_NB8 &&
+              csr_f64_variant<1, false>() == FV_TV_CSR64_NB1 && csr_f64_variant<8, true>() == (FV_TV_CSR64_NB8 | FV_TV_CSR64_MEM),
               "FV_TV_* bits of include/flashvit_testing.h");
 
 template <typename TA, int NB, int U, bool DB>
@@ -216,6 +219,39 @@ int launch_csr(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb)
     return launch_csr_nb<8>(ctx, slots, nb);
 }
 
+// trellis_step_csr_f64 (FV_KERNEL_CSR_F64): the same two forms of the score rows
+template <int NB>
+int launch_csr_f64_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb)
+{
+    fvk::CsrF64Args<NB> a;
+    a.ck = ctx->CSk.p; a.c64 = ctx->CS64.p; a.tile_off = ctx->CSoff.p; a.tile_nwb = ctx->CSnwb.p;
+    a.K = ctx->K; a.nrows = ctx->nrows;
+    a.ntiles = (ctx->K + fvk::TILE_W - 1) / fvk::TILE_W;
+    a.tiles_per_xcd = (a.ntiles + 7) / 8;
+    a.nb = nb; a.vanilla = ctx->vanilla;
+    for (int t = 0; t < NB; ++t) a.t[t] = slots[t < nb ? t : 0];
+    hipStream_t st = ctx->lstream ? ctx->lstream : ctx->stream;
+    if (ctx->opt_csr_mem || fvk::csr_f64_lds_bytes<NB>(ctx->nrows, false) > 160 * 1024) {
+        if (ctx->test_record) ctx->test_variants |= csr_f64_variant<NB, true>();
+        hipLaunchKernelGGL((fvk::trellis_step_csr_f64<NB, true>), dim3(a.tiles_per_xcd * 8), dim3(fvk::SP_BLOCK),
+                           fvk::csr_f64_lds_bytes<NB>(ctx->nrows, true), st, a);
+    } else {
+        if (ctx->test_record) ctx->test_variants |= csr_f64_variant<NB, false>();
+        hipLaunchKernelGGL((fvk::trellis_step_csr_f64<NB, false>), dim3(a.tiles_per_xcd * 8), dim3(fvk::SP_BLOCK),
+                           fvk::csr_f64_lds_bytes<NB>(ctx->nrows, false), st, a);
+    }
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_csr_f64(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb)
+{
+    if (nb <= 1) return launch_csr_f64_nb<1>(ctx, slots, nb);
+    if (nb <= 2) return launch_csr_f64_nb<2>(ctx, slots, nb);
+    if (nb <= 4) return launch_csr_f64_nb<4>(ctx, slots, nb);
+    return launch_csr_f64_nb<8>(ctx, slots, nb);
+}
+
 template <int NB, int U, bool DB, int NWV>
 int launch_u16_variant(fv_ctx *ctx, const fvk::StepArgs<NB> &a)
 {
@@ -273,6 +309,7 @@ int launch_step_kernel(fv_ctx *ctx, int kernel, const fvk::TaskSlot *slots, int 
         return launch_step<fvk::q16_t>(ctx, slots, nb, reverse);
     case FV_KERNEL_SPARSE_Q16: return launch_sparse(ctx, slots, nb);
     case FV_KERNEL_SPARSE_CSR: return launch_csr(ctx, slots, nb);
+    case FV_KERNEL_CSR_F64: return launch_csr_f64(ctx, slots, nb);
     case FV_KERNEL_F64_STREAM: return launch_step<double>(ctx, slots, nb, reverse);
     case FV_KERNEL_F32_REFINE: return launch_step<float>(ctx, slots, nb, reverse);
     case FV_KERNEL_Q16_REFINE: return launch_step<fvk::q16_t>(ctx, slots, nb, reverse);
@@ -367,7 +404,7 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
     // (the float64 kernel beyond one LDS row sweeps slabs of source rows: four tasks per launch keep a slab at ~10000 rows)
     const bool slabbed = (kernel == FV_KERNEL_F64_STREAM || kernel == FV_KERNEL_Q16_REFINE) && !ctx->full_ok;
     int cap = std::max(1, std::min(ctx->opt_max_batch, slabbed ? 4 : max_batch_for(ctx->nrows, !ctx->full_ok)));
-    if (kernel == FV_KERNEL_SPARSE_CSR) cap = ctx->opt_max_batch;     // (rows that do not fit LDS are read from memory)
+    if (kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64) cap = ctx->opt_max_batch;     // (rows that do not fit LDS are read from memory)
     const bool whole_gen = passes[0].whole;       // generation 0: bracket its step launches for the stats
     // The batches of a lock-step are independent, and a step launch is latency-bound at both ends (staging the score
     // rows; reductions and refine): the right-hand generations of the packed 16-bit kernel therefore run as batches of
@@ -382,7 +419,7 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
     // of three launches on three streams — no fork / join, a third of the host launches — cfg2 right-hand 1.64 -> 1.79 ms,
     // cfg3 43.8 -> 51.1 ms: workgroups of one launch run in phase, all in their prologue or all in their sweep; what the
     // streams provide is the stagger.)
-    const bool two = ((kernel == FV_KERNEL_U16_REFINE && ctx->u16_ok) || ((kernel == FV_KERNEL_SPARSE_Q16 || kernel == FV_KERNEL_SPARSE_CSR) && maxlen >= 64)) &&
+    const bool two = ((kernel == FV_KERNEL_U16_REFINE && ctx->u16_ok) || ((kernel == FV_KERNEL_SPARSE_Q16 || kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64) && maxlen >= 64)) &&
                      !(ctx->opt_debug & 262144) && (!whole_gen || batch == BATCH_FORK) && np > FORK_CAP &&
                      !ctx->opt_profile && !(ctx->opt_debug & 64);
     const int nbatches = (np + FORK_CAP - 1) / FORK_CAP;
@@ -564,6 +601,9 @@ int full_setup(fv_ctx *ctx)
     if ((rc = set_big_lds(ctx, &fvk::trellis_step_csr<1, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_csr<2, false>)) ||
         (rc = set_big_lds(ctx, &fvk::trellis_step_csr<4, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_csr<8, false>)))
         return rc;
+    if ((rc = set_big_lds(ctx, &fvk::trellis_step_csr_f64<1, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_csr_f64<2, false>)) ||
+        (rc = set_big_lds(ctx, &fvk::trellis_step_csr_f64<4, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_csr_f64<8, false>)))
+        return rc;
     if ((rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, 8, false, 16>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, U_DB16, true, 16>)) ||
         (rc = set_big_lds(ctx, &fvk::trellis_step_u16<2, 8, false, 16>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<2, U_DB16, true, 16>)) ||
         (rc = set_big_lds(ctx, &fvk::trellis_step_u16<4, 8, false, 16>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<4, U_DB16, true, 16>)) ||
@@ -648,19 +688,26 @@ int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &ker
     //   * the float64 kernel in slabs of source rows (launch_step_nb): any K the float64 table fits the device for, any
     //     model; 8 B per cell instead of 2.
     if (ctx->csr) {
-        // a model set by fv_set_model_sparse has no dense table: the walk over its stored entries is the one kernel
-        if (ctx->opt_kernel != FV_KERNEL_AUTO && ctx->opt_kernel != FV_KERNEL_SPARSE_Q16) {
-            ctx->detail = "a model set by fv_set_model_sparse has no dense table: FV_KERNEL_AUTO or FV_KERNEL_SPARSE_Q16";
+        // a model set by fv_set_model_sparse has no dense table: the walks over its stored entries are its kernels — the
+        // filter walk, or under FV_KERNEL_CSR_F64 the float64 walk, which has no condition on the values
+        const bool f64 = ctx->opt_kernel == FV_KERNEL_CSR_F64;
+        if (!f64 && ctx->opt_kernel != FV_KERNEL_AUTO && ctx->opt_kernel != FV_KERNEL_SPARSE_Q16) {
+            ctx->detail = "a model set by fv_set_model_sparse has no dense table: FV_KERNEL_AUTO or FV_KERNEL_SPARSE_Q16 (the filter walk), or FV_KERNEL_CSR_F64";
             return FV_ERR_UNSUPPORTED;
         }
-        if (!ctx->view.logs_nonpositive) {
-            ctx->detail = "fv_set_model_sparse: the walk over the stored entries is a filter kernel and needs every model entry in [0,1]";
+        if (!f64 && !ctx->view.logs_nonpositive) {
+            ctx->detail = "fv_set_model_sparse: the walk over the stored entries is a filter kernel and needs every model entry in [0,1] "
+                          "(and every staged emission score <= 0); FV_KERNEL_CSR_F64 decodes such input";
             return FV_ERR_UNSUPPORTED;
         }
         for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
         FV_HIP(hipSetDevice(ctx->device));
-        kernel = FV_KERNEL_SPARSE_CSR;
+        kernel = f64 ? FV_KERNEL_CSR_F64 : FV_KERNEL_SPARSE_CSR;
         return fvi::ensure_workspace(ctx, T, rows_needed, nscores);
+    }
+    if (ctx->opt_kernel == FV_KERNEL_CSR_F64) {
+        ctx->detail = "FV_KERNEL_CSR_F64 walks the stored entries of a model set by fv_set_model_sparse: this model was set by fv_set_model";
+        return FV_ERR_UNSUPPORTED;
     }
     const bool wide = !ctx->full_ok;
     const bool big = wide && ctx->u16_ok && ctx->view.logs_nonpositive && !ctx->vanilla &&
@@ -711,6 +758,7 @@ void reset_stats(fv_ctx *ctx, int kernel, int generations)
     ctx->stats.table_bytes_per_step = (long long)((ctx->K + fvk::TILE_W - 1) / fvk::TILE_W) * ctx->nrows * fvk::TILE_W * (kernel == FV_KERNEL_F64_STREAM ? 8 : kernel == FV_KERNEL_F32_REFINE ? 4 : 2);
     if (kernel == FV_KERNEL_SPARSE_Q16) ctx->stats.table_bytes_per_step = (long long)ctx->SPdata.bytes();
     if (kernel == FV_KERNEL_SPARSE_CSR) ctx->stats.table_bytes_per_step = (long long)(ctx->CSk.bytes() + ctx->CSq.bytes());
+    if (kernel == FV_KERNEL_CSR_F64) ctx->stats.table_bytes_per_step = (long long)(ctx->CSk.bytes() + ctx->CS64.bytes());
     ctx->stats.density = ctx->density;
 }
 
@@ -884,9 +932,10 @@ extern "C" int fv_test_forward(fv_ctx *ctx, const int *ob, int T, const fv_test_
 extern "C" int fv_decode_vanilla(fv_ctx *ctx, const int *ob, int T, int *path_out, float *score_out)
 {
     if (!ctx) return FV_ERR_ARG;
-    if (ctx->csr) { ctx->detail = "fv_decode_vanilla: not available on a model set by fv_set_model_sparse (its kernel reads the dense table)"; return FV_ERR_UNSUPPORTED; }
+    // (a model set by fv_set_model_sparse: the float64 walk carries the baseline's rounding order, the filter walk cannot)
+    if (ctx->csr && ctx->opt_kernel != FV_KERNEL_CSR_F64) { ctx->detail = "fv_decode_vanilla: not available on a model set by fv_set_model_sparse (its kernel reads the dense table) unless FV_KERNEL_CSR_F64 is selected"; return FV_ERR_UNSUPPORTED; }
     const int keep_kernel = ctx->opt_kernel;
-    ctx->opt_kernel = FV_KERNEL_F64_STREAM;      // the baseline's expression has no filter form
+    if (!ctx->csr) ctx->opt_kernel = FV_KERNEL_F64_STREAM;      // the baseline's expression has no filter form
     ctx->vanilla = 1;
     int rc = fv_decode_full(ctx, ob, T, 1, FV_MODE_SINGLE_PASS, path_out, score_out);
     ctx->vanilla = 0;

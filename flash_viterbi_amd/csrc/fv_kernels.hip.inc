@@ -1456,6 +1456,144 @@ static inline size_t csr_lds_bytes(int nrows, bool mem)
     return (mem ? (size_t)0 : (size_t)nrows * NB * 4) + (size_t)NB * SP_WAVES * TILE_W * 12;
 }
 
+// The float64 walk over the same CSC-32 table (FV_KERNEL_CSR_F64): every stored entry is evaluated with the reference
+// expression from its float64 log — what trellis_step<double, ...> does for every cell of a dense table, the absent
+// entries being that table's -inf cells, which a strict '>' never takes.  No filter, no window, no refine, and so no
+// condition on the sign of a log or of an emission score: the walk of a model with entries above 1 and of staged scores
+// above 0.  It streams ck (16 B per 4 entries) and c64 (32 B per 4 entries: two 16-byte loads per lane) — 12 B per
+// padded entry — and never reads cq.
+// A lane's entries ascend in k with its position (chunk 4 * wave-block + rg of its column), so the strict '>' within the
+// lane and `better` across lanes, waves and the workgroup give the reference's lowest-k winner.  Pads hold k = 0 and a
+// log of -inf: -inf never wins.
+// Dead sources are NOT read as -inf here: with a log or a score above 0 a source at -FLT_MAX can yield a cell above
+// -FLT_MAX, which the dense float64 kernel takes.
+// args.vanilla (uniform per launch): the baseline's rounding order, (float)(((double)T1[k] + log A) + log B), as
+// trellis_step<double, ...> carries it.
+template <int NB>
+struct CsrF64Args {
+    const uint4 *ck;
+    const double *c64;
+    const long long *tile_off;   // [ntiles] first vector of each tile
+    const int *tile_nwb;         // [ntiles] wave-blocks (64 vectors) in each tile
+    int K, nrows, ntiles, tiles_per_xcd, nb, vanilla;
+    TaskSlot t[NB];
+};
+
+template <int NB, bool MEM>
+__global__ __launch_bounds__(SP_BLOCK) void trellis_step_csr_f64(const CsrF64Args<NB> args)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int nrows = args.nrows;
+    float *T1s = reinterpret_cast<float *>(smem);              // [nrows][NB] (MEM: absent)
+    float *redR = T1s + (MEM ? (size_t)0 : (size_t)nrows * NB);  // [NB][TILE_W][SP_WAVES]
+    int *redK = reinterpret_cast<int *>(redR + NB * SP_WAVES * TILE_W);
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane & (TILE_W - 1), rg = lane >> 4;
+    const int tile = (blockIdx.x & 7) * args.tiles_per_xcd + (blockIdx.x >> 3);
+    if (tile >= args.ntiles) return;                          // workgroup-uniform
+    const int col = tile * TILE_W + c;
+    const int K = args.K;
+    const size_t v0 = (size_t)args.tile_off[tile] + rg * TILE_W + c;      // this lane's vector of wave-block 0
+    const uint4 *kb = args.ck + v0;
+    const double2 *lb = reinterpret_cast<const double2 *>(args.c64) + 2 * v0;
+    const int nwb = args.tile_nwb[tile];
+    const int nj = nwb > w ? (nwb - w + SP_WAVES - 1) / SP_WAVES : 0;     // wave-blocks of this wave
+    auto vec = [&](int j) { return (size_t)(w + SP_WAVES * j) * (4 * TILE_W); };
+    constexpr int U = 4;
+    uint4 curk[U];
+    double2 curl[U][2];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        if (u < nj) { curk[u] = kb[vec(u)]; curl[u][0] = lb[2 * vec(u)]; curl[u][1] = lb[2 * vec(u) + 1]; }
+
+    const bool vanilla = args.vanilla != 0;
+    float tmp[NB];
+    double tmp64[NB];
+    if constexpr (!MEM) stage_rows<NB, SP_BLOCK>(T1s, args.t, nrows, tid);
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        tmp[t] = (t < args.nb && col < K) ? args.t[t].tmp_row[col] : 0.0f;
+        tmp64[t] = (vanilla && t < args.nb && col < K) ? args.t[t].tmp64_row[col] : 0.0;
+    }
+    __syncthreads();
+
+    float m1[NB];
+    int k1[NB];
+#pragma unroll
+    for (int t = 0; t < NB; ++t) { m1[t] = FV_NEG_INF; k1[t] = INT_MAX; }
+
+    auto visit = [&](unsigned int k, double L) {
+        float tv[NB];
+        if constexpr (MEM) {
+#pragma unroll
+            for (int t = 0; t < NB; ++t) tv[t] = args.t[t].t1_in[k];
+        } else {
+            load_t1<NB>(T1s, (int)k, tv);
+        }
+#pragma unroll
+        for (int t = 0; t < NB; ++t) {
+            const float y = vanilla ? (float)(((double)tv[t] + L) + tmp64[t]) : exact_cell(tmp[t], tv[t], L);
+            const bool gt = y > m1[t];
+            m1[t] = gt ? y : m1[t];
+            k1[t] = gt ? (int)k : k1[t];
+        }
+    };
+    for (int p0 = 0; p0 < nj; p0 += U) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (p0 + u < nj) {
+                const uint4 k4 = curk[u];
+                visit(k4.x, curl[u][0].x); visit(k4.y, curl[u][0].y);
+                visit(k4.z, curl[u][1].x); visit(k4.w, curl[u][1].y);
+            }
+        }
+        if (p0 + U < nj) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (p0 + U + u < nj) {
+                    curk[u] = kb[vec(p0 + U + u)];
+                    curl[u][0] = lb[2 * vec(p0 + U + u)]; curl[u][1] = lb[2 * vec(p0 + U + u) + 1];
+                }
+        }
+    }
+
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        float r = m1[t];
+        int kbest = k1[t];
+        wave_best(r, kbest);
+        if (lane < TILE_W) { redR[(t * TILE_W + c) * SP_WAVES + w] = r; redK[(t * TILE_W + c) * SP_WAVES + w] = kbest; }
+    }
+    __syncthreads();
+    if (w < NB && w < args.nb) {
+        // 8 wave results per column: lanes (c, rg<2) read 4 each
+        float r = FV_NEG_INF;
+        int kbest = INT_MAX;
+        if (rg < 2) {
+            const float4 fv = *reinterpret_cast<const float4 *>(redR + (w * TILE_W + c) * SP_WAVES + rg * 4);
+            const int4 fk = *reinterpret_cast<const int4 *>(redK + (w * TILE_W + c) * SP_WAVES + rg * 4);
+            r = fv.x; kbest = fk.x;
+            if (better(fv.y, fk.y, r, kbest)) { r = fv.y; kbest = fk.y; }
+            if (better(fv.z, fk.z, r, kbest)) { r = fv.z; kbest = fk.z; }
+            if (better(fv.w, fk.w, r, kbest)) { r = fv.w; kbest = fk.w; }
+        }
+        wave_best(r, kbest);
+        if (lane < TILE_W && col < K) {
+            // a column no finite entry reaches: the reference's initial (-FLT_MAX, -1), as last_column_csr leaves it
+            const bool any = r > -FLT_MAX;
+            args.t[w].t1_out[col] = any ? r : -FLT_MAX;
+            args.t[w].bp_out[col] = any ? kbest : -1;
+        }
+    }
+}
+
+template <int NB>
+static inline size_t csr_f64_lds_bytes(int nrows, bool mem)
+{
+    return (mem ? (size_t)0 : (size_t)nrows * NB * 4) + (size_t)NB * SP_WAVES * TILE_W * 8;
+}
+
 // ---------------------------------------------------------------- small kernels
 
 

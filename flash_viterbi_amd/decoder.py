@@ -16,11 +16,16 @@ MODE_SINGLE_PASS = 1
 KERNEL_AUTO, KERNEL_F64_STREAM, KERNEL_F32_REFINE, KERNEL_F16_REFINE, KERNEL_Q16_REFINE, KERNEL_SPARSE_Q16 = 0, 1, 2, 3, 4, 5
 KERNEL_U16_REFINE = 6
 KERNEL_SPARSE_CSR = 7                  # reported by stats()["kernel"] for a model set by set_model_sparse; never chosen
+KERNEL_CSR_F64 = 8                     # models set by set_model_sparse: the float64 walk (entries above 1, emission scores above 0)
 OPT_KERNEL, OPT_MAX_BATCH, OPT_PROFILE, OPT_SEL_MARGIN, OPT_DEBUG = 1, 2, 3, 4, 100
 DEBUG_TIMING_ONLY = (1 << 0) | (1 << 4) | (1 << 5) | (1 << 11) | (1 << 12)      # refused by the shipped library
 DEBUG_BATCH_GEN0_SERIAL = 1 << 28      # decode_full_batch: the whole-sequence passes on one stream (speed only)
 DEBUG_BEAM_BATCH_GEN0_OTHER = 1 << 29  # decode_beam_batch: the whole-sequence passes in the launch form that is not the default (speed only)
 DEBUG_CSR_ROWS_IN_MEMORY = 1 << 31     # sparse-set models: the step kernel reads its score rows from memory at any K (speed only)
+# FV_TV_CSR64_* of include/flashvit_testing.h (test_forward's variants): trellis_step_csr_f64<NB, *> for NB = 1, 2, 4, 8, and the
+# bit every launch that read its score rows from memory sets in addition
+TV_CSR64_NB = (1 << 58, 1 << 59, 1 << 60, 1 << 61)
+TV_CSR64_MEM = 1 << 62
 WARN_BEAM_MISS = 1
 ERR_ARG, ERR_NOMEM, ERR_NO_PRED, ERR_DEVICE, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 UNIQUE_ID_BYTES = 128

@@ -81,7 +81,7 @@ enum {
                                form (the route of K > 65536), 23 runs of undecided steps always decided in full, 24 four-wave select also on steps that may have to be resolved,
                                25 / 26 the 16-bit step kernel in 16-wave / 8-wave workgroups whatever the launch size (25 also: the float64
                                step kernel in 16-wave workgroups for small beams too).  Models set by fv_set_model_sparse: 31 the
-                               step kernel reads its score rows from memory at any K (the form of K beyond one LDS row); bit 30
+                               step kernels read their score rows from memory at any K (the form of K beyond one LDS row); bit 30
                                is not assigned and refused */
 };
 #define FV_DEBUG_TIMING_ONLY ((1 << 0) | (1 << 4) | (1 << 5) | (1 << 11) | (1 << 12))
@@ -109,6 +109,12 @@ enum {
     FV_KERNEL_SPARSE_CSR = 7,  /* REPORTED ONLY (fv_stats.kernel; fv_set_option answers FV_ERR_ARG to it): the walk over the
                                   stored transitions of a model set by fv_set_model_sparse — the scheme of SPARSE_Q16 with
                                   32-bit source states, no dense table behind it */
+    FV_KERNEL_CSR_F64 = 8,     /* models set by fv_set_model_sparse only: the float64 walk over the stored transitions — the
+                                  reference expression on every stored entry from its float64 log (12 B per entry: 32-bit
+                                  source state + float64 log), no filter and so no condition on the values: the kernel
+                                  of a sparse-set model with entries above 1 or with staged emission scores above 0.  Same
+                                  bits out as the same model set by fv_set_model under F64_STREAM.  On a model set by
+                                  fv_set_model the full-state decodes answer FV_ERR_UNSUPPORTED to it */
 };
 
 typedef struct {
@@ -190,12 +196,19 @@ int fv_set_model(fv_ctx *ctx, const float *A, const float *B, const float *Pi, i
  * On a sparse-set model:
  *   - fv_decode_full, fv_decode_full_batch, fv_set_partition, fv_create_multi contexts and fv_test_forward work as on
  *     any model; fv_stats.kernel reports FV_KERNEL_SPARSE_CSR.  FV_OPT_KERNEL values FV_KERNEL_AUTO and
- *     FV_KERNEL_SPARSE_Q16 select that walk; any other (a kernel that streams a dense table) answers FV_ERR_UNSUPPORTED
- *     at decode.
- *   - A model with an entry above 1 is accepted here, as by fv_set_model, but its decode answers FV_ERR_UNSUPPORTED: the
- *     walk is a filter kernel (its error bracket needs every log <= 0) and there is no float64 table to fall back to.
- *   - fv_decode_beam, fv_decode_beam_batch, fv_decode_vanilla and fv_decode_checkpoint answer FV_ERR_UNSUPPORTED before
- *     any device work: their kernels gather rows of the dense table. */
+ *     FV_KERNEL_SPARSE_Q16 select that walk, FV_KERNEL_CSR_F64 the float64 walk (reported as such); any other (a kernel
+ *     that streams a dense table) answers FV_ERR_UNSUPPORTED at decode.
+ *   - A model with an entry above 1 is accepted here, as by fv_set_model, but under FV_KERNEL_AUTO / FV_KERNEL_SPARSE_Q16
+ *     its decode answers FV_ERR_UNSUPPORTED: that walk is a filter kernel (its error bracket needs every log <= 0) and
+ *     there is no dense float64 table to fall back to.  The same holds once a staged emission score is above 0.
+ *     FV_KERNEL_CSR_F64 decodes both: any model values, any staged scores, ob != NULL and ob == NULL, both modes, every
+ *     FV_OPT_MAX_BATCH, bit for bit what fv_set_model + FV_KERNEL_F64_STREAM deliver (path with its -1 entries, score,
+ *     return code) — and so, for a model within [0,1], what the filter walk delivers.
+ *   - fv_decode_vanilla: FV_ERR_UNSUPPORTED unless FV_KERNEL_CSR_F64 is selected; then the float64 walk runs with the
+ *     baseline's rounding order and delivers what fv_decode_vanilla delivers on the dense-set model.
+ *   - fv_decode_beam, fv_decode_beam_batch, fv_test_beam_step and fv_decode_checkpoint answer FV_ERR_UNSUPPORTED before
+ *     any device work under every FV_OPT_KERNEL value, FV_KERNEL_CSR_F64 included: their kernels gather rows of the
+ *     dense table. */
 int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const int *col, const float *val,
                         const float *B, const float *Pi, int K, int M);
 
@@ -213,7 +226,8 @@ int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const int *col, c
  *   Values: finite or -inf.  A NaN, a +inf or a finite double whose float conversion is infinite answers FV_ERR_ARG, with
  * the lowest offending (t, state) in fv_last_error_detail.  A score above 0 (a density above 1) is accepted and handled
  * as a B entry above 1: decodes on these emissions take FV_KERNEL_F64_STREAM under AUTO, answer FV_ERR_UNSUPPORTED to a
- * forced filter kernel and on a model set by fv_set_model_sparse, and the beam path takes its float64 step kernel.
+ * forced filter kernel and on a model set by fv_set_model_sparse (unless FV_KERNEL_CSR_F64 is selected there), and the beam
+ * path takes its float64 step kernel.
  *   Returns FV_ERR_STATE without a model, FV_ERR_ARG for T < 1, ld < K, a bad dtype or a NULL pointer, FV_ERR_NOMEM (the
  * byte count in the detail, before anything is allocated) when 12 * T * K bytes plus the raw copy exceed the free device
  * memory.  A failed call leaves the context with no staged emissions.

@@ -197,6 +197,15 @@ int fv_test_beam_select(fv_ctx *ctx, int K, int beam, int s, const fv_test_selec
 #define FV_TV_CSR_MEM_NB2    (1ull << (FV_TV_CSR_SHIFT + 5))   /* trellis_step_csr<2, true> */
 #define FV_TV_CSR_MEM_NB4    (1ull << (FV_TV_CSR_SHIFT + 6))   /* trellis_step_csr<4, true> */
 #define FV_TV_CSR_MEM_NB8    (1ull << (FV_TV_CSR_SHIFT + 7))   /* trellis_step_csr<8, true> */
+/* The float64 walk of the same models (FV_KERNEL_CSR_F64): trellis_step_csr_f64<NB, MEM>.  Six bits were left, so the
+ * NB x MEM grid above does not fit: one bit per NB, and FV_TV_CSR64_MEM set IN ADDITION by every launch that read its
+ * score rows from memory. */
+#define FV_TV_CSR64_SHIFT    58
+#define FV_TV_CSR64_NB1      (1ull << (FV_TV_CSR64_SHIFT + 0))   /* trellis_step_csr_f64<1, *> */
+#define FV_TV_CSR64_NB2      (1ull << (FV_TV_CSR64_SHIFT + 1))   /* trellis_step_csr_f64<2, *> */
+#define FV_TV_CSR64_NB4      (1ull << (FV_TV_CSR64_SHIFT + 2))   /* trellis_step_csr_f64<4, *> */
+#define FV_TV_CSR64_NB8      (1ull << (FV_TV_CSR64_SHIFT + 3))   /* trellis_step_csr_f64<8, *> */
+#define FV_TV_CSR64_MEM      (1ull << (FV_TV_CSR64_SHIFT + 4))   /* trellis_step_csr_f64<*, true> */
 
 #ifdef __cplusplus
 }
