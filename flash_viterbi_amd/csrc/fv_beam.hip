@@ -357,42 +357,26 @@ int beam_tables(fv_ctx *ctx)
     return 0;
 }
 
-// The per-step buffers of a beam decode over T observations (a batch: all sequences end to end), indexed by absolute
-// time.  nseq > 0 (fv_decode_beam_batch): the sizes — these and fvi::ensure_workspace's — are first added up in 64 bits and
-// compared with the free device memory plus what growing a buffer releases, before anything is allocated.
+// The workspace of a beam decode over T observations (a batch: all sequences end to end): the per-step buffers, indexed
+// by absolute time, on top of what every decode needs.  nseq > 0 (fv_decode_beam_batch): the whole request is first added
+// up in 64 bits and compared with the free device memory plus what growing a buffer releases, before anything is allocated.
 int beam_workspace(fv_ctx *ctx, int T, int beam, int nseq)
 {
     const size_t K = (size_t)ctx->K, BP = (size_t)fvb::beam_pitch(beam), cap = (size_t)fvb::cand_cap_for(ctx->K, beam), t = (size_t)T;
-    auto each = [&](auto &&f) {
-        f(ctx->d_scores, t * K); f(ctx->d_hval, t * BP); f(ctx->d_hstate, t * BP);
-        f(ctx->d_doubt, t * fvb::DOUBT_CAP); f(ctx->d_doubt_count, t);
-        f(ctx->d_slot_val, t * beam); f(ctx->d_slot_state, t * beam);
-        f(ctx->d_tie_list, t * K); f(ctx->d_tie_count, (size_t)4);
-        f(ctx->d_cut, t * fvb::CUT_W); f(ctx->d_cand_count, t);
-        if (cap) f(ctx->d_cand, t * cap);
-        f(ctx->d_dupwin, t); f(ctx->d_needfull, (size_t)std::max(4, nseq));
-        if (nseq > 0) f(ctx->d_seqof, t);
-    };
+    fvi::Wants w;
+    w.add(ctx->d_scores, t * K); w.add(ctx->d_hval, t * BP); w.add(ctx->d_hstate, t * BP);
+    w.add(ctx->d_doubt, t * fvb::DOUBT_CAP); w.add(ctx->d_doubt_count, t);
+    w.add(ctx->d_slot_val, t * beam); w.add(ctx->d_slot_state, t * beam);
+    w.add(ctx->d_tie_list, t * K); w.add(ctx->d_tie_count, (size_t)4);
+    w.add(ctx->d_cut, t * fvb::CUT_W); w.add(ctx->d_cand_count, t);
+    if (cap) w.add(ctx->d_cand, t * cap);
+    w.add(ctx->d_dupwin, t); w.add(ctx->d_needfull, (size_t)std::max(4, nseq));
     if (nseq > 0) {
-        unsigned long long grow = 0, released = 0;
-        auto need = [&](auto &b, size_t n) { if (n > b.n) { grow += (unsigned long long)n * sizeof(*b.p); released += b.bytes(); } };
-        each(need);
-        need(ctx->d_ob, t); need(ctx->d_ans, t); need(ctx->d_bp, t * K);
-        need(ctx->d_rows, (size_t)2 * ctx->nrows); need(ctx->d_pack, fvi::pack_ints(ctx, T, std::max(nseq, 2)));
-        if (grow) {
-            size_t free_b = 0, total_b = 0;
-            FV_HIP(hipMemGetInfo(&free_b, &total_b));
-            if (grow > (unsigned long long)free_b + released) {
-                ctx->detail = "beam batch workspace: " + std::to_string(grow) + " bytes needed (score rows, back-pointers and tie list: " +
-                              std::to_string(16ull * t * K) + "), " + std::to_string((unsigned long long)free_b + released) +
-                              " bytes of device memory free";
-                return FV_ERR_NOMEM;
-            }
-        }
+        w.add(ctx->d_seqof, t);
+        w.what = "beam batch workspace";
+        w.dominant = "score rows, back-pointers and tie list: " + std::to_string(16ull * t * K);
     }
-    hipError_t first = hipSuccess;
-    each([&](auto &b, size_t n) { if (first == hipSuccess) first = b.ensure(n); });
-    FV_HIP(first);
+    if (int rc = fvi::ensure_workspace(ctx, T, 1, nseq > 0 ? std::max(nseq, 2) : 1, std::move(w))) return rc;
     FV_HIP(hipMemsetAsync(ctx->d_cut.p, 0xFF, t * fvb::CUT_W * sizeof(float), ctx->stream));      // NaN: no earlier pass has left a cut here
     FV_HIP(hipMemsetAsync(ctx->d_cand_count.p, 0, t * sizeof(int), ctx->stream));
     FV_HIP(hipMemsetAsync(ctx->d_dupwin.p, 0, t * sizeof(int), ctx->stream));
@@ -440,6 +424,12 @@ int run_beam_generations(fv_ctx *ctx, std::vector<std::vector<fv::Pass>> &gens, 
     return 0;
 }
 
+// statistics of a beam decode about to start (the float64 rows of the beam's members per step; no density is reported)
+void start_beam_stats(fv_ctx *ctx, const fv::Plan &plan, int beam_width)
+{
+    ctx->start_stats(FV_KERNEL_F64_STREAM, plan.generations(), (long long)beam_width * ctx->K * 8, 0.0);
+}
+
 int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_width, int mode, int *path_out, float *score_out)
 {
     if (!ctx || !path_out || T < 2 || n_split < 1) return FV_ERR_ARG;
@@ -452,26 +442,16 @@ int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_wi
     FV_HIP(hipSetDevice(ctx->device));
     fv::Plan plan;
     if ((rc = fv::build_plan(T, n_split, mode, ctx->nranks, plan))) return rc;
-    std::vector<std::vector<fv::Pass>> gens(plan.generations());
-    size_t most = 1;
-    for (const fv::Pass &p : plan.passes)
-        if (p.owner < 0 || p.owner % ctx->nranks == ctx->rank) gens[p.generation].push_back(p);
-    for (auto &g : gens) most = std::max(most, g.size());
-    if ((rc = fvi::ensure_workspace(ctx, T, 1))) return rc;
-    (void)most;
+    std::vector<std::vector<fv::Pass>> gens = fvi::deal_passes(ctx, plan);
     if ((rc = beam_workspace(ctx, T, beam_width, 0))) return rc;
     if ((rc = beam_tables(ctx))) return rc;
-
-    ctx->fresh_stats();
-    ctx->stats.kernel = FV_KERNEL_F64_STREAM;
-    ctx->stats.generations = plan.generations();
-    ctx->stats.table_bytes_per_step = (long long)beam_width * ctx->K * 8;
+    start_beam_stats(ctx, plan, beam_width);
 
     if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
     if ((rc = run_beam_generations(ctx, gens, beam_width, T, 1, nullptr))) return rc;
-    ctx->stats.cells = ctx->stats.task_steps * (long long)ctx->K * beam_width;
-    ctx->stats.alg_bytes = 4 * ctx->stats.cells;
-    return fvi::finish_decode(ctx, plan, T, path_out, score_out, t0, 0, true);
+    ctx->close_stats((long long)ctx->K * beam_width, 0);
+    const long long whole[2] = { 0, T };
+    return fvi::finish_decode(ctx, plan, whole, 1, path_out, score_out, nullptr, t0, 0, true);
 }
 
 // fv_decode_beam_batch: the forest plan (fv::build_forest, as fv_decode_full_batch) run by the beam generation driver.
@@ -480,47 +460,19 @@ int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_wi
 int decode_beam_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split, int beam_width, int mode,
                            int *path_out, float *score_out, int *status_out)
 {
-    if (!offsets || !path_out || nseq < 1 || n_split < 1) return FV_ERR_ARG;
-    if (mode != FV_MODE_REFERENCE && mode != FV_MODE_SINGLE_PASS) return FV_ERR_ARG;
-    if (offsets[0] != 0) { ctx->detail = "fv_decode_beam_batch: offsets[0] must be 0"; return FV_ERR_ARG; }
-    std::vector<int> lengths((size_t)nseq);
-    for (int s = 0; s < nseq; ++s) {
-        const long long len = offsets[s + 1] - offsets[s];
-        if (len < 0) { ctx->detail = "fv_decode_beam_batch: offsets decrease at sequence " + std::to_string(s); return FV_ERR_ARG; }
-        if (len < 2) { ctx->detail = "fv_decode_beam_batch: sequence " + std::to_string(s) + " has fewer than 2 observations"; return FV_ERR_ARG; }
-        if (offsets[s + 1] > 0x7fffffffLL) { ctx->detail = "fv_decode_beam_batch: more than 2^31 - 1 observations in all (at sequence " + std::to_string(s) + ")"; return FV_ERR_ARG; }
-        lengths[(size_t)s] = (int)len;
-    }
-    int rc = fvi::emission_view(ctx, ob, offsets[nseq]);       // (ob == NULL: sequence s on staged rows offsets[s] ..)
-    if (rc) return rc;
-    if (ctx->K == 0) return FV_ERR_STATE;
-    if ((rc = beam_admit(ctx, beam_width))) return rc;
-    for (int s = 0; s < nseq; ++s)
-        for (long long j = offsets[s]; j < offsets[s + 1]; ++j)
-            if (ob[j] < 0 || ob[j] >= ctx->view.nsym) {
-                ctx->detail = "fv_decode_beam_batch: sequence " + std::to_string(s) + " holds a symbol outside [0, M) at position " + std::to_string(j - offsets[s]);
-                return FV_ERR_ARG;
-            }
+    const char *who = "fv_decode_beam_batch";
+    std::vector<int> lengths;
+    int rc = fvi::batch_lengths(ctx, who, ob, offsets, nseq, n_split, mode, path_out, lengths);
+    if (rc || (rc = beam_admit(ctx, beam_width)) || (rc = fvi::batch_symbols(ctx, who, ob, offsets, nseq))) return rc;
     auto t0 = clk::now();
     const int sumT = (int)offsets[nseq];
     fv::Plan plan;
-    int bad = -1;
-    if ((rc = fv::build_forest(lengths.data(), nseq, n_split, mode, plan, &bad))) {
-        ctx->detail = "fv_decode_beam_batch: sequence " + std::to_string(bad) + " of length " + std::to_string(lengths[(size_t)std::max(bad, 0)]) +
-                      " has no plan for n_split = " + std::to_string(n_split) + " (T == 2 * n_split with n_split > 2)";
-        return rc;
-    }
-    std::vector<std::vector<fv::Pass>> gens(plan.generations());
-    for (const fv::Pass &p : plan.passes) gens[p.generation].push_back(p);
+    if ((rc = fvi::batch_plan(ctx, who, lengths, n_split, mode, plan))) return rc;
+    std::vector<std::vector<fv::Pass>> gens = fvi::deal_passes(ctx, plan);
     FV_HIP(hipSetDevice(ctx->device));
     if ((rc = beam_workspace(ctx, sumT, beam_width, nseq))) return rc;           // (checks the whole working set first)
-    if ((rc = fvi::ensure_workspace(ctx, sumT, 1, std::max(nseq, 2)))) return rc;
     if ((rc = beam_tables(ctx))) return rc;
-
-    ctx->fresh_stats();
-    ctx->stats.kernel = FV_KERNEL_F64_STREAM;
-    ctx->stats.generations = plan.generations();
-    ctx->stats.table_bytes_per_step = (long long)beam_width * ctx->K * 8;
+    start_beam_stats(ctx, plan, beam_width);
 
     if ((rc = fvi::begin_decode(ctx, ob, sumT))) return rc;
     // time -> sequence: how heap_build_all and tie_fixup find the gate of a step (4 bytes per observation)
@@ -528,9 +480,8 @@ int decode_beam_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets,
     for (int s = 0; s < nseq; ++s) std::fill(ctx->h_seqof.begin() + offsets[s], ctx->h_seqof.begin() + offsets[s + 1], s);
     FV_HIP(hipMemcpyAsync(ctx->d_seqof.p, ctx->h_seqof.data(), (size_t)sumT * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     if ((rc = run_beam_generations(ctx, gens, beam_width, sumT, nseq, ctx->d_seqof.p))) return rc;
-    ctx->stats.cells = ctx->stats.task_steps * (long long)ctx->K * beam_width;
-    ctx->stats.alg_bytes = 4 * ctx->stats.cells;
-    return fvi::finish_decode_batch(ctx, offsets, nseq, path_out, score_out, status_out, t0, 0, true);
+    ctx->close_stats((long long)ctx->K * beam_width, 0);
+    return fvi::finish_decode(ctx, plan, offsets, nseq, path_out, score_out, status_out, t0, 0, true);
 }
 }  // namespace
 

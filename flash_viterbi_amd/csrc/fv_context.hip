@@ -29,59 +29,53 @@ namespace fvi {
 
 size_t device_bytes(const fv_ctx *c)
 {
-    return c->LA32.bytes() + c->LA16.bytes() + c->LAQ16.bytes() + c->SPdata.bytes() + c->SPoff.bytes() + c->SPnwb.bytes() + c->LB32T.bytes() + c->LA64.bytes() + c->LB64T.bytes() + c->LPi64.bytes() +
-           c->d_ob.bytes() + c->d_ans.bytes() + c->d_bp.bytes() + c->d_gather.bytes() + c->d_rows.bytes() + c->d_ckpt.bytes() +
-           c->d_score.bytes() + c->d_counters.bytes() + c->d_hval.bytes() + c->d_scores.bytes() +
-           c->d_hstate.bytes() + c->d_flags.bytes() + c->d_slot_val.bytes() + c->d_slot_state.bytes() +
-           c->LA64R.bytes() + c->LAQ16R.bytes() + c->d_qaux.bytes() + c->d_tie_list.bytes() + c->d_tie_count.bytes() + c->d_cut.bytes() + c->d_dupwin.bytes() + c->d_cand.bytes() + c->d_cand_count.bytes() + c->d_passL.bytes() + c->d_needfull.bytes() + c->d_seqof.bytes() + c->d_doubt.bytes() + c->d_doubt_count.bytes() + c->d_pack.bytes() +
-           c->CSk.bytes() + c->CSq.bytes() + c->CS64.bytes() + c->CSoff.bytes() + c->CSnwb.bytes() + c->CRptr.bytes() + c->CRcol.bytes() + c->CRlog.bytes() +
-           c->E32.bytes() + c->E64.bytes() + c->d_emflags.bytes();
+    size_t sum = 0;
+    c->each_buffer([&](const auto &b) { sum += b.bytes(); });
+    return sum;
 }
 
-// ints in front of the answers in the result block: the counters (64-bit each), then the scores (one per sequence of a
-// batch decode) padded to a multiple of four
+// ints in front of the answers in the result block: the counters (64-bit each), then the scores (one per sequence)
+// padded to a multiple of four
 inline size_t pack_head(int nscores) { return 2 * FV_NCOUNTERS + (size_t)std::max(4, round_up(nscores, 4)); }
 
 // result block + the staged observations
-size_t pack_ints(const fv_ctx *ctx, int T, int nscores) { return pack_head(nscores) + (size_t)T * std::max(1, ctx->nranks) + (size_t)T; }
+static size_t pack_ints(const fv_ctx *ctx, int T, int nscores) { return pack_head(nscores) + (size_t)T * std::max(1, ctx->nranks) + (size_t)T; }
 
-int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed, int nscores)
+int grant(fv_ctx *ctx, const Wants &w, bool check)
 {
-    const size_t want_rows = rows_needed * 2 * (size_t)ctx->nrows;
-    const size_t want_pack = pack_ints(ctx, T, nscores);
-    if (nscores > 1) {
+    if (check) {
         // A batch's working set grows with the total length (arg rows: T * K int32): sized in 64 bits and compared with
         // what the device has free (plus what growing a buffer releases first) before anything is allocated.
         unsigned long long grow = 0, released = 0;
-        auto need = [&](size_t have_bytes, unsigned long long want_bytes) {
-            if (want_bytes > have_bytes) { grow += want_bytes; released += have_bytes; }
-        };
-        need(ctx->d_ob.bytes(), 4ull * T);
-        need(ctx->d_ans.bytes(), 4ull * T);
-        need(ctx->d_bp.bytes(), 4ull * T * ctx->K);
-        need(ctx->d_rows.bytes(), 4ull * want_rows);
-        need(ctx->d_pack.bytes(), 4ull * want_pack);
+        for (const Wants::Want &x : w.list)
+            if (x.n > x.have) { grow += (unsigned long long)x.n * x.elem; released += (unsigned long long)x.have * x.elem; }
         if (grow) {
             size_t free_b = 0, total_b = 0;
             FV_HIP(hipMemGetInfo(&free_b, &total_b));
             if (grow > (unsigned long long)free_b + released) {
-                ctx->detail = "batch workspace: " + std::to_string(grow) + " bytes needed (arg rows " + std::to_string(4ull * T * ctx->K) +
-                              "), " + std::to_string((unsigned long long)free_b + released) + " bytes of device memory free";
+                ctx->detail = w.what + ": " + std::to_string(grow) + " bytes needed (" + w.dominant + "), " +
+                              std::to_string((unsigned long long)free_b + released) + " bytes of device memory free";
                 return FV_ERR_NOMEM;
             }
         }
     }
-    FV_HIP(ctx->d_ob.ensure(T));
-    FV_HIP(ctx->d_ans.ensure(T));
-    FV_HIP(ctx->d_bp.ensure((size_t)T * ctx->K));
-    if (want_rows > ctx->d_rows.n) {
-        FV_HIP(ctx->d_rows.ensure(want_rows));
-        FV_HIP(hipMemsetAsync(ctx->d_rows.p, 0, want_rows * sizeof(float), ctx->stream));   // row pads stay zero
-    }
+    for (const Wants::Want &x : w.list) FV_HIP(x.ensure(x.buf, x.n));
+    return 0;
+}
+
+int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed, int nscores, Wants w)
+{
+    const size_t want_rows = rows_needed * 2 * (size_t)ctx->nrows;
+    const size_t want_pack = pack_ints(ctx, T, nscores);
+    const bool rows_grow = want_rows > ctx->d_rows.n;
+    w.add(ctx->d_ob, (size_t)T); w.add(ctx->d_ans, (size_t)T); w.add(ctx->d_bp, (size_t)T * ctx->K);
+    w.add(ctx->d_rows, want_rows); w.add(ctx->d_pack, want_pack);
+    if (nscores > 1 && w.what.empty()) { w.what = "batch workspace"; w.dominant = "arg rows " + std::to_string(4ull * T * ctx->K); }
+    if (int rc = grant(ctx, w, nscores > 1)) return rc;
+    if (rows_grow) FV_HIP(hipMemsetAsync(ctx->d_rows.p, 0, want_rows * sizeof(float), ctx->stream));   // row pads stay zero
     FV_HIP(ctx->d_score.ensure((size_t)std::max(4, nscores)));
     FV_HIP(ctx->d_counters.ensure(FV_NCOUNTERS));
     if (ctx->comm || ctx->group) FV_HIP(ctx->d_gather.ensure((size_t)T * ctx->nranks));
-    FV_HIP(ctx->d_pack.ensure(want_pack));
     if (want_pack > ctx->h_pin_n) {
         if (ctx->h_pin) { (void)hipHostFree(ctx->h_pin); ctx->h_pin = nullptr; ctx->h_pin_n = 0; }
         FV_HIP(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_pin), want_pack * sizeof(int), hipHostMallocDefault));
@@ -90,19 +84,9 @@ int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed, int nscores)
     return 0;
 }
 
-constexpr size_t PACK_HEAD = 2 * FV_NCOUNTERS + 4;        // ints in front of the answers: the counters (64-bit each), score + padding
-
-__global__ void pack_result(const unsigned long long *counters, const float *score, const int *ans, size_t nans, int *out)
-{
-    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid < 2 * FV_NCOUNTERS) out[tid] = reinterpret_cast<const int *>(counters)[tid];
-    if (tid == 0) out[2 * FV_NCOUNTERS] = __float_as_int(*score);
-    for (size_t i = tid; i < nans; i += (size_t)gridDim.x * blockDim.x) out[PACK_HEAD + i] = ans[i];
-}
-
-// the same block for a batch decode: [counters | nscore scores, padded | answers of all sequences]
-__global__ void pack_result_batch(const unsigned long long *counters, const float *score, int nscore, size_t head, const int *ans,
-                                  size_t nans, int *out)
+// the result block: [counters | nscore scores, padded to `head` | the answers of all sequences, or the gathered answers]
+__global__ void pack_result(const unsigned long long *counters, const float *score, int nscore, size_t head, const int *ans,
+                            size_t nans, int *out)
 {
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
     if (tid < 2 * FV_NCOUNTERS) out[tid] = reinterpret_cast<const int *>(counters)[tid];
@@ -151,6 +135,58 @@ int begin_decode(fv_ctx *ctx, const int *ob, int T)
     return 0;
 }
 
+int batch_lengths(fv_ctx *ctx, const char *who, const int *&ob, const long long *offsets, int nseq, int n_split, int mode,
+                  const int *path_out, std::vector<int> &lengths)
+{
+    if (!offsets || !path_out || nseq < 1 || n_split < 1) return FV_ERR_ARG;
+    if (mode != FV_MODE_REFERENCE && mode != FV_MODE_SINGLE_PASS) return FV_ERR_ARG;
+    const std::string w = who;
+    if (offsets[0] != 0) { ctx->detail = w + ": offsets[0] must be 0"; return FV_ERR_ARG; }
+    lengths.resize((size_t)nseq);
+    for (int s = 0; s < nseq; ++s) {
+        const long long len = offsets[s + 1] - offsets[s];
+        if (len < 0) { ctx->detail = w + ": offsets decrease at sequence " + std::to_string(s); return FV_ERR_ARG; }
+        if (len < 2) { ctx->detail = w + ": sequence " + std::to_string(s) + " has fewer than 2 observations"; return FV_ERR_ARG; }
+        if (offsets[s + 1] > 0x7fffffffLL) { ctx->detail = w + ": more than 2^31 - 1 observations in all (at sequence " + std::to_string(s) + ")"; return FV_ERR_ARG; }
+        lengths[(size_t)s] = (int)len;
+    }
+    if (int rc = emission_view(ctx, ob, offsets[nseq])) return rc;       // (ob == NULL: sequence s on staged rows offsets[s] ..)
+    return ctx->K == 0 ? FV_ERR_STATE : 0;
+}
+
+int batch_symbols(fv_ctx *ctx, const char *who, const int *ob, const long long *offsets, int nseq)
+{
+    for (int s = 0; s < nseq; ++s)
+        for (long long j = offsets[s]; j < offsets[s + 1]; ++j)
+            if (ob[j] < 0 || ob[j] >= ctx->view.nsym) {
+                ctx->detail = std::string(who) + ": sequence " + std::to_string(s) + " holds a symbol outside [0, M) at position " + std::to_string(j - offsets[s]);
+                return FV_ERR_ARG;
+            }
+    return 0;
+}
+
+int batch_plan(fv_ctx *ctx, const char *who, const std::vector<int> &lengths, int n_split, int mode, fv::Plan &plan)
+{
+    int bad = -1;
+    const int rc = fv::build_forest(lengths.data(), (int)lengths.size(), n_split, mode, plan, &bad);
+    if (rc)
+        ctx->detail = std::string(who) + ": sequence " + std::to_string(bad) + " of length " + std::to_string(lengths[(size_t)std::max(bad, 0)]) +
+                      " has no plan for n_split = " + std::to_string(n_split) + " (T == 2 * n_split with n_split > 2)";
+    return rc;
+}
+
+std::vector<std::vector<fv::Pass>> deal_passes(const fv_ctx *ctx, const fv::Plan &plan, size_t *most)
+{
+    std::vector<std::vector<fv::Pass>> gens(plan.generations());
+    for (const fv::Pass &p : plan.passes)
+        if (p.owner < 0 || p.owner % ctx->nranks == ctx->rank) gens[p.generation].push_back(p);
+    if (most) {
+        *most = 1;
+        for (const auto &g : gens) *most = std::max(*most, g.size());
+    }
+    return gens;
+}
+
 // statistics of a finished decode: event times and the device counters the result block brought back
 static int read_stats(fv_ctx *ctx, const unsigned long long *counters, clk::time_point t0, size_t nprof)
 {
@@ -185,20 +221,17 @@ static int read_stats(fv_ctx *ctx, const unsigned long long *counters, clk::time
     return 0;
 }
 
-int finish_decode(fv_ctx *ctx, const fv::Plan &plan, int T, int *path_out, float *score_out, clk::time_point t0,
-                  size_t nprof, bool beam)
+int finish_decode(fv_ctx *ctx, const fv::Plan &plan, const long long *offsets, int nseq, int *path_out, float *score_out,
+                  int *status_out, clk::time_point t0, size_t nprof, bool beam)
 {
-    std::vector<int> host;
-    const bool gathered = (ctx->comm || ctx->group) && !plan.seg_L.empty();
-    if (gathered) {
-        int rc = gather_answers(ctx, T);                  // one RCCL all-gather of every rank's answer array (fv_comm.hip)
-        if (rc) return rc;
-        host.resize((size_t)T * ctx->nranks);
-    }
+    const int T = (int)offsets[nseq];
+    const bool gathered = (ctx->comm || ctx->group) && !plan.seg_L.empty();      // (never a batch: they take no partition)
+    if (gathered)
+        if (int rc = gather_answers(ctx, T)) return rc;   // one RCCL all-gather of every rank's answer array (fv_comm.hip)
     FV_HIP(hipEventRecord(ctx->ev_stop, ctx->stream));
-    // [counters | score | answers] in one block, one device-to-host copy into pinned memory
-    const size_t nans = gathered ? host.size() : (size_t)T, total = PACK_HEAD + nans;
-    hipLaunchKernelGGL(pack_result, dim3(64), dim3(256), 0, ctx->stream, ctx->d_counters.p, ctx->d_score.p,
+    // [counters | scores | answers] in one block, one device-to-host copy into pinned memory
+    const size_t nans = gathered ? (size_t)T * ctx->nranks : (size_t)T, head = pack_head(nseq), total = head + nans;
+    hipLaunchKernelGGL(pack_result, dim3(64), dim3(256), 0, ctx->stream, ctx->d_counters.p, ctx->d_score.p, nseq, head,
                        gathered ? ctx->d_gather.p : ctx->d_ans.p, nans, ctx->d_pack.p);
     FV_HIP(hipGetLastError());
     FV_HIP(hipMemcpyAsync(ctx->h_pin, ctx->d_pack.p, total * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -206,44 +239,16 @@ int finish_decode(fv_ctx *ctx, const fv::Plan &plan, int T, int *path_out, float
     for (hipGraphExec_t ge : ctx->graphs) (void)hipGraphExecDestroy(ge);
     ctx->graphs.clear();
     unsigned long long counters[FV_NCOUNTERS];
-    float score;
     std::memcpy(counters, ctx->h_pin, sizeof counters);
-    std::memcpy(&score, ctx->h_pin + 2 * FV_NCOUNTERS, sizeof score);
     if (gathered) {
-        std::memcpy(host.data(), ctx->h_pin + PACK_HEAD, nans * sizeof(int));
+        const std::vector<int> host(ctx->h_pin + head, ctx->h_pin + head + nans);
         merge_gathered(plan, host, T, ctx->nranks, path_out);
     } else {
-        std::memcpy(path_out, ctx->h_pin + PACK_HEAD, nans * sizeof(int));
+        std::memcpy(path_out, ctx->h_pin + head, nans * sizeof(int));
     }
-    if (score_out) *score_out = score;
-
-    if (int rc = read_stats(ctx, counters, t0, nprof)) return rc;
-    bool neg = false;
-    for (int j = 0; j < T; ++j) neg |= path_out[j] < 0;
-    if (neg) return beam ? FV_WARN_BEAM_MISS : FV_ERR_NO_PRED;
-    return FV_OK;
-}
-
-// Epilogue of fv_decode_full_batch / fv_decode_beam_batch: every sequence's answers, the nseq scores and the counters in
-// one block, one device-to-host copy, one sync; the scan for entries without a predecessor (beam: after a beam miss) is
-// per sequence.  Return: the most negative status, else the largest (FV_WARN_BEAM_MISS), else 0.
-int finish_decode_batch(fv_ctx *ctx, const long long *offsets, int nseq, int *path_out, float *score_out, int *status_out,
-                        clk::time_point t0, size_t nprof, bool beam)
-{
-    const size_t nans = (size_t)offsets[nseq], head = pack_head(nseq), total = head + nans;
-    FV_HIP(hipEventRecord(ctx->ev_stop, ctx->stream));
-    hipLaunchKernelGGL(pack_result_batch, dim3(64), dim3(256), 0, ctx->stream, ctx->d_counters.p, ctx->d_score.p, nseq, head,
-                       ctx->d_ans.p, nans, ctx->d_pack.p);
-    FV_HIP(hipGetLastError());
-    FV_HIP(hipMemcpyAsync(ctx->h_pin, ctx->d_pack.p, total * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    FV_HIP(hipStreamSynchronize(ctx->stream));
-    for (hipGraphExec_t ge : ctx->graphs) (void)hipGraphExecDestroy(ge);
-    ctx->graphs.clear();
-    unsigned long long counters[FV_NCOUNTERS];
-    std::memcpy(counters, ctx->h_pin, sizeof counters);
-    std::memcpy(path_out, ctx->h_pin + head, nans * sizeof(int));
     if (score_out) std::memcpy(score_out, ctx->h_pin + 2 * FV_NCOUNTERS, (size_t)nseq * sizeof(float));
     if (int rc = read_stats(ctx, counters, t0, nprof)) return rc;
+    // entries without a predecessor (beam: after a beam miss), per sequence
     int worst = FV_OK, warn = FV_OK;
     for (int s = 0; s < nseq; ++s) {
         bool neg = false;
@@ -326,13 +331,6 @@ extern "C" void fv_destroy(fv_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm) ncclCommDestroy(ctx->comm);
-    ctx->LA32.release(); ctx->LA16.release(); ctx->LAQ16.release(); ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release(); ctx->LB32T.release(); ctx->LA64.release(); ctx->LB64T.release(); ctx->LPi64.release();
-    ctx->d_ob.release(); ctx->d_ans.release(); ctx->d_bp.release(); ctx->d_gather.release(); ctx->d_rows.release(); ctx->d_ckpt.release();
-    ctx->d_score.release(); ctx->d_counters.release(); ctx->d_hval.release(); ctx->d_scores.release();
-    ctx->d_hstate.release(); ctx->d_flags.release(); ctx->d_slot_val.release(); ctx->d_slot_state.release();
-    ctx->LA64R.release(); ctx->LAQ16R.release(); ctx->d_qaux.release(); ctx->d_tie_list.release(); ctx->d_tie_count.release(); ctx->d_cut.release(); ctx->d_dupwin.release(); ctx->d_cand.release(); ctx->d_cand_count.release(); ctx->d_passL.release(); ctx->d_needfull.release(); ctx->d_seqof.release(); ctx->d_doubt.release(); ctx->d_doubt_count.release(); ctx->d_pack.release();
-    fvi::release_csr(ctx);
-    ctx->E32.release(); ctx->E64.release(); ctx->d_emflags.release();
     if (ctx->h_pin) { (void)hipHostFree(ctx->h_pin); ctx->h_pin = nullptr; ctx->h_pin_n = 0; }
     for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
@@ -346,7 +344,7 @@ extern "C" void fv_destroy(fv_ctx *ctx)
         if (ctx->aux[q]) (void)hipStreamDestroy(ctx->aux[q]);
     }
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;          // (the device buffers free themselves)
 }
 
 namespace fvi {
@@ -506,20 +504,45 @@ int build_host_tables(const float *A, const float *B, const float *Pi, int K, in
     return FV_OK;
 }
 
-// Device side of fv_set_model, once per device.  Tables are released and overwritten in place: until every upload has
-// succeeded the context holds NO model (K = 0 makes every decode return FV_ERR_STATE), so a failure half way (e.g.
-// NOMEM on a larger second model) can never pair the old sizes with partly new tables.
-int upload_tables(fv_ctx *ctx, const HostTables &h)
+// What both model setters do first on a device: the context holds NO model from here until every upload has succeeded
+// (K = 0 makes every decode return FV_ERR_STATE), so a failure half way (e.g. NOMEM on a larger second model) can never
+// pair the old sizes with partly new tables.  Every table that is rebuilt rather than overwritten in place is released;
+// keep_dense: the tile-major tables of fv_set_model stay allocated, to be overwritten (log B and log Pi always do).
+static void drop_model(fv_ctx *ctx, bool keep_dense)
 {
-    FV_HIP(hipSetDevice(ctx->device));
     ctx->K = 0; ctx->M = 0; ctx->nrows = 0; ctx->full_ok = false; ctx->u16_ok = false; ctx->laq16_ready = false;
-    ctx->rowq_ready = false; ctx->beam_q16_ready = false;
+    ctx->rowq_ready = false; ctx->beam_q16_ready = false; ctx->csr = false;
     ctx->emis_rows = 0; ctx->emis_positive = false;      // staged emission scores belong to the model they were staged under
     (void)hipStreamSynchronize(ctx->stream);
     ctx->LA64R.release(); ctx->LAQ16R.release();
     ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release();
-    release_csr(ctx);
-    ctx->window16 = h.window16; ctx->windowq = h.windowq; ctx->qscale = h.qscale; ctx->density = h.density;
+    ctx->CSk.release(); ctx->CSq.release(); ctx->CS64.release(); ctx->CSoff.release(); ctx->CSnwb.release();
+    ctx->CRptr.release(); ctx->CRcol.release(); ctx->CRlog.release();
+    if (!keep_dense) { ctx->LA32.release(); ctx->LA16.release(); ctx->LAQ16.release(); ctx->LA64.release(); }
+}
+
+// ... and last: log B and log Pi, then the sizes that make the context hold the model, and statistics from zero
+static int finish_upload(fv_ctx *ctx, const HostTables &e)
+{
+    ctx->window16 = e.window16; ctx->windowq = e.windowq; ctx->qscale = e.qscale; ctx->density = e.density;
+    FV_HIP(ctx->LB64T.ensure((size_t)e.M * e.K));
+    FV_HIP(ctx->LB32T.ensure((size_t)e.M * e.K));
+    FV_HIP(ctx->LPi64.ensure(e.K));
+    FV_HIP(hipMemcpy(ctx->LB64T.p, e.b64.data(), e.b64.size() * sizeof(double), hipMemcpyHostToDevice));
+    FV_HIP(hipMemcpy(ctx->LB32T.p, e.b32.data(), e.b32.size() * sizeof(float), hipMemcpyHostToDevice));
+    FV_HIP(hipMemcpy(ctx->LPi64.p, e.pi64.data(), e.pi64.size() * sizeof(double), hipMemcpyHostToDevice));
+    ctx->K = e.K; ctx->M = e.M; ctx->nrows = e.nrows;
+    ctx->logs_nonpositive = !e.any_big;
+    ctx->stats = fv_stats{};
+    ctx->stats.device_bytes = (long long)device_bytes(ctx);
+    return FV_OK;
+}
+
+// Device side of fv_set_model, once per device: the tables are overwritten in place.
+int upload_tables(fv_ctx *ctx, const HostTables &h)
+{
+    FV_HIP(hipSetDevice(ctx->device));
+    drop_model(ctx, true);
     const size_t tab = h.tab;
     if (h.full_ok) {
         FV_HIP(ctx->LAQ16.ensure(tab));
@@ -542,30 +565,11 @@ int upload_tables(fv_ctx *ctx, const HostTables &h)
     } else {
         ctx->LA32.release(); ctx->LA16.release(); ctx->LAQ16.release();
     }
-    FV_HIP(ctx->LB64T.ensure((size_t)h.M * h.K));
-    FV_HIP(ctx->LB32T.ensure((size_t)h.M * h.K));
-    FV_HIP(ctx->LPi64.ensure(h.K));
     FV_HIP(hipMemcpy(ctx->LA64.p, h.h64.data(), tab * sizeof(double), hipMemcpyHostToDevice));
-    FV_HIP(hipMemcpy(ctx->LB64T.p, h.b64.data(), h.b64.size() * sizeof(double), hipMemcpyHostToDevice));
-    FV_HIP(hipMemcpy(ctx->LB32T.p, h.b32.data(), h.b32.size() * sizeof(float), hipMemcpyHostToDevice));
-    FV_HIP(hipMemcpy(ctx->LPi64.p, h.pi64.data(), h.pi64.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = finish_upload(ctx, h)) return rc;
     ctx->laq16_ready = h.full_ok;          // beyond the float32 limit: built on first use (fv_full.hip)
-    ctx->K = h.K; ctx->M = h.M; ctx->nrows = h.nrows; ctx->full_ok = h.full_ok; ctx->u16_ok = h.u16_ok;     // LA64R / LAQ16R: rebuilt on the next beam decode
-    ctx->logs_nonpositive = !h.any_big;
-    ctx->stats = fv_stats{};
-    ctx->stats.device_bytes = (long long)device_bytes(ctx);
+    ctx->full_ok = h.full_ok; ctx->u16_ok = h.u16_ok;     // LA64R / LAQ16R: rebuilt on the next beam decode
     return FV_OK;
-}
-
-}  // namespace fvi
-
-namespace fvi {
-
-void release_csr(fv_ctx *ctx)
-{
-    ctx->csr = false;
-    ctx->CSk.release(); ctx->CSq.release(); ctx->CS64.release(); ctx->CSoff.release(); ctx->CSnwb.release();
-    ctx->CRptr.release(); ctx->CRcol.release(); ctx->CRlog.release();
 }
 
 // what fv_set_model_sparse computes on the host: everything is O(nnz + K * M)
@@ -692,15 +696,7 @@ int upload_csr(fv_ctx *ctx, const HostCsr &h, const long long *row_ptr, const in
 {
     const HostTables &e = h.e;
     FV_HIP(hipSetDevice(ctx->device));
-    ctx->K = 0; ctx->M = 0; ctx->nrows = 0; ctx->full_ok = false; ctx->u16_ok = false; ctx->laq16_ready = false;
-    ctx->rowq_ready = false; ctx->beam_q16_ready = false;
-    ctx->emis_rows = 0; ctx->emis_positive = false;      // staged emission scores belong to the model they were staged under
-    (void)hipStreamSynchronize(ctx->stream);
-    ctx->LA64R.release(); ctx->LAQ16R.release();
-    ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release();
-    ctx->LA32.release(); ctx->LA16.release(); ctx->LAQ16.release(); ctx->LA64.release();
-    release_csr(ctx);
-    ctx->window16 = e.window16; ctx->windowq = e.windowq; ctx->qscale = e.qscale; ctx->density = e.density;
+    drop_model(ctx, false);
     const size_t nnz = h.rlog.size(), nv = h.ck.size();
     FV_HIP(ctx->CSk.ensure(std::max<size_t>(nv, 1)));
     FV_HIP(ctx->CSq.ensure(std::max<size_t>(nv, 1)));
@@ -722,17 +718,8 @@ int upload_csr(fv_ctx *ctx, const HostCsr &h, const long long *row_ptr, const in
         FV_HIP(hipMemcpy(ctx->CRcol.p, col, nnz * sizeof(int), hipMemcpyHostToDevice));
         FV_HIP(hipMemcpy(ctx->CRlog.p, h.rlog.data(), nnz * sizeof(double), hipMemcpyHostToDevice));
     }
-    FV_HIP(ctx->LB64T.ensure((size_t)e.M * e.K));
-    FV_HIP(ctx->LB32T.ensure((size_t)e.M * e.K));
-    FV_HIP(ctx->LPi64.ensure(e.K));
-    FV_HIP(hipMemcpy(ctx->LB64T.p, e.b64.data(), e.b64.size() * sizeof(double), hipMemcpyHostToDevice));
-    FV_HIP(hipMemcpy(ctx->LB32T.p, e.b32.data(), e.b32.size() * sizeof(float), hipMemcpyHostToDevice));
-    FV_HIP(hipMemcpy(ctx->LPi64.p, e.pi64.data(), e.pi64.size() * sizeof(double), hipMemcpyHostToDevice));
-    ctx->K = e.K; ctx->M = e.M; ctx->nrows = e.nrows;
+    if (int rc = finish_upload(ctx, e)) return rc;
     ctx->csr = true;
-    ctx->logs_nonpositive = !e.any_big;
-    ctx->stats = fv_stats{};
-    ctx->stats.device_bytes = (long long)device_bytes(ctx);
     ctx->stats.density = ctx->density;
     return FV_OK;
 }
@@ -800,7 +787,6 @@ static int stage_emissions_on(fv_ctx *ctx, const void *scores, int dtype, int T,
     FV_HIP(ctx->E64.ensure(cells));
     FV_HIP(ctx->d_emflags.ensure(2));
     DevBuf<unsigned char> raw;
-    struct Free { DevBuf<unsigned char> &b; ~Free() { b.release(); } } free_raw{ raw };
     const void *src = scores;
     if (!in_place) {
         FV_HIP(raw.ensure(raw_bytes));

@@ -750,16 +750,14 @@ int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &ker
     return fvi::ensure_workspace(ctx, T, rows_needed, nscores);
 }
 
-void reset_stats(fv_ctx *ctx, int kernel, int generations)
+// statistics of a full-state decode about to start: the table bytes a step of `kernel` streams
+void start_full_stats(fv_ctx *ctx, int kernel, int generations)
 {
-    ctx->fresh_stats();
-    ctx->stats.kernel = kernel;
-    ctx->stats.generations = generations;
-    ctx->stats.table_bytes_per_step = (long long)((ctx->K + fvk::TILE_W - 1) / fvk::TILE_W) * ctx->nrows * fvk::TILE_W * (kernel == FV_KERNEL_F64_STREAM ? 8 : kernel == FV_KERNEL_F32_REFINE ? 4 : 2);
-    if (kernel == FV_KERNEL_SPARSE_Q16) ctx->stats.table_bytes_per_step = (long long)ctx->SPdata.bytes();
-    if (kernel == FV_KERNEL_SPARSE_CSR) ctx->stats.table_bytes_per_step = (long long)(ctx->CSk.bytes() + ctx->CSq.bytes());
-    if (kernel == FV_KERNEL_CSR_F64) ctx->stats.table_bytes_per_step = (long long)(ctx->CSk.bytes() + ctx->CS64.bytes());
-    ctx->stats.density = ctx->density;
+    long long table = (long long)((ctx->K + fvk::TILE_W - 1) / fvk::TILE_W) * ctx->nrows * fvk::TILE_W * (kernel == FV_KERNEL_F64_STREAM ? 8 : kernel == FV_KERNEL_F32_REFINE ? 4 : 2);
+    if (kernel == FV_KERNEL_SPARSE_Q16) table = (long long)ctx->SPdata.bytes();
+    if (kernel == FV_KERNEL_SPARSE_CSR) table = (long long)(ctx->CSk.bytes() + ctx->CSq.bytes());
+    if (kernel == FV_KERNEL_CSR_F64) table = (long long)(ctx->CSk.bytes() + ctx->CS64.bytes());
+    ctx->start_stats(kernel, generations, table, ctx->density);
 }
 
 int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, int *path_out, float *score_out)
@@ -772,15 +770,11 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
     fv::Plan plan;
     rc = fv::build_plan(T, n_split, mode, ctx->nranks, plan);
     if (rc) return rc;
-    // generations of passes this rank runs
-    std::vector<std::vector<fv::Pass>> gens(plan.generations());
     size_t most = 1;
-    for (const fv::Pass &p : plan.passes)
-        if (p.owner < 0 || p.owner % ctx->nranks == ctx->rank) gens[p.generation].push_back(p);
-    for (auto &g : gens) most = std::max(most, g.size());
+    std::vector<std::vector<fv::Pass>> gens = fvi::deal_passes(ctx, plan, &most);
     int kernel = FV_KERNEL_AUTO;
     if ((rc = prepare_full(ctx, ob, T, most, kernel))) return rc;
-    reset_stats(ctx, kernel, plan.generations());
+    start_full_stats(ctx, kernel, plan.generations());
 
     if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
     FV_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
@@ -791,9 +785,9 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
         if ((rc = run_generation_full(ctx, gens[g], kernel, nprof))) return rc;
         if (g == 0) FV_HIP(hipEventRecord(ctx->ev_top, ctx->stream));
     }
-    ctx->stats.cells = ctx->stats.task_steps * (long long)ctx->K * ctx->K + ctx->stats.column_steps * (long long)ctx->K;
-    ctx->stats.alg_bytes = 4 * ctx->stats.cells;
-    return fvi::finish_decode(ctx, plan, T, path_out, score_out, t0, nprof, false);
+    ctx->close_stats((long long)ctx->K * ctx->K, ctx->K);
+    const long long whole[2] = { 0, T };
+    return fvi::finish_decode(ctx, plan, whole, 1, path_out, score_out, nullptr, t0, nprof, false);
 }
 
 // fv_decode_full_batch: the forest plan (build_plan of every sequence on one concatenated time axis) run generation by
@@ -803,42 +797,19 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
 int decode_full_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, int n_split, int mode, int *path_out,
                            float *score_out, int *status_out)
 {
-    if (!offsets || !path_out || nseq < 1 || n_split < 1) return FV_ERR_ARG;
-    if (mode != FV_MODE_REFERENCE && mode != FV_MODE_SINGLE_PASS) return FV_ERR_ARG;
-    if (offsets[0] != 0) { ctx->detail = "fv_decode_full_batch: offsets[0] must be 0"; return FV_ERR_ARG; }
-    std::vector<int> lengths((size_t)nseq);
-    for (int s = 0; s < nseq; ++s) {
-        const long long len = offsets[s + 1] - offsets[s];
-        if (len < 0) { ctx->detail = "fv_decode_full_batch: offsets decrease at sequence " + std::to_string(s); return FV_ERR_ARG; }
-        if (len < 2) { ctx->detail = "fv_decode_full_batch: sequence " + std::to_string(s) + " has fewer than 2 observations"; return FV_ERR_ARG; }
-        if (offsets[s + 1] > 0x7fffffffLL) { ctx->detail = "fv_decode_full_batch: more than 2^31 - 1 observations in all (at sequence " + std::to_string(s) + ")"; return FV_ERR_ARG; }
-        lengths[(size_t)s] = (int)len;
-    }
-    if (int rv = fvi::emission_view(ctx, ob, offsets[nseq])) return rv;       // (ob == NULL: sequence s on staged rows offsets[s] ..)
-    if (ctx->K == 0) return FV_ERR_STATE;
-    for (int s = 0; s < nseq; ++s)
-        for (long long j = offsets[s]; j < offsets[s + 1]; ++j)
-            if (ob[j] < 0 || ob[j] >= ctx->view.nsym) {
-                ctx->detail = "fv_decode_full_batch: sequence " + std::to_string(s) + " holds a symbol outside [0, M) at position " + std::to_string(j - offsets[s]);
-                return FV_ERR_ARG;
-            }
+    const char *who = "fv_decode_full_batch";
+    std::vector<int> lengths;
+    int rc = fvi::batch_lengths(ctx, who, ob, offsets, nseq, n_split, mode, path_out, lengths);
+    if (rc || (rc = fvi::batch_symbols(ctx, who, ob, offsets, nseq))) return rc;
     auto t0 = clk::now();
     const int sumT = (int)offsets[nseq];
     fv::Plan plan;
-    int bad = -1;
-    int rc = fv::build_forest(lengths.data(), nseq, n_split, mode, plan, &bad);
-    if (rc) {
-        ctx->detail = "fv_decode_full_batch: sequence " + std::to_string(bad) + " of length " + std::to_string(lengths[(size_t)std::max(bad, 0)]) +
-                      " has no plan for n_split = " + std::to_string(n_split) + " (T == 2 * n_split with n_split > 2)";
-        return rc;
-    }
-    std::vector<std::vector<fv::Pass>> gens(plan.generations());
+    if ((rc = fvi::batch_plan(ctx, who, lengths, n_split, mode, plan))) return rc;
     size_t most = 1;
-    for (const fv::Pass &p : plan.passes) gens[p.generation].push_back(p);
-    for (auto &g : gens) most = std::max(most, g.size());
+    std::vector<std::vector<fv::Pass>> gens = fvi::deal_passes(ctx, plan, &most);
     int kernel = FV_KERNEL_AUTO;
     if ((rc = prepare_full(ctx, ob, sumT, most, kernel, std::max(nseq, 2)))) return rc;
-    reset_stats(ctx, kernel, plan.generations());
+    start_full_stats(ctx, kernel, plan.generations());
 
     if ((rc = fvi::begin_decode(ctx, ob, sumT))) return rc;
     FV_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
@@ -853,9 +824,8 @@ int decode_full_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets,
         if ((rc = run_generation_full(ctx, gens[g], kernel, nprof, gen0))) return rc;
         if (g == 0) FV_HIP(hipEventRecord(ctx->ev_top, ctx->stream));
     }
-    ctx->stats.cells = ctx->stats.task_steps * (long long)ctx->K * ctx->K + ctx->stats.column_steps * (long long)ctx->K;
-    ctx->stats.alg_bytes = 4 * ctx->stats.cells;
-    return fvi::finish_decode_batch(ctx, offsets, nseq, path_out, score_out, status_out, t0, nprof);
+    ctx->close_stats((long long)ctx->K * ctx->K, ctx->K);
+    return fvi::finish_decode(ctx, plan, offsets, nseq, path_out, score_out, status_out, t0, nprof, false);
 }
 
 // fv_test_forward (include/flashvit_testing.h): the caller's passes as one right-hand generation of run_generation_full
@@ -884,7 +854,7 @@ int test_forward_impl(fv_ctx *ctx, const int *ob, int T, const fv_test_pass *tp,
     int kernel = FV_KERNEL_AUTO;
     int rc = prepare_full(ctx, ob, T, (size_t)np, kernel);
     if (rc) return rc;
-    reset_stats(ctx, kernel, 1);
+    start_full_stats(ctx, kernel, 1);
     ctx->stats.passes = np;
     if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
     // Answer array: a valid state at every R (the generation's back-track starts there), then every pass's initial state
@@ -976,12 +946,8 @@ int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *pat
         FV_HIP(ctx->d_ckpt.ensure((size_t)nck * nrows));
         FV_HIP(hipMemsetAsync(ctx->d_ckpt.p, 0, (size_t)nck * nrows * sizeof(float), ctx->stream));   // row pads stay zero
     }
-    ctx->fresh_stats();
-    ctx->stats.kernel = FV_KERNEL_F64_STREAM;
-    ctx->stats.generations = 2;
+    start_full_stats(ctx, FV_KERNEL_F64_STREAM, 2);
     ctx->stats.passes = 1 + nck;
-    ctx->stats.table_bytes_per_step = (long long)((K + fvk::TILE_W - 1) / fvk::TILE_W) * nrows * fvk::TILE_W * 8;
-    ctx->stats.density = ctx->density;
     if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
     FV_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
 
@@ -1049,8 +1015,8 @@ int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *pat
         hipLaunchKernelGGL(fvk::backtrack, dim3(1), dim3(64), 0, ctx->stream, ch, ctx->d_bp.p, K, ctx->d_ans.p);
         FV_HIP(hipGetLastError());
     }
-    ctx->stats.cells = ctx->stats.task_steps * (long long)K * K;
-    ctx->stats.alg_bytes = 4 * ctx->stats.cells;
-    return fvi::finish_decode(ctx, plan, T, path_out, score_out, t0, 0, false);
+    ctx->close_stats((long long)K * K, 0);
+    const long long whole[2] = { 0, T };
+    return fvi::finish_decode(ctx, plan, whole, 1, path_out, score_out, nullptr, t0, 0, false);
 }
 }  // namespace

@@ -1,6 +1,6 @@
 // fv_internal.h — what the translation units of libflashvit.so share: the context behind the opaque fv_ctx of
 // include/flashvit.h, device buffers, the error macro and the few functions that cross a seam.
-//   fv_context.hip  fv_create / fv_destroy / fv_set_model / options / statistics, workspace, decode epilogue
+//   fv_context.hip  fv_create / fv_destroy / fv_set_model / options / statistics, workspace, batch admission, decode epilogue
 //   fv_full.hip     full-state kernels and their decode drivers (FLASH, vanilla, checkpoint)
 //   fv_beam.hip     FLASH-BS kernels and their decode driver
 //   fv_comm.hip     multi-GPU: partition, RCCL all-gather, merge, the single-process multi-device context
@@ -29,10 +29,15 @@
 using clk = std::chrono::steady_clock;
 inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
 
+// device memory that frees itself (on the device that is current: fv_destroy sets it before it deletes the context)
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t want)
     {
         if (want <= n) return hipSuccess;
@@ -163,12 +168,33 @@ struct fv_ctx {
 
     fv_stats stats{};
     // statistics of a decode about to start: everything cleared but what the model and the staged emissions own
-    void fresh_stats()
+    void start_stats(int kernel, int generations, long long table_bytes_per_step, double density_reported)
     {
         const double model_ms = stats.set_model_ms, emis_ms = stats.set_emissions_ms;
         const long long rows = stats.emission_rows;
         stats = fv_stats{};
         stats.set_model_ms = model_ms; stats.set_emissions_ms = emis_ms; stats.emission_rows = rows;
+        stats.kernel = kernel; stats.generations = generations;
+        stats.table_bytes_per_step = table_bytes_per_step; stats.density = density_reported;
+    }
+    // ... and of one whose launches are all queued: cells evaluated per task step and per column step, 4 B each
+    void close_stats(long long cells_per_task_step, long long cells_per_column_step)
+    {
+        stats.cells = stats.task_steps * cells_per_task_step + stats.column_steps * cells_per_column_step;
+        stats.alg_bytes = 4 * stats.cells;
+    }
+
+    // every device buffer of the context: the one list (device_bytes adds them up; each frees itself with the context)
+    template <class F>
+    void each_buffer(F &&f) const
+    {
+        f(LA32); f(LB32T); f(LA16); f(LAQ16); f(SPdata); f(SPoff); f(SPnwb); f(LA64); f(LB64T); f(LPi64);
+        f(CSk); f(CSq); f(CS64); f(CSoff); f(CSnwb); f(CRptr); f(CRcol); f(CRlog);
+        f(E32); f(E64); f(d_emflags);
+        f(d_ob); f(d_ans); f(d_bp); f(d_gather); f(d_rows); f(d_score); f(d_ckpt); f(d_counters); f(d_pack);
+        f(d_hval); f(d_scores); f(d_slot_val); f(d_hstate); f(d_slot_state); f(d_flags); f(LA64R); f(LAQ16R); f(d_qaux);
+        f(d_tie_list); f(d_cut); f(d_cand); f(d_cand_count); f(d_dupwin); f(d_doubt); f(d_doubt_count); f(d_needfull);
+        f(d_seqof); f(d_passL); f(d_tie_count);
     }
 };
 
@@ -203,19 +229,41 @@ struct HostTables {
 };
 int build_host_tables(const float *A, const float *B, const float *Pi, int K, int M, HostTables &h, std::string &detail);
 int upload_tables(fv_ctx *ctx, const HostTables &h);
-void release_csr(fv_ctx *ctx);           // drops the tables of a model set by fv_set_model_sparse
 
 size_t device_bytes(const fv_ctx *c);
-// (nscores > 1: a batch decode — room for that many scores, sizes checked against free device memory first)
-int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed, int nscores = 1);
-// ints of the result block (and of the pinned host block) a decode of T observations with nscores scores needs
-size_t pack_ints(const fv_ctx *ctx, int T, int nscores);
-// decode epilogue: (multi-rank: all-gather + merge,) path / score / counters to the host, one sync, statistics
-int finish_decode(fv_ctx *ctx, const fv::Plan &plan, int T, int *path_out, float *score_out, clk::time_point t0,
-                  size_t nprof, bool beam);
-// (beam: a sequence whose path holds -1 reports FV_WARN_BEAM_MISS instead of FV_ERR_NO_PRED)
-int finish_decode_batch(fv_ctx *ctx, const long long *offsets, int nseq, int *path_out, float *score_out, int *status_out,
-                        clk::time_point t0, size_t nprof, bool beam = false);
+// A workspace request: buffers and the elements each is wanted to hold.  A batch decode names itself (`what`) and its
+// dominant term: its request is then refused with those, before anything is allocated, if the device has not the room.
+struct Wants {
+    struct Want { void *buf; size_t n, have, elem; hipError_t (*ensure)(void *, size_t); };
+    std::vector<Want> list;
+    std::string what, dominant;
+    template <typename T>
+    void add(DevBuf<T> &b, size_t n)
+    {
+        list.push_back({ &b, n, b.n, sizeof(T), [](void *p, size_t m) { return static_cast<DevBuf<T> *>(p)->ensure(m); } });
+    }
+};
+// grows every buffer of the request; check: the growth is first added up in 64 bits and compared with the free device
+// memory plus what growing releases (FV_ERR_NOMEM with bytes needed, the dominant term and bytes free)
+int grant(fv_ctx *ctx, const Wants &w, bool check);
+// the workspace every decode needs, for T observations, rows_needed passes in flight and nscores scores, added to what
+// the caller wants (the beam buffers).  nscores > 1: a batch decode, whose request is checked before it is granted.
+int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed, int nscores = 1, Wants w = {});
+// Admission of fv_decode_full_batch / fv_decode_beam_batch (`who`, for the detail text), in the steps the entry points
+// take in this order: arguments, offsets -> lengths, emission view and model; the symbols' range; the forest plan.
+int batch_lengths(fv_ctx *ctx, const char *who, const int *&ob, const long long *offsets, int nseq, int n_split, int mode,
+                  const int *path_out, std::vector<int> &lengths);
+int batch_symbols(fv_ctx *ctx, const char *who, const int *ob, const long long *offsets, int nseq);
+int batch_plan(fv_ctx *ctx, const char *who, const std::vector<int> &lengths, int n_split, int mode, fv::Plan &plan);
+// the passes of a plan this rank runs (all of them on a context without a partition), generation by generation;
+// most: the size of the largest generation
+std::vector<std::vector<fv::Pass>> deal_passes(const fv_ctx *ctx, const fv::Plan &plan, size_t *most = nullptr);
+// Decode epilogue of nseq sequences laid end to end (a single decode: nseq = 1, and its one extra branch, the
+// multi-rank all-gather + merge): paths / scores / counters to the host in one copy, one sync, statistics.  A sequence
+// whose path holds -1 reports FV_ERR_NO_PRED (beam: FV_WARN_BEAM_MISS) in status_out; the return value is the most
+// negative status, else the largest.
+int finish_decode(fv_ctx *ctx, const fv::Plan &plan, const long long *offsets, int nseq, int *path_out, float *score_out,
+                  int *status_out, clk::time_point t0, size_t nprof, bool beam);
 int drained(fv_ctx *ctx, int rc);
 // decode prologue, before any admission check: chooses what the decode reads its emission term from.  ob != NULL: the
 // model's log B.  ob == NULL: the T rows fv_set_emissions staged (FV_ERR_ARG if there are fewer), and ob is pointed at
