@@ -84,6 +84,19 @@ int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed, int nscores, Wants 
     return 0;
 }
 
+int ensure_flat_workspace(fv_ctx *ctx, int T, size_t passes, long long arg_rows, int chain_len)
+{
+    Wants w;
+    const size_t want_rows = passes * 2 * (size_t)ctx->nrows;
+    const bool rows_grow = want_rows > ctx->d_rows.n;
+    w.add(ctx->d_rows, want_rows); w.add(ctx->d_snap, (size_t)T); w.add(ctx->d_flat_bp, (size_t)std::max(arg_rows, 1ll) * ctx->K);
+    w.add(ctx->d_chain, (size_t)std::max(chain_len, 1)); w.add(ctx->d_flat, std::max(passes, (size_t)1));
+    w.what = "flat generations workspace"; w.dominant = "private arg rows " + std::to_string(4ull * (unsigned long long)arg_rows * ctx->K);
+    if (int rc = grant(ctx, w, true)) return rc;
+    if (rows_grow) FV_HIP(hipMemsetAsync(ctx->d_rows.p, 0, want_rows * sizeof(float), ctx->stream));   // row pads stay zero
+    return 0;
+}
+
 // the result block: [counters | nscore scores, padded to `head` | the answers of all sequences, or the gathered answers]
 __global__ void pack_result(const unsigned long long *counters, const float *score, int nscore, size_t head, const int *ans,
                             size_t nans, int *out)
@@ -215,6 +228,10 @@ static int read_stats(fv_ctx *ctx, const unsigned long long *counters, clk::time
     st.beam_list_long = (long long)counters[12];
     st.beam_list_entries = (long long)counters[13];
     st.beam_chain_cuts = (long long)counters[14];
+    if (counters[fvk::FLAT_COUNTER]) {               // the resolver of a flat decode met a generation it could not commit
+        st.flat_first_miss = (int)(counters[fvk::FLAT_COUNTER] >> 32);
+        st.flat_missed = (int)(counters[fvk::FLAT_COUNTER] & 0xffffffffull);
+    }
     if (counters[5]) { ctx->detail = "heap replay: producer/consumer hand-shake timed out"; return FV_ERR_DEVICE; }
     st.device_bytes = (long long)fvi::device_bytes(ctx);
     st.ranks = ctx->nranks;
@@ -923,6 +940,13 @@ extern "C" int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, i
     return FV_OK;
 }
 
+extern "C" int fv_test_flat_poison(fv_ctx *ctx, int t)
+{
+    if (!ctx || t < -1) return FV_ERR_ARG;
+    ctx->flat_poison = t;
+    return FV_OK;
+}
+
 extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
 {
     if (!ctx) return FV_ERR_ARG;
@@ -942,6 +966,9 @@ extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
         ctx->opt_max_batch = (int)value; return FV_OK;
     case FV_OPT_PROFILE:
         ctx->opt_profile = value ? 1 : 0; return FV_OK;
+    case FV_OPT_FLAT_GENERATIONS:
+        if (value < 0 || value > 2) return FV_ERR_ARG;
+        ctx->opt_flat = (int)value; return FV_OK;
     case FV_OPT_SEL_MARGIN:
         if (value < 0 || value > 100000) return FV_ERR_ARG;
         ctx->opt_sel_margin = (float)value * 1e-3f; return FV_OK;

@@ -580,6 +580,195 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
     return 0;
 }
 
+// FV_OPT_FLAT_GENERATIONS — the right-hand passes of ALL generations as one independent set.
+//
+// run_generation_full orders the generations because generation g + 1 reads Ans[L-1] and Ans[R] from generation g's
+// back-track.  Those two states are, in practice, the ones the whole-sequence chain already holds there, so after
+// generation 0 every right-hand pass is started from a snapshot S of that chain: one init_rows, the step launches of all
+// passes dealt to the streams by length (a pass is at most T / 4 steps long: 31 dependent lock-steps at cfg2 instead of
+// 57), one back-track launch into per-pass chain slots, and a one-workgroup resolver that commits the chains generation
+// by generation while S agrees with the committed answers.  A pass is a deterministic function of (L, R, start state,
+// end state, observations): where the resolver commits, every bit is the generation-by-generation result; where it
+// stops (counter FLAT_COUNTER), decode_full_impl runs the remaining generations the old way.
+constexpr int FLAT_STREAMS = 3, FLAT_CAP = 4;      // today's winning form of a forked generation: batches of four, three streams
+// auto: from the smallest measured K at which the flat form wins, and up to the longest measured T at which it does — long
+// sequences keep their launch slots full generation by generation, have nothing to gain, and the more passes a decode
+// has the likelier one of them mis-speculates (cfg3, T = 4096: 2 of 4095, which costs the whole fall-back)
+constexpr int FLAT_AUTO_MIN_K = 512, FLAT_AUTO_MAX_T = 1024;
+
+// the batch size and stream count run_generation_full would take for a forked right-hand generation of this kernel
+// (maxlen: steps of the longest right-hand pass, nlong: right-hand passes of more than one step)
+void flat_shape(const fv_ctx *ctx, int kernel, int maxlen, int nlong, int &cap, int &nstreams)
+{
+    const bool slabbed = (kernel == FV_KERNEL_F64_STREAM || kernel == FV_KERNEL_Q16_REFINE) && !ctx->full_ok;
+    cap = std::max(1, std::min(ctx->opt_max_batch, slabbed ? 4 : max_batch_for(ctx->nrows, !ctx->full_ok)));
+    if (kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64) cap = ctx->opt_max_batch;
+    const bool walk = kernel == FV_KERNEL_SPARSE_Q16 || kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64;
+    const bool fork = ((kernel == FV_KERNEL_U16_REFINE && ctx->u16_ok) || (walk && maxlen >= 64)) && !(ctx->opt_debug & 262144) && nlong > FLAT_CAP;
+    nstreams = fork ? FLAT_STREAMS : 1;
+    if (fork) cap = std::min(cap, FLAT_CAP);
+}
+
+int run_flat_full(fv_ctx *ctx, int kernel, int T)
+{
+    const fv::FlatPlan &fp = ctx->flat_plan;
+    const int K = ctx->K, np = (int)fp.passes.size(), nstreams = fp.nstreams;
+    const bool two = nstreams > 1;
+    hipStream_t streams[FLAT_STREAMS] = { ctx->stream, ctx->aux[0], ctx->aux[1] };
+    auto row = [&](int i, int parity) { return ctx->d_rows.p + (size_t)i * 2 * ctx->nrows + (size_t)parity * ctx->nrows; };
+    auto arg_rows = [&](const fv::FlatPass &p) { return p.arg_row < 0 ? ctx->d_bp.p + (size_t)(p.L + 1) * K : ctx->d_flat_bp.p + (size_t)p.arg_row * K; };
+    // pass table (kept on the device across decodes of one plan)
+    if (ctx->flat_uploaded != ctx->d_flat.p) {
+        std::vector<fvk::FlatDesc> table((size_t)np);
+        for (int i = 0; i < np; ++i) table[(size_t)i] = fvk::FlatDesc{ fp.passes[i].L, fp.passes[i].R, fp.passes[i].generation, fp.passes[i].chain, fp.passes[i].arg_row };
+        FV_HIP(hipMemcpyAsync(ctx->d_flat.p, table.data(), (size_t)np * sizeof(fvk::FlatDesc), hipMemcpyHostToDevice, ctx->stream));
+        FV_HIP(hipStreamSynchronize(ctx->stream));       // (once per plan: `table` is gone after this scope)
+        ctx->flat_uploaded = ctx->d_flat.p;
+    }
+    hipLaunchKernelGGL(fvk::flat_snapshot, dim3((T + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_ans.p, ctx->d_snap.p, T, ctx->flat_poison, K);
+    FV_HIP(hipGetLastError());
+    // init rows of every pass, from S
+    for (int base = 0; base < np; base += fvk::PASS_CHUNK) {
+        fvk::PassChunk ch;
+        ch.n = std::min(fvk::PASS_CHUNK, np - base);
+        for (int q = 0; q < ch.n; ++q) ch.p[q] = fvk::PassDesc{ fp.passes[base + q].L, fp.passes[base + q].R, 0, 0, (long long)(base + q) * 2 * ctx->nrows };
+        if (ctx->csr)
+            hipLaunchKernelGGL(fvk::init_rows_csr, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->CRptr.p,
+                               ctx->CRcol.p, ctx->CRlog.p, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_snap.p, ctx->d_rows.p, K);
+        else
+            hipLaunchKernelGGL(fvk::init_rows, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->LA64.p, ctx->nrows,
+                               ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_snap.p, ctx->d_rows.p, K);
+        FV_HIP(hipGetLastError());
+    }
+    if (two) {
+        // (as run_generation_full: nothing may wait on the other queues while the serial generation 0 runs; polled)
+        if (!ctx->fork_active) {
+            hipError_t qe;
+            while ((qe = hipStreamQuery(ctx->stream)) == hipErrorNotReady) std::this_thread::yield();
+            FV_HIP(qe);
+        }
+        ctx->fork_active = true;
+        FV_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
+        for (int q = 1; q < nstreams; ++q) FV_HIP(hipStreamWaitEvent(streams[q], ctx->ev_fork, 0));
+    }
+    ctx->forked_batches = two;
+    struct Unfork { fv_ctx *c; ~Unfork() { c->forked_batches = false; c->lstream = nullptr; } } unfork{ ctx };
+    const bool col_last = !(ctx->opt_debug & 8);
+    // single-column last steps of a set of passes, on one stream
+    auto columns = [&](const std::vector<int> &which, hipStream_t st) -> int {
+        for (size_t base = 0; base < which.size(); base += fvk::COL_CHUNK) {
+            const int n = (int)std::min((size_t)fvk::COL_CHUNK, which.size() - base);
+            fvk::ColJob jobs[fvk::COL_CHUNK];
+            for (int q = 0; q < n; ++q) {
+                const int i = which[base + q];
+                const fv::FlatPass &p = fp.passes[i];
+                const int len = p.R - p.L;
+                jobs[q] = fvk::ColJob{ row(i, (len - 1) & 1), ctx->view.lb32 + (size_t)ctx->h_ob[p.R] * K, arg_rows(p) + (size_t)(len - 1) * K, p.R };
+            }
+            if (ctx->csr) {
+                fvk::CsrColArgs cc;
+                cc.ck = ctx->CSk.p; cc.c64 = ctx->CS64.p; cc.tile_off = ctx->CSoff.p; cc.tile_nwb = ctx->CSnwb.p;
+                cc.ans = ctx->d_snap.p; cc.K = K; cc.n = n;
+                std::copy(jobs, jobs + n, cc.p);
+                hipLaunchKernelGGL(fvk::last_column_csr, dim3(n), dim3(256), 0, st, cc);
+            } else {
+                fvk::ColArgs c;
+                c.LA64 = ctx->LA64.p; c.ans = ctx->d_snap.p; c.K = K; c.nrows = ctx->nrows; c.n = n;
+                std::copy(jobs, jobs + n, c.p);
+                hipLaunchKernelGGL(fvk::last_column, dim3(n), dim3(256), 0, st, c);
+            }
+            FV_HIP(hipGetLastError());
+            ctx->stats.column_steps += n;
+        }
+        return 0;
+    };
+    // Every stream walks its batches one after the other (a batch keeps its stream); the host deals its launches to the
+    // streams in turn, so that each queue always holds work.
+    struct Cursor { size_t b = 0; int s = 1; };
+    Cursor cur[FLAT_STREAMS];
+    for (bool any = true; any;) {
+        any = false;
+        for (int sid = 0; sid < nstreams; ++sid) {
+            Cursor &c = cur[sid];
+            const std::vector<int> &mine = fp.stream_batches[(size_t)sid];
+            if (c.b >= mine.size()) continue;
+            any = true;
+            const fv::FlatBatch &bt = fp.batches[(size_t)mine[c.b]];
+            const int s = c.s;
+            // passes are sorted longest first: those with more than s steps take a full step, those with exactly s finish
+            // with their single column (FV_OPT_DEBUG bit 3: with a full step as well)
+            int nb = 0;
+            std::vector<int> done;
+            fvk::TaskSlot slots[fvk::MAX_BATCH];
+            for (int i : bt.pass) {
+                const fv::FlatPass &p = fp.passes[i];
+                const int len = p.R - p.L;
+                if (len < s) continue;
+                if (len == s && col_last) { done.push_back(i); continue; }
+                slots[nb].t1_in = row(i, (s - 1) & 1);
+                slots[nb].t1_out = row(i, s & 1);
+                slots[nb].tmp_row = ctx->view.lb32 + (size_t)ctx->h_ob[p.L + s] * K;
+                slots[nb].tmp64_row = ctx->view.lb64 + (size_t)ctx->h_ob[p.L + s] * K;
+                slots[nb].bp_out = arg_rows(p) + (size_t)(s - 1) * K;
+                ++nb;
+            }
+            if (nb) {
+                ctx->lstream = streams[sid];
+                const int rc = launch_step_kernel(ctx, kernel, slots, nb, s & 1);
+                ctx->lstream = nullptr;
+                if (rc) return rc;
+                ctx->stats.step_launches += 1;
+                ctx->stats.task_steps += nb;
+            }
+            if (!done.empty()) { const int rc = columns(done, streams[sid]); if (rc) return rc; }
+            if (++c.s > bt.len) { ++c.b; c.s = 1; }
+        }
+    }
+    // the one-step passes: column jobs only
+    for (int sid = 0; sid < nstreams; ++sid) {
+        std::vector<int> ones;
+        for (int i = 0; i < np; ++i) if (fp.passes[i].batch < 0 && fp.passes[i].stream == sid) ones.push_back(i);
+        if (ones.empty()) continue;
+        if (col_last) { const int rc = columns(ones, streams[sid]); if (rc) return rc; continue; }
+        const size_t cap = (size_t)std::max(1, ctx->flat_key[2]);
+        for (size_t base = 0; base < ones.size(); base += cap) {      // FV_OPT_DEBUG bit 3: as full steps
+            const int nb = (int)std::min(cap, ones.size() - base);
+            fvk::TaskSlot slots[fvk::MAX_BATCH];
+            for (int q = 0; q < nb; ++q) {
+                const int i = ones[base + q];
+                const fv::FlatPass &p = fp.passes[i];
+                slots[q].t1_in = row(i, 0); slots[q].t1_out = row(i, 1);
+                slots[q].tmp_row = ctx->view.lb32 + (size_t)ctx->h_ob[p.R] * K;
+                slots[q].tmp64_row = ctx->view.lb64 + (size_t)ctx->h_ob[p.R] * K;
+                slots[q].bp_out = arg_rows(p);
+            }
+            ctx->lstream = streams[sid];
+            const int rc = launch_step_kernel(ctx, kernel, slots, nb, 1);
+            ctx->lstream = nullptr;
+            if (rc) return rc;
+            ctx->stats.step_launches += 1;
+            ctx->stats.task_steps += nb;
+        }
+    }
+    for (int q = 1; q < nstreams; ++q) {
+        FV_HIP(hipEventRecord(ctx->ev_join[q - 1], streams[q]));
+        FV_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join[q - 1], 0));
+    }
+    // every chain in one launch, then the resolver
+    hipLaunchKernelGGL(fvk::backtrack_flat, dim3(np), dim3(64), 0, ctx->stream, ctx->d_flat.p, ctx->d_bp.p, ctx->d_flat_bp.p, K,
+                       ctx->d_snap.p, ctx->d_chain.p);
+    FV_HIP(hipGetLastError());
+    fvk::FlatGens gens;
+    gens.ngen = (int)fp.gen_begin.size() - 1;
+    for (int g = 0; g <= gens.ngen; ++g) gens.begin[g] = fp.gen_begin[(size_t)g];
+    hipLaunchKernelGGL(fvk::flat_resolve, dim3(1), dim3(1024), 0, ctx->stream, ctx->d_flat.p, gens, ctx->d_snap.p, ctx->d_chain.p,
+                       ctx->d_ans.p, ctx->d_counters.p + fvk::FLAT_COUNTER);
+    FV_HIP(hipGetLastError());
+    ctx->stats.passes += np;
+    ctx->stats.flat_passes = np;
+    return 0;
+}
+
 }  // namespace
 
 namespace fvi {
@@ -776,17 +965,52 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
     if ((rc = prepare_full(ctx, ob, T, most, kernel))) return rc;
     start_full_stats(ctx, kernel, plan.generations());
 
+    // the flat form of the right-hand generations: one device, one sequence, the reference's task tree, nothing that
+    // brackets or captures single launches — and room for its workspace
+    bool flat = ctx->opt_flat != 0 && mode == FV_MODE_REFERENCE && plan.generations() >= 2 && plan.generations() - 1 <= fvk::FLAT_MAX_GENS &&
+                !ctx->group && !ctx->comm && ctx->nranks == 1 && !ctx->opt_profile && !ctx->vanilla && !(ctx->opt_debug & 64);
+    if (flat) {
+        int cap = 1, nstreams = 1, maxlen = 0, nlong = 0;
+        for (const fv::Pass &p : plan.passes)
+            if (!p.whole) { maxlen = std::max(maxlen, p.R - p.L); nlong += p.R - p.L > 1 ? 1 : 0; }
+        flat_shape(ctx, kernel, maxlen, nlong, cap, nstreams);
+        // auto: the measured form only — the packed 16-bit kernel's three streams, more than one right-hand generation
+        if (ctx->opt_flat == 1 && !(kernel == FV_KERNEL_U16_REFINE && nstreams > 1 && ctx->K >= FLAT_AUTO_MIN_K && T <= FLAT_AUTO_MAX_T && plan.generations() >= 3)) flat = false;
+        if (flat) {
+            const int key[4] = { T, n_split, cap, nstreams };
+            if (std::memcmp(key, ctx->flat_key, sizeof key) != 0) {
+                fv::build_flat(plan, cap, nstreams, ctx->flat_plan);
+                std::memcpy(ctx->flat_key, key, sizeof key);
+                ctx->flat_uploaded = nullptr;
+            }
+            const int wrc = fvi::ensure_flat_workspace(ctx, T, ctx->flat_plan.passes.size(), ctx->flat_plan.arg_rows, ctx->flat_plan.chain_len);
+            if (wrc == FV_ERR_NOMEM) { flat = false; ctx->detail.clear(); }
+            else if (wrc) return wrc;
+        }
+    }
+
     if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
     FV_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
     size_t nprof = 0;
     ctx->fork_active = false;
-    for (size_t g = 0; g < gens.size(); ++g) {
+    for (size_t g = 0; g < gens.size() && !(flat && g == 1); ++g) {
         ctx->stats.passes += (int)gens[g].size();
         if ((rc = run_generation_full(ctx, gens[g], kernel, nprof))) return rc;
         if (g == 0) FV_HIP(hipEventRecord(ctx->ev_top, ctx->stream));
     }
+    if (flat && (rc = run_flat_full(ctx, kernel, T))) return rc;
     ctx->close_stats((long long)ctx->K * ctx->K, ctx->K);
     const long long whole[2] = { 0, T };
+    rc = fvi::finish_decode(ctx, plan, whole, 1, path_out, score_out, nullptr, t0, nprof, false);
+    if (!flat || ctx->stats.flat_first_miss < 1 || rc == FV_ERR_DEVICE) return rc;
+    // a generation the resolver could not commit: the answers are exact through the one before it, and the decode goes on
+    // from there generation by generation (the one extra host round trip of the flat form)
+    ctx->fork_active = false;
+    for (size_t g = (size_t)ctx->stats.flat_first_miss; g < gens.size(); ++g) {
+        ctx->stats.passes += (int)gens[g].size();
+        if ((rc = run_generation_full(ctx, gens[g], kernel, nprof))) return rc;
+    }
+    ctx->close_stats((long long)ctx->K * ctx->K, ctx->K);
     return fvi::finish_decode(ctx, plan, whole, 1, path_out, score_out, nullptr, t0, nprof, false);
 }
 

@@ -114,6 +114,14 @@ struct fv_ctx {
     DevBuf<int> d_ob, d_ans, d_bp, d_gather;
     DevBuf<float> d_rows, d_score, d_ckpt;            // d_ckpt: kept score rows of fv_decode_checkpoint
     DevBuf<unsigned long long> d_counters;
+    // FV_OPT_FLAT_GENERATIONS (fv_full.hip, run_flat_full): snapshot S of the whole-sequence chain, the private arg rows of
+    // the generations >= 2, the chain of every right-hand pass and the pass table the back-track and the resolver read
+    DevBuf<int> d_snap, d_flat_bp, d_chain;
+    DevBuf<fvk::FlatDesc> d_flat;
+    fv::FlatPlan flat_plan;                   // the plan d_flat holds, kept across decodes of one (T, n_split, cap, streams)
+    int flat_key[4] = { 0, 0, 0, 0 };
+    const void *flat_uploaded = nullptr;      // d_flat.p at the upload (a grown buffer is filled again)
+    int flat_poison = -1;                     // fv_test_flat_poison
     // decode epilogue: path (or the gathered paths), score and counters are packed into one device block and come back
     // in ONE copy into pinned host memory (three small pageable copies cost ~15 us each)
     DevBuf<int> d_pack;
@@ -145,6 +153,7 @@ struct fv_ctx {
     int opt_kernel = FV_KERNEL_AUTO;
     int opt_max_batch = fvk::MAX_BATCH;
     int opt_profile = 0;
+    int opt_flat = 1;        // FV_OPT_FLAT_GENERATIONS: 0 off, 1 auto, 2 on
     int vanilla = 0;         // set for the duration of fv_decode_vanilla
     int opt_csr_mem = 0;     // FV_OPT_DEBUG bit 31: trellis_step_csr / trellis_step_csr_f64 read their score rows from memory at any K
     int opt_debug = 0;       // FV_OPT_DEBUG bits: 1 skip refine (timing only), 2 no reverse sweep, 4 alternate unroll, 8 full last step,
@@ -176,6 +185,7 @@ struct fv_ctx {
         stats.set_model_ms = model_ms; stats.set_emissions_ms = emis_ms; stats.emission_rows = rows;
         stats.kernel = kernel; stats.generations = generations;
         stats.table_bytes_per_step = table_bytes_per_step; stats.density = density_reported;
+        stats.flat_first_miss = -1;
     }
     // ... and of one whose launches are all queued: cells evaluated per task step and per column step, 4 B each
     void close_stats(long long cells_per_task_step, long long cells_per_column_step)
@@ -192,6 +202,7 @@ struct fv_ctx {
         f(CSk); f(CSq); f(CS64); f(CSoff); f(CSnwb); f(CRptr); f(CRcol); f(CRlog);
         f(E32); f(E64); f(d_emflags);
         f(d_ob); f(d_ans); f(d_bp); f(d_gather); f(d_rows); f(d_score); f(d_ckpt); f(d_counters); f(d_pack);
+        f(d_snap); f(d_flat_bp); f(d_chain); f(d_flat);
         f(d_hval); f(d_scores); f(d_slot_val); f(d_hstate); f(d_slot_state); f(d_flags); f(LA64R); f(LAQ16R); f(d_qaux);
         f(d_tie_list); f(d_cut); f(d_cand); f(d_cand_count); f(d_dupwin); f(d_doubt); f(d_doubt_count); f(d_needfull);
         f(d_seqof); f(d_passL); f(d_tie_count);
@@ -249,6 +260,9 @@ int grant(fv_ctx *ctx, const Wants &w, bool check);
 // the workspace every decode needs, for T observations, rows_needed passes in flight and nscores scores, added to what
 // the caller wants (the beam buffers).  nscores > 1: a batch decode, whose request is checked before it is granted.
 int ensure_workspace(fv_ctx *ctx, int T, size_t rows_needed, int nscores = 1, Wants w = {});
+// the extra workspace of a flat decode (score rows of `passes` passes, arg_rows private arg rows, the snapshot, the chains and
+// the pass table), checked against the free device memory before anything grows: FV_ERR_NOMEM leaves every buffer as it was
+int ensure_flat_workspace(fv_ctx *ctx, int T, size_t passes, long long arg_rows, int chain_len);
 // Admission of fv_decode_full_batch / fv_decode_beam_batch (`who`, for the detail text), in the steps the entry points
 // take in this order: arguments, offsets -> lengths, emission view and model; the symbols' range; the forest plan.
 int batch_lengths(fv_ctx *ctx, const char *who, const int *&ob, const long long *offsets, int nseq, int n_split, int mode,

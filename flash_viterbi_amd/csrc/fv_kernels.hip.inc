@@ -1823,38 +1823,107 @@ __global__ __launch_bounds__(256) void last_column_csr(const CsrColArgs args)
 // chunk's result stands only if the state it entered with equals the state the chunk above it — itself verified —
 // left with (the map is deterministic: equal at one time means equal from there on); the first chunk that fails
 // restarts from the verified state, and the others are walked again behind it.
-__global__ __launch_bounds__(64) void backtrack(const PassChunk ch, const int *bp, int K, int *ans)
+//
+// One pass [L, R] walked by one wave: bp is the arg row of time L + 1 (the row of time j at bp + (j - L - 1) * K), `end` the
+// state at time R, out[j - L] receives c[j] for j = L .. R-1.
+__device__ __forceinline__ void backtrack_walk(int L, int R, const int *bp, int K, int end, int *out)
 {
-    const PassDesc p = ch.p[blockIdx.x];
-    const int lane = threadIdx.x, len = p.R - p.L;
-    auto hop = [&](int st, int j) { return st >= 0 ? bp[(size_t)j * K + st] : -1; };       // state at time j -> state at time j - 1
+    const int lane = threadIdx.x, len = R - L;
+    auto hop = [&](int st, int j) { return st >= 0 ? bp[(size_t)(j - L - 1) * K + st] : -1; };       // state at time j -> state at time j - 1
     if (len < BT_MIN_PARALLEL) {
         if (lane != 0) return;
-        int st = ans[p.R];
-        for (int j = p.R; j > p.L; --j) { st = hop(st, j); ans[j - 1] = st; }
+        int st = end;
+        for (int j = R; j > L; --j) { st = hop(st, j); out[j - 1 - L] = st; }
         return;
     }
     const int cs = (len + 63) / 64;                      // times per chunk; chunk c: from time top(c) down to top(c + 1)
-    auto top = [&](int c) { return max(p.R - c * cs, p.L); };
-    int base = 0, exact = ans[p.R];                      // chunks below `base` are final; `exact` = state at time top(base)
-    while (base < 64 && top(base) > p.L) {               // (wave-uniform)
+    auto top = [&](int c) { return max(R - c * cs, L); };
+    int base = 0, exact = end;                           // chunks below `base` are final; `exact` = state at time top(base)
+    while (base < 64 && top(base) > L) {                 // (wave-uniform)
         int x = -2, y = -2;                              // state this lane entered its chunk with / left it with
-        if (lane >= base && top(lane) > p.L) {
+        if (lane >= base && top(lane) > L) {
             const int t_hi = top(lane), t_lo = top(lane + 1);
             int t = min(top(base), t_hi + BT_WARMUP), st = exact;     // at top(base) `exact` is the true state; above the chunk it is a guess
             for (; t > t_hi; --t) st = hop(st, t);
             x = st;
-            for (; t > t_lo; --t) { st = hop(st, t); ans[t - 1] = st; }
+            for (; t > t_lo; --t) { st = hop(st, t); out[t - 1 - L] = st; }
             y = st;
         }
         const int y_above = __shfl_up(y, 1);
         // lanes whose walk started at top(base) started from the true state: consistent by construction
-        const bool ok = lane <= base || top(lane) <= p.L || min(top(base), top(lane) + BT_WARMUP) == top(base) || x == y_above;
+        const bool ok = lane <= base || top(lane) <= L || min(top(base), top(lane) + BT_WARMUP) == top(base) || x == y_above;
         const unsigned long long bad = ~__ballot(ok);
         if (!bad) break;
         const int f = __ffsll((long long)bad) - 1;       // first chunk that entered with the wrong state: everything above it is final
         exact = __shfl(y, f - 1);
         base = f;
+    }
+}
+
+__global__ __launch_bounds__(64) void backtrack(const PassChunk ch, const int *bp, int K, int *ans)
+{
+    const PassDesc p = ch.p[blockIdx.x];
+    backtrack_walk(p.L, p.R, bp + (size_t)(p.L + 1) * K, K, ans[p.R], ans + p.L);
+}
+
+// ---------------------------------------------------------------- flat generations (FV_OPT_FLAT_GENERATIONS)
+
+// S = the answer array after the whole-sequence pass's back-track: the states every right-hand pass of the flat set is
+// conditioned on.  poison >= 0 (fv_test_flat_poison): S[poison] is replaced by another state.
+__global__ void flat_snapshot(const int *ans, int *S, int T, int poison, int K)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T) return;
+    const int s = ans[i];
+    S[i] = i == poison ? (s + 1) % K : s;
+}
+
+// The back-track of every pass of the flat set in one launch, a wave each: arg rows at the pass's private rows (or, for a
+// generation-1 pass, at its own times of the by-time array), end state from S, chain into the pass's slot.
+__global__ __launch_bounds__(64) void backtrack_flat(const FlatDesc *desc, const int *bp, const int *flat_bp, int K, const int *S, int *chains)
+{
+    const FlatDesc p = desc[blockIdx.x];
+    const int *rows = p.arg_row < 0 ? bp + (size_t)(p.L + 1) * K : flat_bp + (size_t)p.arg_row * K;
+    backtrack_walk(p.L, p.R, rows, K, S[p.R], chains + p.chain);
+}
+
+// The resolver, one workgroup.  Generation by generation: a pass ran from S[L-1] and S[R]; the generation-by-generation
+// decode would have run it from the answers the generations before it left there.  While the two agree for every pass of
+// a generation, its chains are what that decode produces and are committed to ans[L..R-1].  At the first generation where
+// a pass disagrees nothing more is committed: counter = generation << 32 | disagreeing passes, and ans is exact through
+// the generation before.
+__global__ __launch_bounds__(1024) void flat_resolve(const FlatDesc *desc, const FlatGens gens, const int *S, const int *chains, int *ans,
+                                                     unsigned long long *counter)
+{
+    __shared__ int miss;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    for (int g = 0; g < gens.ngen; ++g) {
+        const int b0 = gens.begin[g], b1 = gens.begin[g + 1];
+        if (threadIdx.x == 0) miss = 0;
+        __syncthreads();
+        int m = 0;
+        for (int i = b0 + threadIdx.x; i < b1; i += blockDim.x) {
+            const FlatDesc p = desc[i];
+            if ((p.L > 0 && S[p.L - 1] != ans[p.L - 1]) || S[p.R] != ans[p.R]) ++m;
+        }
+        if (m) atomicAdd(&miss, m);
+        __syncthreads();
+        if (miss) {                                      // workgroup-uniform
+            if (threadIdx.x == 0) *counter = ((unsigned long long)(g + 1) << 32) | (unsigned int)miss;
+            return;
+        }
+        if (b1 - b0 >= (int)blockDim.x) {                // many short passes: a thread each
+            for (int i = b0 + threadIdx.x; i < b1; i += blockDim.x) {
+                const FlatDesc p = desc[i];
+                for (int j = p.L; j < p.R; ++j) ans[j] = chains[p.chain + j - p.L];
+            }
+        } else {                                         // few long ones: a wave each
+            for (int i = b0 + wave; i < b1; i += nwaves) {
+                const FlatDesc p = desc[i];
+                for (int j = p.L + lane; j < p.R; j += 64) ans[j] = chains[p.chain + j - p.L];
+            }
+        }
+        __syncthreads();                                 // the next generation's check reads these answers
     }
 }
 

@@ -26,6 +26,11 @@ constexpr int BT_WARMUP = 32, BT_MIN_PARALLEL = 128;
 struct PassDesc { int L, R, from_pi, whole; long long row_off; };   // row_off: float offset of the pass's 2 score rows
 constexpr int PASS_CHUNK = 64;
 struct PassChunk { int n; PassDesc p[PASS_CHUNK]; };
+// FV_OPT_FLAT_GENERATIONS: one right-hand pass of the flat set as the back-track and the resolver see it (fv_schedule.h, FlatPass)
+struct FlatDesc { int L, R, generation, chain; long long arg_row; };
+constexpr int FLAT_MAX_GENS = 40;          // (a generation halves the pass length: T < 2^31 has at most 32)
+struct FlatGens { int ngen; int begin[FLAT_MAX_GENS + 1]; };   // passes [begin[g], begin[g + 1]) are generation g + 1
+constexpr int FLAT_COUNTER = 15;           // device statistics word of the resolver: first-miss generation << 32 | missed passes
 
 // LDS of one trellis_step / trellis_step_u16 workgroup (score rows + reduction scratch)
 template <int NB>

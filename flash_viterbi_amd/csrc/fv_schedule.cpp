@@ -126,7 +126,66 @@ int build_forest(const int *lengths, int nseq, int n_split, int mode, Plan &plan
     return 0;
 }
 
+void build_flat(const Plan &plan, int cap, int nstreams, FlatPlan &flat)
+{
+    flat = FlatPlan();
+    cap = std::max(cap, 1);
+    flat.nstreams = std::max(nstreams, 1);
+    flat.gen_begin.push_back(0);
+    for (const Pass &p : plan.passes) {
+        if (p.whole || p.generation < 1) continue;
+        while ((int)flat.gen_begin.size() < p.generation) flat.gen_begin.push_back((int)flat.passes.size());
+        FlatPass f{ p.L, p.R, p.generation, -1, flat.chain_len, -1, 0 };
+        if (p.generation > 1) { f.arg_row = flat.arg_rows; flat.arg_rows += p.R - p.L; }
+        flat.chain_len += p.R - p.L;
+        flat.passes.push_back(f);
+    }
+    flat.gen_begin.push_back((int)flat.passes.size());
+    // batches: the passes by length, longest first (stable: generation order within a length), `cap` at a time — the
+    // passes of a batch that are still running at a lock-step are a prefix of it
+    std::vector<int> order;
+    for (int i = 0; i < (int)flat.passes.size(); ++i)
+        if (flat.passes[i].R - flat.passes[i].L > 1) order.push_back(i);
+    auto len = [&](int i) { return flat.passes[i].R - flat.passes[i].L; };
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len(a) > len(b); });
+    for (size_t q = 0; q < order.size(); ++q) {
+        if (flat.batches.empty() || (int)flat.batches.back().pass.size() == cap)
+            flat.batches.push_back(FlatBatch{ {}, len(order[q]), 0 });
+        flat.batches.back().pass.push_back(order[q]);
+    }
+    // deal: every batch to the stream with the fewest step launches so far (a batch whose longest pass has l steps takes l - 1 step launches)
+    std::vector<long long> load((size_t)flat.nstreams, 0);
+    flat.stream_batches.assign((size_t)flat.nstreams, {});
+    auto least = [&]() { return (int)(std::min_element(load.begin(), load.end()) - load.begin()); };
+    for (int b = 0; b < (int)flat.batches.size(); ++b) {
+        const int s = least();
+        flat.batches[b].stream = s;
+        flat.stream_batches[(size_t)s].push_back(b);
+        load[(size_t)s] += flat.batches[b].len - 1;
+        for (int i : flat.batches[b].pass) { flat.passes[i].batch = b; flat.passes[i].stream = s; }
+    }
+    const int s1 = least();
+    for (FlatPass &f : flat.passes) if (f.batch < 0) f.stream = s1;
+}
+
 }  // namespace fv
+
+extern "C" int fv_plan_flat(int T, int n_split, int batch_cap, int nstreams, fv_flat_info *out, int cap)
+{
+    if (batch_cap < 1 || nstreams < 1) return FV_ERR_ARG;
+    fv::Plan plan;
+    int rc = fv::build_plan(T, n_split, FV_MODE_REFERENCE, 1, plan);
+    if (rc) return rc;
+    fv::FlatPlan flat;
+    fv::build_flat(plan, batch_cap, nstreams, flat);
+    const int n = (int)flat.passes.size();
+    for (int i = 0; i < n && i < cap && out; ++i) {
+        const fv::FlatPass &f = flat.passes[i];
+        out[i].L = f.L; out[i].R = f.R; out[i].generation = f.generation; out[i].batch = f.batch; out[i].stream = f.stream;
+        out[i].chain = f.chain; out[i].arg_row = f.arg_row;
+    }
+    return n;
+}
 
 extern "C" int fv_plan_passes_batch(const int *lengths, int nseq, int n_split, int mode, fv_pass_info *out, int cap)
 {

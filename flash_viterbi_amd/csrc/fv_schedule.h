@@ -37,4 +37,32 @@ int build_plan(int T, int n_split, int mode, int nranks, Plan &plan);
 // the sequence build_plan refused.
 int build_forest(const int *lengths, int nseq, int n_split, int mode, Plan &plan, int *bad_seq);
 
+// The right-hand passes of ALL generations of a one-rank plan as one independent set (fv_full.hip, run_flat_full): every
+// pass takes its two conditioning states from the whole-sequence chain instead of from the generation before it, so
+// nothing orders the passes but the streams they are dealt to.
+struct FlatPass {
+    int L, R, generation;
+    long long arg_row;   // first of its R - L private arg rows (passes of different generations overlap in time); -1: a
+                         // generation-1 pass, which keeps the rows of its own times in the by-time array
+    int chain;           // first of its R - L chain entries c[L..R-1]
+    int batch;           // index into FlatPlan::batches; -1: a one-step pass (its only step is the single-column one)
+    int stream;          // stream that carries every launch of the pass
+};
+struct FlatBatch {
+    std::vector<int> pass;   // indices into FlatPlan::passes, longest first, at most `cap` of them
+    int len, stream;         // len: steps of the longest
+};
+struct FlatPlan {
+    std::vector<FlatPass> passes;     // in the order of Plan::passes (sorted by generation), the whole-sequence pass left out
+    std::vector<int> gen_begin;       // passes[gen_begin[g - 1] .. gen_begin[g]) is generation g >= 1
+    std::vector<FlatBatch> batches;   // longest first
+    std::vector<std::vector<int>> stream_batches;   // per stream: its batches in launch order
+    long long arg_rows = 0;           // private arg rows in all
+    int chain_len = 0;                // chain entries in all
+    int nstreams = 1;
+};
+// cap: most passes per batch; nstreams: streams the batches are dealt to, longest batch first to the stream with the
+// least step launches so far (equal sums of length, none idles); one-step passes go to the stream with the least.
+void build_flat(const Plan &plan, int cap, int nstreams, FlatPlan &flat);
+
 }  // namespace fv

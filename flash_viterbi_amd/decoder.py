@@ -18,6 +18,8 @@ KERNEL_U16_REFINE = 6
 KERNEL_SPARSE_CSR = 7                  # reported by stats()["kernel"] for a model set by set_model_sparse; never chosen
 KERNEL_CSR_F64 = 8                     # models set by set_model_sparse: the float64 walk (entries above 1, emission scores above 0)
 OPT_KERNEL, OPT_MAX_BATCH, OPT_PROFILE, OPT_SEL_MARGIN, OPT_DEBUG = 1, 2, 3, 4, 100
+OPT_FLAT_GENERATIONS = 5               # 0 off, 1 auto (default), 2 on: all right-hand generations at once from the whole-sequence chain
+FLAT_OFF, FLAT_AUTO, FLAT_ON = 0, 1, 2
 DEBUG_TIMING_ONLY = (1 << 0) | (1 << 4) | (1 << 5) | (1 << 11) | (1 << 12)      # refused by the shipped library
 DEBUG_BATCH_GEN0_SERIAL = 1 << 28      # decode_full_batch: the whole-sequence passes on one stream (speed only)
 DEBUG_BEAM_BATCH_GEN0_OTHER = 1 << 29  # decode_beam_batch: the whole-sequence passes in the launch form that is not the default (speed only)
@@ -49,10 +51,17 @@ class Stats(ctypes.Structure):
                 ("beam_spec_steps", ctypes.c_longlong), ("beam_reach_events", ctypes.c_longlong),
                 ("beam_list_short", ctypes.c_longlong), ("beam_list_long", ctypes.c_longlong), ("beam_list_entries", ctypes.c_longlong),
                 ("beam_chain_cuts", ctypes.c_longlong),
+                ("flat_passes", ctypes.c_int), ("flat_missed", ctypes.c_int), ("flat_first_miss", ctypes.c_int),
                 ("set_emissions_ms", ctypes.c_double), ("emission_rows", ctypes.c_longlong)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FlatInfo(ctypes.Structure):
+    """fv_flat_info: one right-hand pass of the flat schedule."""
+    _fields_ = [("L", ctypes.c_int), ("R", ctypes.c_int), ("generation", ctypes.c_int), ("batch", ctypes.c_int),
+                ("stream", ctypes.c_int), ("chain", ctypes.c_int), ("arg_row", ctypes.c_longlong)]
 
 
 class PassInfo(ctypes.Structure):
@@ -64,10 +73,10 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_last_stats", "fv_strerror", "fv_last_error_detail", "fv_reference_memory_bytes",
            "fv_comm_unique_id", "fv_comm_init", "fv_plan_passes", "fv_merge_paths", "fv_set_partition",
            "fv_create_multi", "fv_device_count", "fv_decode_full_batch", "fv_plan_passes_batch", "fv_decode_beam_batch",
-           "fv_set_model_sparse", "fv_set_emissions", "fv_clear_emissions"]
+           "fv_set_model_sparse", "fv_set_emissions", "fv_clear_emissions", "fv_plan_flat"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select", "fv_test_device_alloc", "fv_test_device_free",
-                "fv_test_stage_emissions_ms"]
+                "fv_test_stage_emissions_ms", "fv_test_flat_poison"]
 TIE_TAG = 1 << 30
 # FV_TS_*: select-kernel instantiations reported by test_beam_select
 TS_BITS = {"topb_select<4,listed>": 1 << 0, "topb_select<4,derived>": 1 << 1, "topb_select<16,listed>": 1 << 2,
@@ -143,6 +152,8 @@ def load_library():
     L.fv_set_partition.argtypes = [vp, ci, ci]
     L.fv_plan_passes.argtypes = [ci, ci, ci, ci, ctypes.POINTER(PassInfo), ci]
     L.fv_merge_paths.argtypes = [ci, ci, ci, vp, vp]
+    L.fv_plan_flat.argtypes = [ci, ci, ci, ci, ctypes.POINTER(FlatInfo), ci]
+    L.fv_test_flat_poison.argtypes = [vp, ci]
     L.fv_test_forward.argtypes = [vp, vp, ci, ctypes.POINTER(ForwardPass), ci, vp, vp, ctypes.POINTER(ctypes.c_ulonglong)]
     cf = ctypes.c_float
     L.fv_test_beam_step.argtypes = [vp, ci, ctypes.POINTER(BeamSet), ci, vp, ci, cf, cf, ci, vp, vp, vp, ctypes.POINTER(ci),
@@ -169,6 +180,17 @@ def plan_passes(T, n_split, mode=MODE_REFERENCE, nranks=1):
     buf = (PassInfo * n)()
     L.fv_plan_passes(T, n_split, mode, nranks, buf, n)
     return [(p.L, p.R, p.generation, p.owner) for p in buf]
+
+
+def plan_flat(T, n_split, batch_cap=4, nstreams=3):
+    """Flat schedule of OPT_FLAT_GENERATIONS (no GPU): list of dicts L, R, generation, batch, stream, chain, arg_row."""
+    L = load_library()
+    n = L.fv_plan_flat(T, n_split, batch_cap, nstreams, None, 0)
+    if n < 0:
+        raise FlashVitError(n)
+    buf = (FlatInfo * max(n, 1))()
+    L.fv_plan_flat(T, n_split, batch_cap, nstreams, buf, n)
+    return [{k: getattr(buf[i], k) for k, _ in FlatInfo._fields_} for i in range(n)]
 
 
 def plan_passes_batch(lengths, n_split, mode=MODE_REFERENCE):
@@ -395,6 +417,10 @@ class FlashViterbi:
         score = ctypes.c_float(0)
         rc = self._check(self._L.fv_decode_checkpoint(self._h, ptr, T, step, _p(path), ctypes.byref(score)))
         return path, np.float32(score.value), rc
+
+    def test_flat_poison(self, t):
+        """fv_test_flat_poison: position t of the snapshot a flat decode speculates from holds a wrong state (t = -1 clears)."""
+        self._check(self._L.fv_test_flat_poison(self._h, int(t)))
 
     def test_device_alloc(self, host_array):
         """fv_test_device_alloc: a device copy of a numpy array on this context's GPU; returns the pointer as an int

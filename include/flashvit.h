@@ -60,6 +60,19 @@ enum {
     FV_OPT_SEL_MARGIN = 4,  /* FLASH-BS: margin, in 1/1000 of the beam spread (max - cut value), below the extrapolated cut value
                                from which the step kernels collect the next select's candidates (default 300; the margin then follows the
                                length of the lists it produces); speed only */
+    FV_OPT_FLAT_GENERATIONS = 5, /* fv_decode_full, FV_MODE_REFERENCE: 0 off, 1 auto (default), 2 on.  On: after the whole-sequence
+                               pass the right-hand passes of ALL generations run as one independent set, each conditioned on the
+                               states the whole-sequence chain holds at L-1 and R instead of the answers of the generation before;
+                               a one-workgroup resolver then commits the chains generation by generation for as long as those
+                               states equal the committed answers, and from the first generation where one differs the decode
+                               finishes generation by generation as with 0.  A pass is a function of (L, R,
+                               start state, end state, observations), so the result is bit for bit that of 0: speed only.  Auto:
+                               on for the packed 16-bit kernel's three-stream form when K >= 512, T <= 1024 and the plan has more than one
+                               right-hand generation (where it was measured to win; longer sequences gain little and pay a whole
+                               fall-back for one missed pass).  Never taken (today's path instead) by multi-rank, partitioned or multi-device contexts,
+                               fv_decode_full_batch, FV_OPT_PROFILE, FV_MODE_SINGLE_PASS, fv_decode_vanilla / _checkpoint,
+                               FV_OPT_DEBUG bit 6, or when the device has no room for the extra workspace (score rows of all
+                               right-hand passes, private arg rows of the generations >= 2, the snapshot and the chains) */
     FV_OPT_DEBUG = 100,     /* UNSTABLE: kernel-tuning switches (a bit mask) that select alternative forms of a kernel or of the
                                launch schedule.  Every bit the library accepts is speed-only — the parity tests run each
                                alternative against the same goldens (tests/test_boundary.py checks that no accepted value
@@ -155,6 +168,12 @@ typedef struct {
     long long beam_list_entries;/* FLASH-BS: total length of the candidate lists the selects ran on (beam_cand_selects of them) */
     long long beam_chain_cuts;  /* FLASH-BS: runs of undecided steps that were decided only back to a step whose replay provably does not
                                    depend on the undecided columns (instead of back to the last step with exact scores) */
+    int flat_passes;            /* FV_OPT_FLAT_GENERATIONS: right-hand passes run speculatively from the whole-sequence chain (0: the decode
+                                   ran generation by generation) */
+    int flat_missed;            /* ... passes of the first generation with a miss whose conditioning states differed from the committed
+                                   answers (0: every chain was committed) */
+    int flat_first_miss;        /* ... that generation (-1: none); the generations from it on were run again generation by generation, and
+                                   the other statistics cover both parts */
     double set_emissions_ms;    /* host wall time of the last fv_set_emissions (copy, staging kernel, its one sync), 0 after a refused one; kept across decodes */
     long long emission_rows;    /* rows staged by fv_set_emissions (0: none); kept across decodes */
 } fv_stats;
@@ -337,6 +356,14 @@ int fv_merge_paths(int T, int n_split, int nranks, const int *gathered, int *pat
  * the number of passes (or <0).  Pass 0 is always the whole-sequence pass. */
 typedef struct { int L, R, generation, owner; } fv_pass_info;
 int fv_plan_passes(int T, int n_split, int mode, int nranks, fv_pass_info *out, int cap);
+
+/* The flat schedule of FV_OPT_FLAT_GENERATIONS for one rank (mode FV_MODE_REFERENCE): every pass of generation >= 1, in the
+ * order of fv_plan_passes, dealt in batches of at most batch_cap passes of one length to nstreams streams.  arg_row: the
+ * first of the pass's R - L private arg rows (-1: a generation-1 pass, which writes the rows of its own times); chain: the
+ * first of its R - L chain entries; batch: -1 for a one-step pass (a single-column job only).  Returns the number of
+ * passes (or <0). */
+typedef struct { int L, R, generation, batch, stream, chain; long long arg_row; } fv_flat_info;
+int fv_plan_flat(int T, int n_split, int batch_cap, int nstreams, fv_flat_info *out, int cap);
 
 /* The schedule of fv_decode_full_batch: the passes of all sequences in launch order (sorted by generation), L and R
  * as positions in the concatenated time axis (sequence s starts at lengths[0] + .. + lengths[s-1]), `owner` = index

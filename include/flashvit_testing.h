@@ -37,6 +37,12 @@ int fv_test_forward(fv_ctx *ctx, const int *ob, int T, const fv_test_pass *passe
                     float *rows_out, int *bp_out, unsigned long long *variants_out);
 /* (ob == NULL: the passes read the rows staged by fv_set_emissions, row t for time t, as the decodes do; T <= staged rows.) */
 
+/* FV_OPT_FLAT_GENERATIONS: a deterministic mis-speculation.  Before the right-hand passes of a flat decode start, entry t of
+ * the snapshot S of the whole-sequence chain is replaced by (S[t] + 1) % K, so every pass that reads position t (as its
+ * L - 1 or its R) runs from a wrong state, the resolver reports its generation, and the decode finishes generation by
+ * generation from there.  Results never change.  t = -1 clears; the setting stays until cleared. */
+int fv_test_flat_poison(fv_ctx *ctx, int t);
+
 /* Device memory for tests of the calls that take a device pointer (fv_set_emissions): the test process has no HIP
  * runtime of its own to allocate with.  `bytes` of device memory on the context's GPU in *out, filled from host_src
  * unless that is NULL; the copy is complete on return.  The free hook waits for nothing but the device. */
