@@ -530,11 +530,13 @@ static void drop_model(fv_ctx *ctx, bool keep_dense)
     ctx->K = 0; ctx->M = 0; ctx->nrows = 0; ctx->full_ok = false; ctx->u16_ok = false; ctx->laq16_ready = false;
     ctx->rowq_ready = false; ctx->beam_q16_ready = false; ctx->csr = false;
     ctx->emis_rows = 0; ctx->emis_positive = false;      // staged emission scores belong to the model they were staged under
+    ctx->emis_P = 0;                                     // ... and so does the emission map
     (void)hipStreamSynchronize(ctx->stream);
     ctx->LA64R.release(); ctx->LAQ16R.release();
     ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release();
     ctx->CSk.release(); ctx->CSq.release(); ctx->CS64.release(); ctx->CSoff.release(); ctx->CSnwb.release();
     ctx->CRptr.release(); ctx->CRcol.release(); ctx->CRlog.release();
+    ctx->EMap.release();
     if (!keep_dense) { ctx->LA32.release(); ctx->LA16.release(); ctx->LAQ16.release(); ctx->LA64.release(); }
 }
 
@@ -780,13 +782,17 @@ extern "C" int fv_set_model(fv_ctx *ctx, const float *A, const float *B, const f
 
 namespace fvi {
 
+constexpr size_t emis_elem_size[4] = { 4, 8, 2, 2 };      // by FV_EMIS_LOG_F32, _F64, _F16, _BF16
+inline bool emis_dtype_ok(int dtype) { return dtype >= FV_EMIS_LOG_F32 && dtype <= FV_EMIS_LOG_BF16; }
+
 // fv_set_emissions on one device.  A block the kernel cannot read where it lies (host memory; a multi-device context,
 // whose members each take a copy) goes into a raw device buffer first, released before the call returns.
 static int stage_emissions_on(fv_ctx *ctx, const void *scores, int dtype, int T, long long ld, bool in_place)
 {
     FV_HIP(hipSetDevice(ctx->device));
-    const size_t K = (size_t)ctx->K, esz = dtype == FV_EMIS_LOG_F64 ? 8 : 4, cells = (size_t)T * K;
-    const size_t raw_bytes = in_place ? 0 : ((size_t)(T - 1) * (size_t)ld + K) * esz;      // (the last row ends at its K-th element)
+    const size_t K = (size_t)ctx->K, esz = emis_elem_size[dtype], cells = (size_t)T * K;
+    const size_t width = ctx->emis_P ? (size_t)ctx->emis_P : K;                            // scores of a row: P through a map
+    const size_t raw_bytes = in_place ? 0 : ((size_t)(T - 1) * (size_t)ld + width) * esz;  // (the last row ends at its last score)
     {   // sized in 64 bits and compared with the free device memory before anything is allocated
         unsigned long long grow = raw_bytes, released = 0;
         if (cells > ctx->E32.n) { grow += 4ull * cells; released += ctx->E32.bytes(); }
@@ -813,11 +819,17 @@ static int stage_emissions_on(fv_ctx *ctx, const void *scores, int dtype, int T,
     unsigned long long got[2] = { 0ull, ~0ull };
     FV_HIP(hipMemsetAsync(ctx->d_emflags.p, 0, sizeof(unsigned long long), ctx->stream));               // no flag
     FV_HIP(hipMemsetAsync(ctx->d_emflags.p + 1, 0xFF, sizeof(unsigned long long), ctx->stream));        // no refused index
-    if (int rc = launch_stage_emissions(ctx, src, dtype, ld, T)) return rc;
+    if (int rc = launch_stage_emissions(ctx, src, dtype, ld, T, ctx->EMap.p, ctx->emis_P)) return rc;
     FV_HIP(hipMemcpyAsync(got, ctx->d_emflags.p, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
     FV_HIP(hipStreamSynchronize(ctx->stream));              // the one sync of the call: copies and kernel are done, `raw` can go
     if (got[0] & FV_EMIS_BAD) {
-        ctx->detail = "fv_set_emissions: the score at (t = " + std::to_string(got[1] / K) + ", state = " + std::to_string(got[1] % K) +
+        std::string cls;
+        if (ctx->emis_P) {                                  // which score of the caller's row that was
+            int p = -1;
+            FV_HIP(hipMemcpy(&p, ctx->EMap.p + got[1] % K, sizeof p, hipMemcpyDeviceToHost));
+            cls = ", class = " + std::to_string(p);
+        }
+        ctx->detail = "fv_set_emissions: the score at (t = " + std::to_string(got[1] / K) + ", state = " + std::to_string(got[1] % K) + cls +
                       ") is NaN, +inf or beyond the float32 range; scores are finite or -inf";
         return FV_ERR_ARG;
     }
@@ -839,8 +851,9 @@ extern "C" int fv_set_emissions(fv_ctx *ctx, const void *scores, int dtype, int 
     ctx->stats.emission_rows = 0;
     ctx->stats.set_emissions_ms = 0.0;           // (a refused call staged nothing: no time to report)
     if (ctx->K == 0) { ctx->detail = "fv_set_emissions: no model (the row length K is the model's)"; return FV_ERR_STATE; }
-    if (!scores || T < 1 || ld < ctx->K || ld > (1ll << 59) / T || (dtype != FV_EMIS_LOG_F32 && dtype != FV_EMIS_LOG_F64)) {
-        ctx->detail = "fv_set_emissions: scores != NULL, T >= 1, ld >= K and dtype FV_EMIS_LOG_F32 or FV_EMIS_LOG_F64";
+    if (!scores || T < 1 || ld < (ctx->emis_P ? ctx->emis_P : ctx->K) || ld > (1ll << 59) / T || !fvi::emis_dtype_ok(dtype)) {
+        ctx->detail = "fv_set_emissions: scores != NULL, T >= 1, ld >= K (ld >= P while an emission map is set) and dtype "
+                      "FV_EMIS_LOG_F32, _F64, _F16 or _BF16";
         return FV_ERR_ARG;
     }
     auto t0 = clk::now();
@@ -864,6 +877,57 @@ extern "C" int fv_set_emissions(fv_ctx *ctx, const void *scores, int dtype, int 
     ctx->stats.emission_rows = T;
     ctx->stats.device_bytes = (long long)fvi::device_bytes(ctx);
     return FV_OK;
+}
+
+// The map is the model's: checked on the host, then 4 * K bytes to every member.  Whatever was staged went through the
+// map that is replaced, so it goes; an argument error comes before that and leaves map and rows as they were.
+extern "C" int fv_set_emission_map(fv_ctx *ctx, const int *pdf_of_state, int P)
+{
+    if (!ctx) return FV_ERR_ARG;
+    if (ctx->K == 0) { ctx->detail = "fv_set_emission_map: no model (the map holds one entry per state of the model)"; return FV_ERR_STATE; }
+    if (!pdf_of_state && P != 0) { ctx->detail = "fv_set_emission_map: pdf_of_state == NULL clears the map and takes P == 0"; return FV_ERR_ARG; }
+    if (pdf_of_state) {
+        if (P < 1) { ctx->detail = "fv_set_emission_map: P >= 1 score classes with a map"; return FV_ERR_ARG; }
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, pdf_of_state) != hipSuccess) (void)hipGetLastError();      // (plain host memory)
+        else if (at.type == hipMemoryTypeDevice) {
+            ctx->detail = "fv_set_emission_map: pdf_of_state is a device pointer; the map is read on the host";
+            return FV_ERR_ARG;
+        }
+        for (int i = 0; i < ctx->K; ++i)
+            if (pdf_of_state[i] < 0 || pdf_of_state[i] >= P) {
+                ctx->detail = "fv_set_emission_map: pdf_of_state[" + std::to_string(i) + "] = " + std::to_string(pdf_of_state[i]) +
+                              " (state " + std::to_string(i) + ") lies outside [0, P = " + std::to_string(P) + ")";
+                return FV_ERR_ARG;
+            }
+    }
+    const int n = fvi::group_size(ctx);
+    auto unset = [&] {
+        for (int r = 0; r < n; ++r) {
+            fv_ctx *m = fvi::group_member(ctx, r);
+            m->emis_rows = 0; m->emis_positive = false; m->emis_P = 0;
+        }
+        ctx->stats.emission_rows = 0;
+        ctx->stats.set_emissions_ms = 0.0;
+    };
+    unset();
+    int rc = FV_OK;
+    for (int r = 0; r < n && rc == FV_OK; ++r) {
+        fv_ctx *m = fvi::group_member(ctx, r);
+        rc = [&]() -> int {
+            fv_ctx *ctx = m;                     // (FV_HIP reports into the member)
+            FV_HIP(hipSetDevice(ctx->device));
+            if (!pdf_of_state) { ctx->EMap.release(); return FV_OK; }
+            FV_HIP(ctx->EMap.ensure((size_t)ctx->K));
+            FV_HIP(hipMemcpy(ctx->EMap.p, pdf_of_state, (size_t)ctx->K * sizeof(int), hipMemcpyHostToDevice));
+            ctx->emis_P = P;
+            return FV_OK;
+        }();
+        if (rc && m != ctx) ctx->detail = m->detail;
+    }
+    if (rc) unset();                             // an upload failed: no map anywhere, nothing staged
+    ctx->stats.device_bytes = (long long)fvi::device_bytes(ctx);
+    return rc;
 }
 
 extern "C" int fv_clear_emissions(fv_ctx *ctx)
@@ -908,8 +972,8 @@ extern "C" int fv_test_device_free(fv_ctx *ctx, void *p)
 // include/flashvit_testing.h: the staging kernel alone between two device events, reps launches back to back
 extern "C" int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, int dtype, int T, long long ld, int reps, float *ms_out)
 {
-    if (!ctx || !ms_out || !dev_scores || T < 1 || reps < 1 || ctx->K == 0 || ld < ctx->K || ld > (1ll << 59) / T ||
-        (dtype != FV_EMIS_LOG_F32 && dtype != FV_EMIS_LOG_F64) || ctx->group)
+    if (!ctx || !ms_out || !dev_scores || T < 1 || reps < 1 || ctx->K == 0 || ld < (ctx->emis_P ? ctx->emis_P : ctx->K) ||
+        ld > (1ll << 59) / T || !fvi::emis_dtype_ok(dtype) || ctx->group)
         return FV_ERR_ARG;
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, dev_scores) != hipSuccess) { (void)hipGetLastError(); return FV_ERR_ARG; }
@@ -927,10 +991,10 @@ extern "C" int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, i
     struct Ev { hipEvent_t &a, &b; ~Ev() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev{ e0, e1 };
     FV_HIP(hipEventCreate(&e0));
     FV_HIP(hipEventCreate(&e1));
-    if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T)) return fvi::drained(ctx, rc);      // warm
+    if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T, ctx->EMap.p, ctx->emis_P)) return fvi::drained(ctx, rc);      // warm
     FV_HIP(hipEventRecord(e0, ctx->stream));
     for (int r = 0; r < reps; ++r)
-        if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T)) return fvi::drained(ctx, rc);
+        if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T, ctx->EMap.p, ctx->emis_P)) return fvi::drained(ctx, rc);
     FV_HIP(hipEventRecord(e1, ctx->stream));
     FV_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0.0f;

@@ -814,16 +814,30 @@ int launch_init_rows(fv_ctx *ctx, const fvk::PassChunk &ch, float *rows)
 }
 
 // Workgroups of EMIS_BLOCK states by rows, about 2048 in all (eight per CU); the kernel strides over the rest.
-int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T)
+template <typename TIN>
+static void launch_stage_as(fv_ctx *ctx, const void *src, long long ld, int T, const int *map, dim3 grid)
+{
+    if (map)
+        hipLaunchKernelGGL((fvk::stage_emissions<TIN, true>), grid, dim3(fvk::EMIS_BLOCK), 0, ctx->stream,
+                           static_cast<const TIN *>(src), ld, T, ctx->K, map, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p);
+    else
+        hipLaunchKernelGGL((fvk::stage_emissions<TIN, false>), grid, dim3(fvk::EMIS_BLOCK), 0, ctx->stream,
+                           static_cast<const TIN *>(src), ld, T, ctx->K, map, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p);
+}
+
+// map != NULL (P > 0): the tied form, rows of P scores gathered through the K entries of map
+int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T, const int *map, int P)
 {
     const int K = ctx->K;
     const int gx = std::min((K + fvk::EMIS_BLOCK - 1) / fvk::EMIS_BLOCK, 2048), gy = std::max(1, std::min(T, 2048 / gx));
-    if (dtype == FV_EMIS_LOG_F64)
-        hipLaunchKernelGGL(fvk::stage_emissions<double>, dim3(gx, gy), dim3(fvk::EMIS_BLOCK), 0, ctx->stream,
-                           static_cast<const double *>(src), ld, T, K, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p);
-    else
-        hipLaunchKernelGGL(fvk::stage_emissions<float>, dim3(gx, gy), dim3(fvk::EMIS_BLOCK), 0, ctx->stream,
-                           static_cast<const float *>(src), ld, T, K, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p);
+    if (P <= 0) map = nullptr;
+    switch (dtype) {
+    case FV_EMIS_LOG_F64: launch_stage_as<double>(ctx, src, ld, T, map, dim3(gx, gy)); break;
+    case FV_EMIS_LOG_F32: launch_stage_as<float>(ctx, src, ld, T, map, dim3(gx, gy)); break;
+    case FV_EMIS_LOG_F16: launch_stage_as<_Float16>(ctx, src, ld, T, map, dim3(gx, gy)); break;
+    case FV_EMIS_LOG_BF16: launch_stage_as<fvk::bf16_bits>(ctx, src, ld, T, map, dim3(gx, gy)); break;
+    default: ctx->detail = "fv_set_emissions: unknown dtype"; return FV_ERR_ARG;
+    }
     FV_HIP(hipGetLastError());
     return 0;
 }

@@ -100,6 +100,10 @@ struct fv_ctx {
     DevBuf<unsigned long long> d_emflags;    // [0] FV_EMIS_BAD / FV_EMIS_POSITIVE bits, [1] lowest t * K + i of a refused value
     long long emis_rows = 0;     // staged rows (0: none)
     bool emis_positive = false;  // a staged score is above 0
+    // fv_set_emission_map: the K states share emis_P score classes through EMap[K] (emis_P == 0: no map, rows of K scores);
+    // it belongs to the model, as log B does
+    DevBuf<int> EMap;
+    int emis_P = 0;
     std::vector<int> h_iota;     // 0, 1, 2, ...: the observation sequence of a decode given ob == NULL
     // What the decode in flight reads its emission term from (fvi::emission_view sets it first thing in every decode):
     // log B of the model by symbol, or the staged rows by time.
@@ -200,7 +204,7 @@ struct fv_ctx {
     {
         f(LA32); f(LB32T); f(LA16); f(LAQ16); f(SPdata); f(SPoff); f(SPnwb); f(LA64); f(LB64T); f(LPi64);
         f(CSk); f(CSq); f(CS64); f(CSoff); f(CSnwb); f(CRptr); f(CRcol); f(CRlog);
-        f(E32); f(E64); f(d_emflags);
+        f(E32); f(E64); f(d_emflags); f(EMap);
         f(d_ob); f(d_ans); f(d_bp); f(d_gather); f(d_rows); f(d_score); f(d_ckpt); f(d_counters); f(d_pack);
         f(d_snap); f(d_flat_bp); f(d_chain); f(d_flat);
         f(d_hval); f(d_scores); f(d_slot_val); f(d_hstate); f(d_slot_state); f(d_flags); f(LA64R); f(LAQ16R); f(d_qaux);
@@ -285,7 +289,8 @@ int drained(fv_ctx *ctx, int rc);
 int emission_view(fv_ctx *ctx, const int *&ob, long long T);
 // fvk::stage_emissions lives with the full-state kernels (fv_full.hip); fv_set_emissions launches it through here
 enum { FV_EMIS_BAD = 1, FV_EMIS_POSITIVE = 2 };
-int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T);
+// (map: the device copy of the emission map and P its class count for the tied form; NULL / 0 without a map)
+int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T, const int *map, int P);
 // decode prologue: observation sequence to the device (through the pinned block), counters and answers cleared
 int begin_decode(fv_ctx *ctx, const int *ob, int T);
 // big-LDS attributes of the kernels each translation unit owns

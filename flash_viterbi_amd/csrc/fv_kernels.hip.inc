@@ -1927,16 +1927,36 @@ __global__ __launch_bounds__(1024) void flat_resolve(const FlatDesc *desc, const
     }
 }
 
-// fv_set_emissions: the caller's T x K block of log scores (row pitch ld elements, float or double) into the two
-// per-time tables the step kernels read in place of log B: E32[t][i] = (float)x, E64[t][i] = (double)x.  Workgroups
-// stride over rows (y) and over states (x), lanes along the state index: coalesced loads and stores, nothing beyond
-// column K - 1 of a row is read.  flags[0] collects FV_EMIS_BAD (1: NaN, +inf, or a finite value whose float is
-// infinite) and FV_EMIS_POSITIVE (2: above 0); flags[1] the lowest t * K + i of a refused value.  One atomic pair per
-// workgroup that saw anything, through LDS.
+// fv_set_emissions: the caller's block of log scores (row pitch ld elements) into the two per-time tables the step
+// kernels read in place of log B: E32[t][i] = (float)x, E64[t][i] = (double)x.  TIN is double, float, _Float16 (IEEE
+// binary16) or bf16_bits (bfloat16); every widening to double is exact.  Workgroups stride over rows (y) and over states
+// (x), lanes along the state index.  !TIED: rows of K scores, x = row[i]: coalesced loads and stores, nothing beyond
+// column K - 1 of a row is read.  TIED (fv_set_emission_map): rows of P scores shared by the K states, x = row[map[i]]:
+// a lane keeps its state and walks the rows, so map[i] is loaded once per state (coalesced) and every row's gather
+// comes from a few KB the whole grid row shares in L2; map[i] was checked on the host; a column no state maps to is
+// never read.  Elements are loaded one by one (2-byte ones need no more than their own alignment).  flags[0] collects
+// FV_EMIS_BAD (1: NaN, +inf, or a finite value whose float is infinite) and FV_EMIS_POSITIVE (2: above 0); flags[1]
+// the lowest t * K + i of a refused value.  One atomic pair per workgroup that saw anything, through LDS.
 constexpr int EMIS_BLOCK = 256;
-template <typename TIN>
-__global__ __launch_bounds__(EMIS_BLOCK) void stage_emissions(const TIN *src, long long ld, int T, int K, float *E32,
-                                                              double *E64, unsigned long long *flags)
+struct bf16_bits { unsigned short u; };
+__device__ inline double emis_widen(double x) { return x; }
+__device__ inline double emis_widen(float x) { return (double)x; }
+__device__ inline double emis_widen(_Float16 x) { return (double)x; }
+__device__ inline double emis_widen(bf16_bits x) { return (double)__uint_as_float((unsigned int)x.u << 16); }
+// one cell: the two stores and the value rules
+__device__ inline void emis_cell(double x, size_t e, float *E32, double *E64, unsigned int &f, unsigned long long &bad)
+{
+    const float xf = (float)x;
+    // accepted: -inf and every value whose float is finite (NaN fails both comparisons)
+    const bool ok = xf < HUGE_VALF && (xf > -HUGE_VALF || x == -HUGE_VAL);
+    if (!ok) { f |= 1u; bad = min(bad, (unsigned long long)e); }
+    if (x > 0.0) f |= 2u;
+    E32[e] = xf;
+    E64[e] = x;
+}
+template <typename TIN, bool TIED>
+__global__ __launch_bounds__(EMIS_BLOCK) void stage_emissions(const TIN *src, long long ld, int T, int K, const int *map,
+                                                              float *E32, double *E64, unsigned long long *flags)
 {
     __shared__ unsigned int s_flags;
     __shared__ unsigned long long s_bad;
@@ -1944,18 +1964,17 @@ __global__ __launch_bounds__(EMIS_BLOCK) void stage_emissions(const TIN *src, lo
     __syncthreads();
     unsigned int f = 0u;
     unsigned long long bad = ~0ull;
-    for (int t = blockIdx.y; t < T; t += gridDim.y) {
-        const TIN *row = src + (size_t)t * (size_t)ld;
+    if constexpr (TIED) {
         for (int i = blockIdx.x * EMIS_BLOCK + threadIdx.x; i < K; i += gridDim.x * EMIS_BLOCK) {
-            const double x = (double)row[i];
-            const float xf = (float)x;
-            const size_t e = (size_t)t * K + i;
-            // accepted: -inf and every value whose float is finite (NaN fails both comparisons)
-            const bool ok = xf < HUGE_VALF && (xf > -HUGE_VALF || x == -HUGE_VAL);
-            if (!ok) { f |= 1u; bad = min(bad, (unsigned long long)e); }
-            if (x > 0.0) f |= 2u;
-            E32[e] = xf;
-            E64[e] = x;
+            const TIN *col = src + map[i];
+            for (int t = blockIdx.y; t < T; t += gridDim.y)
+                emis_cell(emis_widen(col[(size_t)t * (size_t)ld]), (size_t)t * K + i, E32, E64, f, bad);
+        }
+    } else {
+        for (int t = blockIdx.y; t < T; t += gridDim.y) {
+            const TIN *row = src + (size_t)t * (size_t)ld;
+            for (int i = blockIdx.x * EMIS_BLOCK + threadIdx.x; i < K; i += gridDim.x * EMIS_BLOCK)
+                emis_cell(emis_widen(row[i]), (size_t)t * K + i, E32, E64, f, bad);
         }
     }
     if (f) atomicOr(&s_flags, f);

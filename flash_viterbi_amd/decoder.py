@@ -32,6 +32,8 @@ WARN_BEAM_MISS = 1
 ERR_ARG, ERR_NOMEM, ERR_NO_PRED, ERR_DEVICE, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 UNIQUE_ID_BYTES = 128
 EMIS_LOG_F32, EMIS_LOG_F64 = 0, 1     # dtype of fv_set_emissions
+EMIS_LOG_F16, EMIS_LOG_BF16 = 2, 3     # IEEE binary16 / bfloat16 (numpy has no bfloat16: a torch tensor, or a pointer in the tuple form)
+_EMIS_OF_NUMPY = {np.dtype(np.float32): EMIS_LOG_F32, np.dtype(np.float64): EMIS_LOG_F64, np.dtype(np.float16): EMIS_LOG_F16}
 
 
 class Stats(ctypes.Structure):
@@ -73,7 +75,7 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_last_stats", "fv_strerror", "fv_last_error_detail", "fv_reference_memory_bytes",
            "fv_comm_unique_id", "fv_comm_init", "fv_plan_passes", "fv_merge_paths", "fv_set_partition",
            "fv_create_multi", "fv_device_count", "fv_decode_full_batch", "fv_plan_passes_batch", "fv_decode_beam_batch",
-           "fv_set_model_sparse", "fv_set_emissions", "fv_clear_emissions", "fv_plan_flat"]
+           "fv_set_model_sparse", "fv_set_emissions", "fv_clear_emissions", "fv_plan_flat", "fv_set_emission_map"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select", "fv_test_device_alloc", "fv_test_device_free",
                 "fv_test_stage_emissions_ms", "fv_test_flat_poison"]
@@ -128,6 +130,7 @@ def load_library():
     L.fv_set_option.argtypes = [vp, ci, cll]
     L.fv_set_emissions.argtypes = [vp, vp, ci, ci, cll]
     L.fv_clear_emissions.argtypes = [vp]
+    L.fv_set_emission_map.argtypes = [vp, vp, ci]
     L.fv_test_device_alloc.argtypes = [vp, ctypes.c_size_t, vp, ctypes.POINTER(vp)]
     L.fv_test_device_free.argtypes = [vp, vp]
     L.fv_test_stage_emissions_ms.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
@@ -228,6 +231,11 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _is_torch_tensor(x):
+    """whether x is a torch.Tensor, without importing torch for anything that is not one"""
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
 def _ob_arg(ob, T):
     """(keep-alive array, pointer, length) of a decode's observations: an int sequence, or None with T = the number of staged emission
     rows to decode (fv_set_emissions)."""
@@ -290,6 +298,7 @@ class FlashViterbi:
             raise FlashVitError(rc, "fv_create (is a GPU visible? there is no CPU fallback)")
         self._h = h
         self.K = self.M = 0
+        self.P = 0                          # classes of the emission map in force (set_emission_map); 0: none
 
     def close(self):
         if getattr(self, "_h", None):
@@ -314,7 +323,7 @@ class FlashViterbi:
         K, M = B.shape
         assert A.shape == (K, K) and Pi.shape == (K,)
         self._check(self._L.fv_set_model(self._h, _p(A), _p(B), _p(Pi), K, M))
-        self.K, self.M = K, M
+        self.K, self.M, self.P = K, M, 0
 
     def set_model_sparse(self, indptr, indices, data, B, Pi):
         """fv_set_model_sparse: the transition matrix in CSR form by source state (indptr[K + 1], ascending column
@@ -329,31 +338,61 @@ class FlashViterbi:
         # (the array lengths are the wrapper's to check: the library reads row_ptr[K] entries of both)
         assert indptr[-1] <= indices.size, "indptr[K] exceeds the number of stored entries"
         self._check(self._L.fv_set_model_sparse(self._h, _p(indptr), _p(indices), _p(data), _p(B), _p(Pi), K, M))
-        self.K, self.M = K, M
+        self.K, self.M, self.P = K, M, 0
+
+    def set_emission_map(self, pdf_of_state, P=None):
+        """fv_set_emission_map: the K states share P score classes, state i scoring as class pdf_of_state[i]; set_emissions
+        then takes rows of P scores.  P defaults to max(pdf_of_state) + 1.  None clears the map.  Either way the staged
+        rows are dropped.  self.P is the class count in force (0: no map)."""
+        if pdf_of_state is None:
+            self._check(self._L.fv_set_emission_map(self._h, None, 0))
+            self.P = 0
+            return
+        m = np.ascontiguousarray(pdf_of_state, dtype=np.int32)
+        if m.shape != (self.K,):
+            raise ValueError("set_emission_map: one entry per state of the model")
+        P = int(m.max()) + 1 if P is None else int(P)
+        self._check(self._L.fv_set_emission_map(self._h, _p(m), P))
+        self.P = P
 
     def set_emissions(self, scores, ld=None):
-        """fv_set_emissions: per-time log emission scores, row t = the K scores of time t.  `scores` is a 2-D float32
-        or float64 numpy array [T, >= K] (ld: its row pitch in elements, default its width; columns beyond K are not
-        interpreted), or a tuple (device_pointer:int, dtype, T, ld) for a block already on this context's GPU (dtype:
-        np.float32 / np.float64 or EMIS_LOG_F32 / EMIS_LOG_F64; its producer must have finished).  Afterwards every
-        decode_* and test_forward takes ob=None.  There is no torch path: pass tensor.data_ptr() in the tuple form."""
+        """fv_set_emissions: per-time log emission scores, row t = the K scores of time t (the P class scores while an
+        emission map is set).  `scores` is a 2-D float16, float32 or float64 numpy array [T, >= K] (ld: its row pitch in
+        elements, default its width; columns beyond K are not interpreted); a 2-D torch tensor of dtype float16,
+        bfloat16, float32 or float64 with stride(1) == 1, on the CPU or on this context's GPU (ld = stride(0), so a
+        column slice of a wider tensor is staged without a copy; the tensor's current stream is synchronised first); or
+        a tuple (device_pointer:int, dtype, T, ld) for a block already on this context's GPU (dtype: np.float16 /
+        np.float32 / np.float64 or an EMIS_LOG_* code; its producer must have finished).  Afterwards every decode_* and
+        test_forward takes ob=None."""
         if isinstance(scores, tuple):
             ptr, dtype, T, pitch = scores
             if ld is not None:
                 pitch = ld
             if isinstance(dtype, (type, np.dtype, str)):
-                dtype = {np.dtype(np.float32): EMIS_LOG_F32, np.dtype(np.float64): EMIS_LOG_F64}.get(np.dtype(dtype), -1)
+                dtype = _EMIS_OF_NUMPY.get(np.dtype(dtype), -1)
             self._check(self._L.fv_set_emissions(self._h, ctypes.c_void_p(int(ptr)), int(dtype), int(T), int(pitch)))
             return
+        if _is_torch_tensor(scores):
+            import torch
+            codes = {torch.float16: EMIS_LOG_F16, torch.bfloat16: EMIS_LOG_BF16, torch.float32: EMIS_LOG_F32, torch.float64: EMIS_LOG_F64}
+            if scores.dim() != 2 or scores.dtype not in codes or scores.stride(1) != 1 or scores.shape[0] < 1 or scores.shape[1] < 1:
+                raise TypeError("set_emissions: a torch tensor must be 2-D, float16 / bfloat16 / float32 / float64, with stride(1) == 1")
+            pitch = scores.stride(0) if ld is None else int(ld)
+            if scores.shape[0] == 1:
+                pitch = max(pitch, scores.shape[1])         # (one row: its stride is arbitrary and never used)
+            if scores.is_cuda:
+                torch.cuda.current_stream(scores.device).synchronize()      # the C contract: the producer has finished
+            self._check(self._L.fv_set_emissions(self._h, ctypes.c_void_p(scores.data_ptr()), codes[scores.dtype],
+                                                 scores.shape[0], pitch))
+            return
         a = np.asarray(scores)
-        if a.ndim != 2 or a.dtype not in (np.float32, np.float64):
-            raise TypeError("set_emissions: a 2-D float32 or float64 array, or (device_pointer, dtype, T, ld)")
+        if a.ndim != 2 or a.dtype not in _EMIS_OF_NUMPY:
+            raise TypeError("set_emissions: a 2-D float16, float32 or float64 array, a torch tensor, or (device_pointer, dtype, T, ld)")
         a = np.ascontiguousarray(a)
         pitch = a.shape[1] if ld is None else int(ld)
         if pitch > a.shape[1] and a.shape[0] > 1:
             raise ValueError("set_emissions: ld exceeds the row length of the array")
-        dtype = EMIS_LOG_F32 if a.dtype == np.float32 else EMIS_LOG_F64
-        self._check(self._L.fv_set_emissions(self._h, _p(a), dtype, a.shape[0], pitch))
+        self._check(self._L.fv_set_emissions(self._h, _p(a), _EMIS_OF_NUMPY[a.dtype], a.shape[0], pitch))
 
     def clear_emissions(self):
         self._check(self._L.fv_clear_emissions(self._h))
@@ -435,10 +474,11 @@ class FlashViterbi:
 
     def test_stage_emissions_ms(self, ptr, dtype, T, ld, reps):
         """fv_test_stage_emissions_ms: mean milliseconds per launch of the staging kernel over the device block at ptr
-        (device events around reps launches back to back).  Nothing is staged afterwards."""
+        (device events around reps launches back to back); dtype as in set_emissions' tuple form.  While an emission
+        map is set it is the tied form over a T x P block.  Nothing is staged afterwards."""
         ms = ctypes.c_float(0)
-        code = EMIS_LOG_F64 if np.dtype(dtype) == np.float64 else EMIS_LOG_F32
-        self._check(self._L.fv_test_stage_emissions_ms(self._h, ctypes.c_void_p(int(ptr)), code, int(T), int(ld), int(reps), ctypes.byref(ms)))
+        code = dtype if isinstance(dtype, int) else _EMIS_OF_NUMPY.get(np.dtype(dtype), -1)
+        self._check(self._L.fv_test_stage_emissions_ms(self._h, ctypes.c_void_p(int(ptr)), int(code), int(T), int(ld), int(reps), ctypes.byref(ms)))
         return float(ms.value)
 
     def test_forward(self, ob, passes, bp_fill=-2, T=None):

@@ -235,20 +235,28 @@ int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const int *col, c
  * models and profile HMMs, which hold one log score per (time, state) and have no symbol alphabet.  `scores` is T rows of
  * K log scores (K is the model's), row t, state i at scores[t * ld + i], ld >= K in elements; what lies beyond K in a row
  * is never interpreted (a host block is copied as one piece up to the last row's K-th element, pads included).  dtype is
- * FV_EMIS_LOG_F32 (float) or FV_EMIS_LOG_F64 (double).  `scores` may be a host pointer or a device pointer
+ * FV_EMIS_LOG_F32 (float), FV_EMIS_LOG_F64 (double), FV_EMIS_LOG_F16 (IEEE binary16) or FV_EMIS_LOG_BF16 (bfloat16);
+ * rows of the 2-byte types need no more than 2-byte alignment (an odd ld, a block entered at an odd element).  `scores`
+ * may be a host pointer or a device pointer
  * (hipPointerGetAttributes decides); work producing a device block must be complete before the call; the call returns
  * after staging, so the caller may free `scores` at once.
  *   The library keeps two device tables, E32[t][i] = (float)x in the part of (float)log(B[i][o]) (FLASH:167) and
  * E64[t][i] = (double)x in the part of log((double)B[i][o]) (init rows, vanilla / checkpoint arithmetic): for
- * FV_EMIS_LOG_F64 input of log((double)b) values exactly the tables fv_set_model builds from b.  FV_EMIS_LOG_F32 is
- * the same as passing (double)x.
+ * FV_EMIS_LOG_F64 input of log((double)b) values exactly the tables fv_set_model builds from b.  FV_EMIS_LOG_F32,
+ * FV_EMIS_LOG_F16 and FV_EMIS_LOG_BF16 are the same as passing (double)x: each of these widenings is exact.
+ *   Tied scores (fv_set_emission_map): while a map is set, a row holds P class scores in place of K state scores, row t,
+ * class p at scores[t * ld + p], ld >= P, and state i takes x = scores[t * ld + pdf_of_state[i]].  The tables stay T x K
+ * and hold exactly what staging the expanded T x K block without a map would have put there, so everything said here of
+ * values, decodes and ob == NULL holds unchanged.  A class that no state maps to is never interpreted, as a pad column.
  *   Values: finite or -inf.  A NaN, a +inf or a finite double whose float conversion is infinite answers FV_ERR_ARG, with
- * the lowest offending (t, state) in fv_last_error_detail.  A score above 0 (a density above 1) is accepted and handled
+ * the lowest offending (t, state) in fv_last_error_detail (and its class, through a map).  A score above 0 (a density
+ * above 1) is accepted and handled
  * as a B entry above 1: decodes on these emissions take FV_KERNEL_F64_STREAM under AUTO, answer FV_ERR_UNSUPPORTED to a
  * forced filter kernel and on a model set by fv_set_model_sparse (unless FV_KERNEL_CSR_F64 is selected there), and the beam
  * path takes its float64 step kernel.
- *   Returns FV_ERR_STATE without a model, FV_ERR_ARG for T < 1, ld < K, a bad dtype or a NULL pointer, FV_ERR_NOMEM (the
- * byte count in the detail, before anything is allocated) when 12 * T * K bytes plus the raw copy exceed the free device
+ *   Returns FV_ERR_STATE without a model, FV_ERR_ARG for T < 1, ld < K (ld < P with a map), a bad dtype or a NULL pointer,
+ * FV_ERR_NOMEM (the byte count in the detail, before anything is allocated) when 12 * T * K bytes plus the raw copy
+ * (((T - 1) * ld + K) elements; P for K with a map) exceed the free device
  * memory.  A failed call leaves the context with no staged emissions.
  *   Use: every decode call — and fv_test_forward — given ob == NULL reads row t for time t.  The single decodes need
  * T <= staged rows; the batch decodes put sequence s on rows offsets[s] .. offsets[s+1]) and need offsets[nseq] <= staged
@@ -259,6 +267,17 @@ int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const int *col, c
 enum { FV_EMIS_LOG_F32 = 0, FV_EMIS_LOG_F64 = 1 };
 int fv_set_emissions(fv_ctx *ctx, const void *scores, int dtype, int T, long long ld);
 int fv_clear_emissions(fv_ctx *ctx);
+enum { FV_EMIS_LOG_F16 = 2, FV_EMIS_LOG_BF16 = 3 };
+/* The emission map of a model whose K states share P score classes (senones, pdf ids, match / insert columns):
+ * pdf_of_state is a HOST array of K entries in [0, P), P >= 1.  It belongs to the model as B does: uploaded once (4 * K
+ * bytes per device, to every member of a fv_create_multi context), kept until replaced or cleared (pdf_of_state == NULL
+ * with P == 0), dropped by fv_set_model and fv_set_model_sparse.  While it is set fv_set_emissions reads rows of P scores
+ * (see there).  Setting, replacing or clearing the map drops the staged rows: they were expanded through the old one.
+ *   Returns FV_ERR_STATE without a model; FV_ERR_ARG, before any device work and with a detail text, for P < 1 with a
+ * map, P != 0 without one, an entry outside [0, P) (the lowest such state is named) and a device pointer
+ * (hipPointerGetAttributes decides) — an argument error leaves the previous map and the staged rows in place.  An upload
+ * failure leaves no map and nothing staged. */
+int fv_set_emission_map(fv_ctx *ctx, const int *pdf_of_state, int P);
 
 int fv_set_option(fv_ctx *ctx, int key, long long value);
 

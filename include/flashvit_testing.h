@@ -50,10 +50,12 @@ int fv_test_device_alloc(fv_ctx *ctx, size_t bytes, const void *host_src, void *
 int fv_test_device_free(fv_ctx *ctx, void *p);
 
 /* The staging kernel of fv_set_emissions alone, timed on the device: one warm launch, then `reps` launches back to back
- * of stage_emissions<TIN> between two events on the context's stream, over the T x K block at dev_scores (a device
- * pointer on the context's GPU, row pitch ld, dtype as for fv_set_emissions); *ms_out is the mean per launch, dispatch
+ * of stage_emissions<TIN, TIED> between two events on the context's stream, over the T x K block at dev_scores (a device
+ * pointer on the context's GPU, row pitch ld, dtype as for fv_set_emissions, the 16-bit types included); while an
+ * emission map is set it is the tied form over a T x P block, ld >= P.  *ms_out is the mean per launch, dispatch
  * gaps included.  Nothing is staged afterwards (the tables are overwritten and the values are not judged).  FV_ERR_ARG: no
- * model, a host pointer, T < 1, ld < K, reps < 1, a bad dtype, a multi-device context.  For tools/bench_emissions.py. */
+ * model, a host pointer, T < 1, ld < K (ld < P with a map), reps < 1, a bad dtype, a multi-device context.  For
+ * tools/bench_emissions.py and tools/bench_emissions_tied.py. */
 int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, int dtype, int T, long long ld, int reps, float *ms_out);
 
 /* One slot set of a beam step: n entries {val[e], state[e]} (states in [0, K)), beam <= n <= beam + 32. */
