@@ -1033,6 +1033,9 @@ extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
     case FV_OPT_FLAT_GENERATIONS:
         if (value < 0 || value > 2) return FV_ERR_ARG;
         ctx->opt_flat = (int)value; return FV_OK;
+    case FV_OPT_ROW_CODES:
+        if (value < 0 || value > 4) return FV_ERR_ARG;
+        ctx->opt_row_codes = (int)value; return FV_OK;
     case FV_OPT_SEL_MARGIN:
         if (value < 0 || value > 100000) return FV_ERR_ARG;
         ctx->opt_sel_margin = (float)value * 1e-3f; return FV_OK;

@@ -100,8 +100,8 @@ int launch_step_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb, int reverse)
     a.ntiles = (ctx->K + fvk::TILE_W - 1) / fvk::TILE_W;
     a.tiles_per_xcd = (a.ntiles + 7) / 8;
     a.nb = nb;
-    a.row_lo = 0; a.srows = ctx->nrows; a.merge = 0;
-    for (int t = 0; t < NB; ++t) a.t[t] = slots[t < nb ? t : 0];
+    a.row_lo = 0; a.srows = ctx->nrows; a.merge = 0; a.codes = 0;
+    for (int t = 0; t < NB; ++t) { a.t[t] = slots[t < nb ? t : 0]; a.c[t] = fvk::CodeSlot{ nullptr, nullptr, nullptr, nullptr }; }
     const size_t lds = fvk::step_lds_bytes<NB>(ctx->nrows);
     constexpr int RBR = 4 * fvk::Tab<TA>::R;
     const int nj_max = (ctx->nrows / RBR + fvk::NWAVES - 1) / fvk::NWAVES;
@@ -256,8 +256,10 @@ template <int NB, int U, bool DB, int NWV>
 int launch_u16_variant(fv_ctx *ctx, const fvk::StepArgs<NB> &a)
 {
     const size_t lds = fvk::u16_lds_bytes<NB, NWV>(ctx->nrows);
-    if (ctx->test_record) ctx->test_variants |= u16_variant<NB, DB, NWV>();
-    hipLaunchKernelGGL((fvk::trellis_step_u16<NB, U, DB, NWV>), dim3(a.tiles_per_xcd * 8), dim3(NWV * 64), lds, ctx->lstream ? ctx->lstream : ctx->stream, a);
+    fvk::StepArgs<NB> b = a;
+    if (!fvk::u16_takes_codes<NB, DB, NWV>()) b.codes &= ~1;
+    if (ctx->test_record) ctx->test_variants |= u16_variant<NB, DB, NWV>() | ((b.codes & 1) ? FV_TV_ROW_CODES : 0ull);
+    hipLaunchKernelGGL((fvk::trellis_step_u16<NB, U, DB, NWV>), dim3(a.tiles_per_xcd * 8), dim3(NWV * 64), lds, ctx->lstream ? ctx->lstream : ctx->stream, b);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -274,7 +276,9 @@ int launch_u16_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb, int reverse)
     a.tiles_per_xcd = (a.ntiles + 7) / 8;
     a.nb = nb;
     a.row_lo = 0; a.srows = ctx->nrows; a.merge = 0;
-    for (int t = 0; t < NB; ++t) a.t[t] = slots[t < nb ? t : 0];
+    a.codes = ctx->launch_codes;          // FV_OPT_ROW_CODES: what launch_step_kernel found for this launch's rows
+    const fvk::CodeSlot *cs = static_cast<const fvk::CodeSlot *>(ctx->launch_code_slots);
+    for (int t = 0; t < NB; ++t) { a.t[t] = slots[t < nb ? t : 0]; a.c[t] = cs[t < nb ? t : 0]; }
     const int nq = ctx->nrows / 32;
     // 8 waves per workgroup (FV_OPT_DEBUG bit 13: 16): everything outside the sweep — quantisation, reductions, refine —
     // is executed by every wave, so fewer, longer waves spend fewer issue slots on it
@@ -296,8 +300,81 @@ int launch_u16(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb, int reverse)
     return launch_u16_nb<8>(ctx, slots, nb, reverse);
 }
 
+// FV_OPT_ROW_CODES — the packed 16-bit kernel leaves, beside every score row it writes, the row's 16-bit codes and tile
+// maxima, and a launch all of whose incoming rows have them copies them instead of quantising the floats again
+// (fv_kernels.hip.inc, trellis_step_u16).  The host knows which kernel wrote each row: every step launch comes through
+// launch_step_kernel, which finds the slots' rows in d_rows, hands the packed kernel their code rows and records what the
+// launch leaves.  Rows outside d_rows (checkpoints), rows the other kernels wrote and rows past the code buffers have none.
+// auto (profiles/row_codes_ab.json): the batched launches only, from the smallest K at which their part
+// of a decode was measured to gain (K = 2048: 0.78 -> 0.73 ms; nothing at 512 and 1024) — small contexts keep their device
+// bytes.  The single-task launches of the whole-sequence pass lose on the route (8.4 -> 8.9 us per step at K = 3965: writing
+// the codes in the launch's tail costs more than the shorter prologue saves), so under auto they neither read nor write codes.
+constexpr int ROW_CODES_AUTO_MIN_K = 2048;
+constexpr int ROW_CODES_AUTO_FAMILIES = 2;       // bit 0 single-task launches, bit 1 batched launches
+
+int coded_row_index(const fv_ctx *ctx, const float *row)
+{
+    if (!row || row < ctx->d_rows.p || row >= ctx->d_rows.p + ctx->d_rows.n) return -1;
+    const size_t off = (size_t)(row - ctx->d_rows.p);
+    if (off % (size_t)ctx->nrows) return -1;
+    const size_t r = off / (size_t)ctx->nrows;
+    return r < ctx->row_coded.size() ? (int)r : -1;
+}
+
+// the code rows for `pairs` passes' score rows (two each); no room for them: the decode runs without the route
+int ensure_row_codes(fv_ctx *ctx, size_t pairs)
+{
+    if (!ctx->row_codes) { ctx->row_coded.clear(); return 0; }
+    const size_t rows = pairs * 2, want = rows * (size_t)ctx->nrows;
+    if (want > ctx->d_rcodes.n || want / fvk::TILE_W > ctx->d_rtmax.n) {
+        if (ctx->d_rcodes.ensure(want) != hipSuccess || ctx->d_rtmax.ensure(want / fvk::TILE_W) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->d_rcodes.release(); ctx->d_rtmax.release();
+            ctx->row_codes = 0; ctx->row_coded.clear();
+            return 0;
+        }
+        // (pad tiles past the last real one are never written: 0xff is code 65535 and a NaN tile maximum, which score_code
+        // turns into 65535 as well)
+        FV_HIP(hipMemsetAsync(ctx->d_rcodes.p, 0xff, ctx->d_rcodes.bytes(), ctx->stream));
+        FV_HIP(hipMemsetAsync(ctx->d_rtmax.p, 0xff, ctx->d_rtmax.bytes(), ctx->stream));
+    }
+    ctx->row_coded.assign(ctx->d_rcodes.n / (size_t)ctx->nrows, 0);
+    return 0;
+}
+
+// init_rows' share: the code rows it writes beside the first row of `n` passes from pass `base` on (NULL: none)
+bool init_rows_coded(fv_ctx *ctx, int base, int n)
+{
+    if (!ctx->row_codes || ctx->csr || (size_t)(base + n) * 2 > ctx->row_coded.size()) return false;
+    for (int q = 0; q < n; ++q) ctx->row_coded[(size_t)(base + q) * 2] = 1;
+    return true;
+}
+
 int launch_step_kernel(fv_ctx *ctx, int kernel, const fvk::TaskSlot *slots, int nb, int reverse)
 {
+    fvk::CodeSlot cs[fvk::MAX_BATCH];
+    const bool packed = kernel == FV_KERNEL_U16_REFINE && (nb <= 1 || !ctx->full_ok || (ctx->opt_debug & 16384) || ctx->forked_batches);
+    bool all_in = packed && ctx->row_codes != 0, all_out = all_in;
+    int rout[fvk::MAX_BATCH];
+    for (int q = 0; q < nb; ++q) {
+        const int rin = coded_row_index(ctx, slots[q].t1_in);
+        rout[q] = coded_row_index(ctx, slots[q].t1_out);
+        const size_t ntp = (size_t)ctx->nrows / fvk::TILE_W;
+        cs[q].c_in = rin >= 0 ? ctx->d_rcodes.p + (size_t)rin * ctx->nrows : nullptr;
+        cs[q].tmax_in = rin >= 0 ? ctx->d_rtmax.p + (size_t)rin * ntp : nullptr;
+        cs[q].c_out = rout[q] >= 0 ? ctx->d_rcodes.p + (size_t)rout[q] * ctx->nrows : nullptr;
+        cs[q].tmax_out = rout[q] >= 0 ? ctx->d_rtmax.p + (size_t)rout[q] * ntp : nullptr;
+        all_in = all_in && rin >= 0 && ctx->row_coded[(size_t)rin];
+        all_out = all_out && rout[q] >= 0;
+    }
+    // a batch only ever shrinks: the rows of a single-task launch are read by single-task launches, so it writes codes only if
+    // those take the route; a batched launch writes them for whichever family reads its rows next
+    const int family = nb <= 1 ? 1 : 2;
+    const bool produce = all_out && (nb > 1 || (ctx->row_codes & 1));
+    ctx->launch_codes = ((all_in && (ctx->row_codes & family)) ? 1 : 0) | (produce ? 2 : 0);
+    ctx->launch_code_slots = cs;
+    for (int q = 0; q < nb; ++q)
+        if (rout[q] >= 0) ctx->row_coded[(size_t)rout[q]] = produce ? 1 : 0;
     switch (kernel) {
     case FV_KERNEL_U16_REFINE:
         // Both filters read the same 16-bit table and give the same bits, so the choice is per launch: the packed
@@ -394,10 +471,12 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
         if (ctx->csr)
             hipLaunchKernelGGL(fvk::init_rows_csr, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->CRptr.p,
                                ctx->CRcol.p, ctx->CRlog.p, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, ctx->d_rows.p, K);
-        else
-        hipLaunchKernelGGL(fvk::init_rows, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch,
-                           ctx->LA64.p, ctx->nrows, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p,
-                           ctx->d_rows.p, K);
+        else {
+            const bool coded = init_rows_coded(ctx, base, ch.n);
+            hipLaunchKernelGGL(fvk::init_rows, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch,
+                               ctx->LA64.p, ctx->nrows, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p,
+                               ctx->d_rows.p, K, coded ? ctx->d_rcodes.p : nullptr, coded ? ctx->d_rtmax.p : nullptr, -1.0f / ctx->qscale);
+        }
         FV_HIP(hipGetLastError());
     }
     const int maxlen = passes[0].R - passes[0].L;
@@ -635,9 +714,12 @@ int run_flat_full(fv_ctx *ctx, int kernel, int T)
         if (ctx->csr)
             hipLaunchKernelGGL(fvk::init_rows_csr, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->CRptr.p,
                                ctx->CRcol.p, ctx->CRlog.p, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_snap.p, ctx->d_rows.p, K);
-        else
+        else {
+            const bool coded = init_rows_coded(ctx, base, ch.n);
             hipLaunchKernelGGL(fvk::init_rows, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->LA64.p, ctx->nrows,
-                               ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_snap.p, ctx->d_rows.p, K);
+                               ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_snap.p, ctx->d_rows.p, K,
+                               coded ? ctx->d_rcodes.p : nullptr, coded ? ctx->d_rtmax.p : nullptr, -1.0f / ctx->qscale);
+        }
         FV_HIP(hipGetLastError());
     }
     if (two) {
@@ -808,7 +890,8 @@ int full_setup(fv_ctx *ctx)
 int launch_init_rows(fv_ctx *ctx, const fvk::PassChunk &ch, float *rows)
 {
     hipLaunchKernelGGL(fvk::init_rows, dim3((ctx->K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch,
-                       ctx->LA64.p, ctx->nrows, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, rows, ctx->K);
+                       ctx->LA64.p, ctx->nrows, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, rows, ctx->K,
+                       static_cast<unsigned short *>(nullptr), static_cast<float *>(nullptr), 0.0f);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -883,8 +966,10 @@ namespace {
 // choice for the model and of the sequence, the kernel choice itself, the 16-bit table of a model beyond the float32
 // kernels' limit (built on the device on first use) and the workspace for `rows_needed` passes in flight.  (The LDS
 // attributes of every step kernel, fvi::full_setup, are set once by fv_create.)
-int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &kernel, int nscores = 1)
+int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &kernel, int nscores = 1, bool auto_codes = false)
 {
+    ctx->row_codes = 0;
+    ctx->row_coded.clear();
     // Beyond the float32 kernels' LDS limit (one score row of K floats) two routes remain:
     //   * the packed 16-bit kernel — a row of 16-bit score codes is half the bytes (K <= 65536); it needs every model entry
     //     in [0,1], and its table is built on the device on first use;
@@ -950,7 +1035,14 @@ int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &ker
         ctx->qscale = -stepf;
         ctx->laq16_ready = true;
     }
-    return fvi::ensure_workspace(ctx, T, rows_needed, nscores);
+    if (int rc = fvi::ensure_workspace(ctx, T, rows_needed, nscores)) return rc;
+    // FV_OPT_ROW_CODES: which launch families of the packed kernel take their score codes from the producer (auto_codes: the
+    // caller is a decode auto was measured on — fv_decode_full of one sequence; the others take the route under 2 only)
+    if (kernel == FV_KERNEL_U16_REFINE && !ctx->vanilla) {
+        const int o = ctx->opt_row_codes;
+        ctx->row_codes = o == 2 ? 3 : o == 3 ? 1 : o == 4 ? 2 : (o == 1 && auto_codes && ctx->K >= ROW_CODES_AUTO_MIN_K) ? ROW_CODES_AUTO_FAMILIES : 0;
+    }
+    return ensure_row_codes(ctx, rows_needed);
 }
 
 // statistics of a full-state decode about to start: the table bytes a step of `kernel` streams
@@ -976,7 +1068,7 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
     size_t most = 1;
     std::vector<std::vector<fv::Pass>> gens = fvi::deal_passes(ctx, plan, &most);
     int kernel = FV_KERNEL_AUTO;
-    if ((rc = prepare_full(ctx, ob, T, most, kernel))) return rc;
+    if ((rc = prepare_full(ctx, ob, T, most, kernel, 1, true))) return rc;
     start_full_stats(ctx, kernel, plan.generations());
 
     // the flat form of the right-hand generations: one device, one sequence, the reference's task tree, nothing that
@@ -1000,6 +1092,7 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
             const int wrc = fvi::ensure_flat_workspace(ctx, T, ctx->flat_plan.passes.size(), ctx->flat_plan.arg_rows, ctx->flat_plan.chain_len);
             if (wrc == FV_ERR_NOMEM) { flat = false; ctx->detail.clear(); }
             else if (wrc) return wrc;
+            else if ((rc = ensure_row_codes(ctx, std::max(most, ctx->flat_plan.passes.size())))) return rc;
         }
     }
 
@@ -1206,7 +1299,8 @@ int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *pat
         ch.n = 1;
         ch.p[0] = fvk::PassDesc{ 0, T - 1, 1, 1, 0 };
         hipLaunchKernelGGL(fvk::init_rows, dim3((K + 255) / 256, 1), dim3(256), 0, ctx->stream, ch, ctx->LA64.p, nrows,
-                           ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, ctx->d_ckpt.p, K);
+                           ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, ctx->d_ckpt.p, K,
+                           static_cast<unsigned short *>(nullptr), static_cast<float *>(nullptr), 0.0f);
         FV_HIP(hipGetLastError());
     }
     // first pass (:213-232)

@@ -118,6 +118,15 @@ struct fv_ctx {
     DevBuf<int> d_ob, d_ans, d_bp, d_gather;
     DevBuf<float> d_rows, d_score, d_ckpt;            // d_ckpt: kept score rows of fv_decode_checkpoint
     DevBuf<unsigned long long> d_counters;
+    // FV_OPT_ROW_CODES (fv_full.hip, launch_step_kernel): beside every score row of d_rows its 16-bit codes [nrows] and
+    // its tile maxima [nrows / 16], allocated only for decodes that take the route (row_codes != 0).  row_coded[r]: row r
+    // of d_rows (in units of nrows floats) was last written by a kernel that left its codes — the host knows, launch by launch.
+    DevBuf<unsigned short> d_rcodes;
+    DevBuf<float> d_rtmax;
+    std::vector<unsigned char> row_coded;
+    int row_codes = 0;       // the decode in flight: bit 0 single-task launches take the route, bit 1 batched launches
+    int launch_codes = 0;    // StepArgs::codes of the launch launch_step_kernel is making
+    const void *launch_code_slots = nullptr;   // ... and its fvk::CodeSlot array (valid during that call)
     // FV_OPT_FLAT_GENERATIONS (fv_full.hip, run_flat_full): snapshot S of the whole-sequence chain, the private arg rows of
     // the generations >= 2, the chain of every right-hand pass and the pass table the back-track and the resolver read
     DevBuf<int> d_snap, d_flat_bp, d_chain;
@@ -158,6 +167,7 @@ struct fv_ctx {
     int opt_max_batch = fvk::MAX_BATCH;
     int opt_profile = 0;
     int opt_flat = 1;        // FV_OPT_FLAT_GENERATIONS: 0 off, 1 auto, 2 on
+    int opt_row_codes = 1;   // FV_OPT_ROW_CODES: 0 off, 1 auto, 2 on; 3 / 4 (measurements): single-task / batched launches only
     int vanilla = 0;         // set for the duration of fv_decode_vanilla
     int opt_csr_mem = 0;     // FV_OPT_DEBUG bit 31: trellis_step_csr / trellis_step_csr_f64 read their score rows from memory at any K
     int opt_debug = 0;       // FV_OPT_DEBUG bits: 1 skip refine (timing only), 2 no reverse sweep, 4 alternate unroll, 8 full last step,
@@ -205,7 +215,7 @@ struct fv_ctx {
         f(LA32); f(LB32T); f(LA16); f(LAQ16); f(SPdata); f(SPoff); f(SPnwb); f(LA64); f(LB64T); f(LPi64);
         f(CSk); f(CSq); f(CS64); f(CSoff); f(CSnwb); f(CRptr); f(CRcol); f(CRlog);
         f(E32); f(E64); f(d_emflags); f(EMap);
-        f(d_ob); f(d_ans); f(d_bp); f(d_gather); f(d_rows); f(d_score); f(d_ckpt); f(d_counters); f(d_pack);
+        f(d_ob); f(d_ans); f(d_bp); f(d_gather); f(d_rows); f(d_rcodes); f(d_rtmax); f(d_score); f(d_ckpt); f(d_counters); f(d_pack);
         f(d_snap); f(d_flat_bp); f(d_chain); f(d_flat);
         f(d_hval); f(d_scores); f(d_slot_val); f(d_hstate); f(d_slot_state); f(d_flags); f(LA64R); f(LAQ16R); f(d_qaux);
         f(d_tie_list); f(d_cut); f(d_cand); f(d_cand_count); f(d_dupwin); f(d_doubt); f(d_doubt_count); f(d_needfull);

@@ -48,6 +48,16 @@ struct TaskSlot {
     const double *tmp64_row; // LB64T + ob[j]*K (vanilla arithmetic only)
 };
 
+// FV_OPT_ROW_CODES (trellis_step_u16 only; NULL where a row has no code row beside it): the 16-bit codes of a slot's rows,
+// linear in k and relative to the maximum of their own 16-column tile, and those tile maxima.  (Beside TaskSlot, not in it:
+// the arguments of the kernels that never read them stay as they are.)
+struct CodeSlot {
+    const unsigned short *c_in;   // [nrows] codes of t1_in (read only when StepArgs::codes bit 0 is set)
+    const float *tmax_in;         // [nrows / 16]
+    unsigned short *c_out;        // [nrows] codes of t1_out (written only when StepArgs::codes bit 1 is set)
+    float *tmax_out;              // [nrows / 16]
+};
+
 template <int NB>
 struct StepArgs {
     const void *LA;          // LA32 or LA64
@@ -69,7 +79,11 @@ struct StepArgs {
     // result of the slabs below row_lo, which stands unless a row of this slab is strictly greater (strict '>', ascending k).
     // Every launch leaves the EXACT best of its rows (the filter kernels refine inside the slab), so the merge is exact.
     int row_lo, srows, merge;
+    // trellis_step_u16 only — FV_OPT_ROW_CODES.  bit 0: every slot's incoming row has its codes beside it (c_in / tmax_in):
+    // the prologue copies them instead of quantising the float row.  bit 1: write the codes of the outgoing rows.
+    int codes;
     TaskSlot t[NB];
+    CodeSlot c[NB];
 };
 
 
@@ -600,6 +614,25 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step(const StepArgs<NB> args
 // rows, exactly as the f32 filter kernels do.  If the column minimum sits within a window of saturation, cells
 // whose sum saturated could still matter: every lane of that column re-walks its rows (rare: a column none of
 // whose live predecessors lies within 65534 steps ~ max|log A| of the row maximum).
+//
+// FV_OPT_ROW_CODES (StepArgs::codes).  Every workgroup of a launch used to quantise the whole incoming row for itself
+// (ntiles times the same work per task).  Instead the workgroup that PRODUCES a 16-column tile w of a row leaves, beside
+// the floats, tmax[w] = the maximum of the tile's real columns (-FLT_MAX if none is reachable) and the codes
+// p(k) = score_code(tmax[w], v_k) relative to it; the consumer takes Mx = max_w tmax[w] (the exact row maximum: the same
+// bits as the fold over the floats), d_w = score_code(Mx, tmax[w]) and stages c'(k) = p(k) (+sat) d_w.
+//   * Distance.  p and d_w are each one rne of a float quotient whose own arithmetic error is below 0.012 step (the
+//     "0.51" above is 0.5 + that), so |step c'(k) - (Mx - v_k)| <= 1.024 step where neither saturated: twice today's term.
+//     Per cell |e| <= 1.03 step + dmax, and the window grows by one rounding on each side of the comparison:
+//     z_a <= z_b + (2.05 step + 2 dmax + 2U) / step.  The refine adds 3.1 code units to (2 dmax + 2U) / step where 1.02 are
+//     needed; a launch on this route adds 4.2 where 2.05 are: the same slack of two units, a window 1.1 units wider, and
+//     only on launches that take the route (the others keep 3.1).
+//   * Saturation.  c'(k) = 65535 in three cases: v_k unreachable (never a winner, unless nothing is: then Zc = 65535 and
+//     every row is walked); p(k) saturated, i.e. (tmax[w] - v_k) / step >= 65534.5; or the add did, p(k) + d_w >= 65535
+//     (d_w = 65535, a tile further than the code range below Mx, included).  In the last two the unclamped code
+//     rne((tmax - v_k) / step) + rne((Mx - tmax) / step) is >= 65534, it obeys the distance bound as any other, and so does
+//     its unclamped sum z* >= 65534 with the table code: if such a cell can attain the exact maximum, Zc + (2.05 + ...) >=
+//     z* >= 65534, and with the two units of slack thr = Zc + W >= 65535 — the guard that walks every row exactly.  The
+//     guard therefore covers every cell whose code saturated, wherever it did.
 typedef unsigned short fv_u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned int pk_adds(unsigned int a, unsigned int b)
 {
@@ -620,6 +653,11 @@ __device__ __forceinline__ unsigned int score_code(float mx, float v, float inv_
     const float q = (mx - v) * inv_step;                   // >= 0; +inf / NaN for unreachable entries or an empty row
     return (v > -0.5f * FLT_MAX && q < 65534.5f) ? (unsigned int)__float2uint_rn(q) : 65535u;
 }
+
+// FV_OPT_ROW_CODES: every form but one has both prologues.  The 16-wave whole-tile form at eight tasks (FV_OPT_DEBUG bit 13
+// only) stands at 120 of its 128 VGPRs and spills with a second prologue in it: it keeps the one it has (the host clears
+// bit 0 of StepArgs::codes for it) and still writes the codes of its outgoing rows.
+template <int NB, bool DB, int NWV> constexpr bool u16_takes_codes() { return !(NB == 8 && NWV == 16 && !DB); }
 
 template <int NB, int U, bool DB, int NWV>
 __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> args)
@@ -656,25 +694,75 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
     // quads (4 consecutive rows) of each score row held by this thread: QPT per task cover 4096 rows, any more are
     // re-read in a loop (K > 4096)
     constexpr int QPT = 1024 / (NWV * 64);
-    float4 v0[QPT][NB];
-#pragma unroll
-    for (int h = 0; h < QPT; ++h) {
-        const int q = min(h * (NWV * 64) + tid, nq4 - 1);
-#pragma unroll
-        for (int t = 0; t < NB; ++t) v0[h][t] = reinterpret_cast<const float4 *>(args.t[t].t1_in)[q];
-    }
-    // keep the scheduler from sinking loads next to their uses (it would, to save registers: one full memory
-    // latency per task instead of one for all of them) or from hoisting the table loads above the rows
-    __builtin_amdgcn_sched_barrier(0);
     uint4 cur[U], nxt[DB ? U : 1];
+    // the first table loads and the emission terms, requested behind a launch's row loads on either route below
+    auto request_table = [&]() {
+        // keep the scheduler from sinking loads next to their uses (it would, to save registers: one full memory
+        // latency per task instead of one for all of them) or from hoisting the table loads above the rows
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int u = 0; u < U; ++u)
-        if (u < nj) cur[u] = LAt[(size_t)block_of(u) * (4 * TILE_W)];
-    __builtin_amdgcn_sched_barrier(0);
+        for (int u = 0; u < U; ++u)
+            if (u < nj) cur[u] = LAt[(size_t)block_of(u) * (4 * TILE_W)];
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int t = 0; t < NB; ++t) tmp[t] = args.t[t].tmp_row[min(col, K - 1)];          // not needed before the refine; pad columns: never stored
-    __builtin_amdgcn_sched_barrier(0);
-    {
+        for (int t = 0; t < NB; ++t) tmp[t] = args.t[t].tmp_row[min(col, K - 1)];          // not needed before the refine; pad columns: never stored
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // FV_OPT_ROW_CODES (workgroup-uniform): the rows came with their codes.  A thread copies chunks of 8 codes (16 bytes; chunk
+    // ch lies in tile ch / 2), the first held in registers as v0 is on the other route, and every wave reads the tile maxima for
+    // itself — four per lane cover 256 tiles, an index past the last tile repeats it, which a maximum does not mind.  (The
+    // two routes are two whole branches, table request included: registers of the one are not live in the other.)
+    const bool coded = u16_takes_codes<NB, DB, NWV>() && (args.codes & 1) != 0;
+    const int nch = nrows >> 3;
+    if (coded) {
+        uint4 cv[NB];
+        float tw[NB], tm[NB][4];
+        const int ch = min(tid, nch - 1);
+#pragma unroll
+        for (int t = 0; t < NB; ++t) cv[t] = reinterpret_cast<const uint4 *>(args.c[t].c_in)[ch];
+        auto request_maxima = [&]() {
+#pragma unroll
+            for (int t = 0; t < NB; ++t) {
+                tw[t] = args.c[t].tmax_in[ch >> 1];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) tm[t][j] = args.c[t].tmax_in[min(lane + 64 * j, args.ntiles - 1)];
+            }
+        };
+        // (eight tasks: the 40 maxima are requested behind the table instead — ahead of it the 16-wave whole-tile form runs out of registers)
+        if constexpr (NB < 8) request_maxima();
+        request_table();
+        if constexpr (NB >= 8) request_maxima();
+        // the row maximum from the tile maxima, in every wave for itself: no LDS round, no barrier
+#pragma unroll
+        for (int t = 0; t < NB; ++t) {
+            float x = fmaxf(fmaxf(tm[t][0], tm[t][1]), fmaxf(tm[t][2], tm[t][3]));
+            for (int i = 256 + lane; i < args.ntiles; i += 64) x = fmaxf(x, args.c[t].tmax_in[i]);       // K > 4096 only
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) x = fmaxf(x, __shfl_xor(x, m));
+            Mx[t] = x;
+        }
+        // codes relative to the tile maximum -> relative to the row maximum: one saturating add of d_w per pair
+        auto put = [&](int ch, int t, const uint4 &p, float tmax_w) {
+            const unsigned int d = score_code(Mx[t], tmax_w, inv_step), dd = d | (d << 16);
+            *reinterpret_cast<uint4 *>(T1c + (size_t)t * npairs + 4 * ch) = make_uint4(pk_adds(p.x, dd), pk_adds(p.y, dd), pk_adds(p.z, dd), pk_adds(p.w, dd));
+        };
+        if (tid < nch) {
+#pragma unroll
+            for (int t = 0; t < NB; ++t) put(tid, t, cv[t], tw[t]);
+        }
+        for (int ch = NWV * 64 + tid; ch < nch; ch += NWV * 64) {       // more rows than 8 per thread
+#pragma unroll
+            for (int t = 0; t < NB; ++t) put(ch, t, reinterpret_cast<const uint4 *>(args.c[t].c_in)[ch], args.c[t].tmax_in[ch >> 1]);
+        }
+    } else {
+        float4 v0[QPT][NB];
+#pragma unroll
+        for (int h = 0; h < QPT; ++h) {
+            const int q = min(h * (NWV * 64) + tid, nq4 - 1);
+#pragma unroll
+            for (int t = 0; t < NB; ++t) v0[h][t] = reinterpret_cast<const float4 *>(args.t[t].t1_in)[q];
+        }
+        request_table();
         // row maxima over the K real entries (pads of a score row are zero: excluded)
         float *redM = reinterpret_cast<float *>(redZ);           // [NB][NWV], free until the column reduction
         float pm[NB];
@@ -874,7 +962,7 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
                 const float zz = fabsf(Mx[t] + tmp[t]) + 65536.0f * step + 1.0f;
                 const unsigned int eb = __float_as_uint(zz) & 0x7f800000u;
                 const float Uf = (eb > (24u << 23) && eb < 0x7f800000u) ? __uint_as_float(eb - (23u << 23)) : (eb >= 0x7f800000u ? 0.0f : FLT_MIN);
-                const float wf = (2.0f * Uf + args.window) * inv_step + 3.1f;
+                const float wf = (2.0f * Uf + args.window) * inv_step + (coded ? 4.2f : 3.1f);     // (two roundings per score code on the row-codes route)
                 const unsigned int W = wf < 65535.0f ? (unsigned int)wf + 1u : 65535u;
                 const unsigned int thr = Zc[t] + W;
                 if (thr >= 65535u) {                              // saturated sums could matter: exact walk of every row
@@ -992,6 +1080,18 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
             // reference: score starts at -FLT_MAX with arg = -1 and only a strictly greater ktmp replaces it
             args.t[w].t1_out[col] = any ? r : -FLT_MAX;
             args.t[w].bp_out[col] = any ? kb : -1;
+        }
+        if (args.codes & 2) {
+            // FV_OPT_ROW_CODES: the tile's maximum over its real columns and every column's code relative to it, beside the floats
+            // (every lane holds its column's result after wave_best; pad columns count as unreachable)
+            const float val = (col < K && any) ? r : -FLT_MAX;
+            float tmx = val;
+#pragma unroll
+            for (int m = 1; m < TILE_W; m <<= 1) tmx = fmaxf(tmx, __shfl_xor(tmx, m));
+            if (lane < TILE_W) {
+                args.c[w].c_out[col] = (unsigned short)score_code(tmx, val, inv_step);
+                if (lane == 0) args.c[w].tmax_out[tile] = tmx;
+            }
         }
     }
 }
@@ -1602,14 +1702,29 @@ static inline size_t csr_f64_lds_bytes(int nrows, bool mem)
 // A negative Ans[L-1] (beam miss, FLASH_BS only) selects the Pi row: the reference reads A[-1][i],
 // which aliases Pi[i] in its VIT struct.
 __global__ void init_rows(const PassChunk ch, const double *LA64, int nrows, const double *LB64T,
-                          const double *LPi64, const int *ob, const int *ans, float *rows, int K)
+                          const double *LPi64, const int *ob, const int *ans, float *rows, int K,
+                          unsigned short *codes, float *tmax, float inv_step)
 {
     const PassDesc p = ch.p[blockIdx.y];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= K) return;
-    int st = p.from_pi ? -1 : ans[p.L - 1];
-    const double x = st < 0 ? LPi64[i] : LA64[tab_index<4>(st, i, nrows)];
-    rows[p.row_off + i] = (float)(x + LB64T[(size_t)ob[p.L] * K + i]);
+    float v = FV_NEG_INF;
+    if (i < K) {
+        int st = p.from_pi ? -1 : ans[p.L - 1];
+        const double x = st < 0 ? LPi64[i] : LA64[tab_index<4>(st, i, nrows)];
+        v = (float)(x + LB64T[(size_t)ob[p.L] * K + i]);
+        rows[p.row_off + i] = v;
+    }
+    // FV_OPT_ROW_CODES (codes != NULL): the row's 16-bit codes per 16-column tile and the tile maxima, as trellis_step_u16
+    // leaves them beside every row it writes (16 consecutive lanes hold a tile; its pad columns count as unreachable)
+    if (codes) {
+        float tmx = v;
+#pragma unroll
+        for (int m = 1; m < TILE_W; m <<= 1) tmx = fmaxf(tmx, __shfl_xor(tmx, m));
+        if (i < (K + TILE_W - 1) / TILE_W * TILE_W) {
+            codes[p.row_off + i] = (unsigned short)score_code(tmx, v, inv_step);
+            if ((i & (TILE_W - 1)) == 0) tmax[(p.row_off + i) / TILE_W] = tmx;
+        }
+    }
 }
 
 // End state of the whole-sequence pass, reference FLASH:186-196: ascending scan with strict '>'

@@ -73,6 +73,16 @@ enum {
                                fv_decode_full_batch, FV_OPT_PROFILE, FV_MODE_SINGLE_PASS, fv_decode_vanilla / _checkpoint,
                                FV_OPT_DEBUG bit 6, or when the device has no room for the extra workspace (score rows of all
                                right-hand passes, private arg rows of the generations >= 2, the snapshot and the chains) */
+    FV_OPT_ROW_CODES = 6,   /* the packed 16-bit step kernel (FV_KERNEL_U16_REFINE): 0 off, 1 auto (default), 2 on wherever that kernel
+                               runs.  On: the kernel leaves, beside every score row it writes, the row's 16-bit codes relative to the
+                               maximum of their 16-column tile and those maxima, and a launch all of whose incoming rows have them
+                               copies them (one saturating add per pair) instead of folding the row maximum and quantising the
+                               float row again in every workgroup.  The refine window of such a launch is 1.1 code
+                               units wider; paths, scores and return codes are those of 0: speed only.  Auto: the batched launches
+                               (right-hand passes) of fv_decode_full of one sequence at K >= 2048, where the route was measured to
+                               win; the single-task launches of the whole-sequence pass lose on it and keep their prologue.  Smaller
+                               models, fv_decode_full_batch and the test hooks take the route under 2 only.  3 / 4 (measurements):
+                               only single-task / only batched launches take it.  Costs 2.25 bytes per score-row entry of device memory where taken */
     FV_OPT_DEBUG = 100,     /* UNSTABLE: kernel-tuning switches (a bit mask) that select alternative forms of a kernel or of the
                                launch schedule.  Every bit the library accepts is speed-only — the parity tests run each
                                alternative against the same goldens (tests/test_boundary.py checks that no accepted value

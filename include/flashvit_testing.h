@@ -214,6 +214,11 @@ int fv_test_beam_select(fv_ctx *ctx, int K, int beam, int s, const fv_test_selec
 #define FV_TV_CSR64_NB4      (1ull << (FV_TV_CSR64_SHIFT + 2))   /* trellis_step_csr_f64<4, *> */
 #define FV_TV_CSR64_NB8      (1ull << (FV_TV_CSR64_SHIFT + 3))   /* trellis_step_csr_f64<8, *> */
 #define FV_TV_CSR64_MEM      (1ull << (FV_TV_CSR64_SHIFT + 4))   /* trellis_step_csr_f64<*, true> */
+/* Not an instantiation but a route: set IN ADDITION by every trellis_step_u16 launch whose prologue copied the score codes
+ * its producers left (FV_OPT_ROW_CODES) instead of quantising the float rows.  Never set while that option resolves to off,
+ * as it does for fv_test_forward under auto. */
+#define FV_TV_ROW_CODES_SHIFT 63
+#define FV_TV_ROW_CODES      (1ull << FV_TV_ROW_CODES_SHIFT)
 
 #ifdef __cplusplus
 }
