@@ -51,6 +51,21 @@ int launch_beam_step(fv_ctx *ctx, const fvb::BeamStepArgs &a, hipStream_t st)
 {
     const int K = ctx->K, beam = a.beam;
     auto record = [&](unsigned long long bit) { if (ctx->test_record) ctx->test_variants |= bit; };
+    if (ctx->csr) {
+        // A model set by fv_set_model_sparse (the entry points let it through under FV_OPT_SPARSE_BEAM only): no row to
+        // gather — the list's entries scatter their CSR rows into the accumulators, then one K-wide finish.
+        record(FV_TV_BEAM_CSR);
+        fvb::BeamCsrArgs ca;
+        ca.a = a;
+        ca.m.ptr = ctx->CRptr.p; ca.m.col = ctx->CRcol.p; ca.m.log = ctx->CRlog.p;
+        ca.acc = ctx->d_csr_acc.p; ca.tieval = ctx->d_csr_tie.p;
+        const int groups = (fvb::beam_pitch(beam) + fvb::CSR_SCATTER_WAVES - 1) / fvb::CSR_SCATTER_WAVES;
+        hipLaunchKernelGGL(fvb::beam_scatter_csr, dim3(groups, a.n), dim3(fvb::CSR_SCATTER_WAVES * 64), 0, st, ca);
+        hipLaunchKernelGGL(fvb::beam_finish_csr, dim3((K + fvb::CSR_FINISH_BLOCK - 1) / fvb::CSR_FINISH_BLOCK, a.n),
+                           dim3(fvb::CSR_FINISH_BLOCK), 0, st, ca);
+        FV_HIP(hipGetLastError());
+        return 0;
+    }
     // The 16-bit filter kernel moves a quarter of the bytes but has two more dependent phases (window,
     // float64 refine): measured at K = 16384, B = 256 it takes 13.7 us + 2.6 us per extra pass of the
     // launch against 10.6 + 5.0 for the float64 kernel, so it is used from ~80 MB of float64 rows per
@@ -95,7 +110,13 @@ unsigned long long select_variant(fvb::SelKernel k)
         { fvb::topb_select<16, true>, FV_TS_SEL16_LISTED }, { fvb::topb_select<16, false>, FV_TS_SEL16_DERIVED },
         { fvb::topb_select<fvb::SEL_MAX_ROUNDS, true>, FV_TS_SEL64_LISTED }, { fvb::topb_select<fvb::SEL_MAX_ROUNDS, false>, FV_TS_SEL64_DERIVED },
         { fvb::topb_select_cand<8, true>, FV_TS_CAND8_LISTED }, { fvb::topb_select_cand<8, false>, FV_TS_CAND8_DERIVED },
-        { fvb::topb_select_cand<16, true>, FV_TS_CAND16_LISTED }, { fvb::topb_select_cand<16, false>, FV_TS_CAND16_DERIVED } };
+        { fvb::topb_select_cand<16, true>, FV_TS_CAND16_LISTED }, { fvb::topb_select_cand<16, false>, FV_TS_CAND16_DERIVED },
+        // (the CSR instantiations differ in the resolve code only: same bits)
+        { fvb::topb_select<4, true, true>, FV_TS_SEL4_LISTED }, { fvb::topb_select<4, false, true>, FV_TS_SEL4_DERIVED },
+        { fvb::topb_select<16, true, true>, FV_TS_SEL16_LISTED }, { fvb::topb_select<16, false, true>, FV_TS_SEL16_DERIVED },
+        { fvb::topb_select<fvb::SEL_MAX_ROUNDS, true, true>, FV_TS_SEL64_LISTED }, { fvb::topb_select<fvb::SEL_MAX_ROUNDS, false, true>, FV_TS_SEL64_DERIVED },
+        { fvb::topb_select_cand<8, true, true>, FV_TS_CAND8_LISTED }, { fvb::topb_select_cand<8, false, true>, FV_TS_CAND8_DERIVED },
+        { fvb::topb_select_cand<16, true, true>, FV_TS_CAND16_LISTED }, { fvb::topb_select_cand<16, false, true>, FV_TS_CAND16_DERIVED } };
     for (const auto &e : tab) if (e.k == k) return e.bit;
     return 0;
 }
@@ -131,8 +152,9 @@ int launch_beam_select(fv_ctx *ctx, int K, int beam, int T, const fvb::ResolveCt
     // K > 65536 (FV_OPT_DEBUG bit 22: any K): beyond the 64 rounds the register kernels hold, every selection runs in the
     // lean kernel — on the candidate list where there is one, otherwise over the K scores in memory
     const bool many = K > fvb::SEL_MAX_ROUNDS * fvb::SEL_BLOCK || (ctx->opt_debug & (1 << 22));
-    fvb::SelKernel lean = (s >= 2 || many) ? fvb::sel_cand_kernel_for(K, cand_cap, listed, many) : nullptr;
-    const fvb::SelKernel kernel = lean ? lean : fvb::sel_kernel_for(K, listed);
+    const bool csr = rcx.csr.ptr != nullptr;        // a sparse-set model's decode: the instantiations that resolve on its rows
+    fvb::SelKernel lean = (s >= 2 || many) ? fvb::sel_cand_kernel_for(K, cand_cap, listed, many, csr) : nullptr;
+    const fvb::SelKernel kernel = lean ? lean : fvb::sel_kernel_for(K, listed, csr);
     if (ctx->test_record) ctx->test_selects |= select_variant(kernel);
     hipLaunchKernelGGL(kernel, dim3(count), dim3(fvb::SEL_BLOCK), fvb::sel_lds(beam), st, a);
     FV_HIP(hipGetLastError());
@@ -159,6 +181,7 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
     rcx.bp = ctx->d_bp.p; rcx.doubt = ctx->d_doubt.p; rcx.doubt_count = ctx->d_doubt_count.p;
     rcx.b.scores_all = ctx->d_scores.p; rcx.b.hval = ctx->d_hval.p; rcx.b.hstate = ctx->d_hstate.p;
     rcx.b.cut = ctx->d_cut.p; rcx.b.passL = ctx->d_passL.p + pass_off;
+    if (ctx->csr) { rcx.csr.ptr = ctx->CRptr.p; rcx.csr.col = ctx->CRcol.p; rcx.csr.log = ctx->CRlog.p; }
     // members of the heaps of passes [first, first + count) at lock-step s: one launch
     auto select = [&](int first, int count, int s, hipStream_t st) -> int {
         return launch_beam_select(ctx, K, beam, T, rcx, rcx.b.passL + first, count, s,
@@ -269,7 +292,8 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
             r.n = std::min(fvb::BEAM_CHUNK, np - base);
             for (int q = 0; q < r.n; ++q)
                 r.p[q] = fvb::BeamEnd{ passes[base + q].L, passes[base + q].R, passes[base + q].whole ? 1 : 0, passes[base + q].seq };
-            hipLaunchKernelGGL(fvb::beam_resolve, dim3(r.n), dim3(fvb::RESOLVE_BLOCK), fvb::heap_lds(beam), ctx->stream, r);
+            hipLaunchKernelGGL(ctx->csr ? fvb::beam_resolve<true> : fvb::beam_resolve<false>, dim3(r.n), dim3(fvb::RESOLVE_BLOCK),
+                               fvb::heap_lds(beam), ctx->stream, r);
             FV_HIP(hipGetLastError());
         }
         return 0;
@@ -293,8 +317,8 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
         f.tie_count = ctx->d_tie_count.p; f.tie_list = ctx->d_tie_list.p; f.tie_cap = (unsigned int)ctx->d_tie_list.n;
         f.slot_val = ctx->d_slot_val.p; f.slot_state = ctx->d_slot_state.p; f.bp = ctx->d_bp.p;
         f.K = K; f.ld = beam_ld(K); f.beam = beam; f.total = ctx->d_counters.p + 6; f.gate = ctx->d_needfull.p;
-        f.seq_of = seq_of;
-        hipLaunchKernelGGL(fvb::tie_fixup, dim3(512), dim3(256), 0, ctx->stream, f);
+        f.seq_of = seq_of; f.csr = rcx.csr;
+        hipLaunchKernelGGL(ctx->csr ? fvb::tie_fixup<true> : fvb::tie_fixup<false>, dim3(512), dim3(256), 0, ctx->stream, f);
         FV_HIP(hipGetLastError());
     }
     if ((rc = ends(0))) return rc;
@@ -308,7 +332,7 @@ extern "C" int fv_decode_beam(fv_ctx *ctx, const int *ob, int T, int n_split, in
                               int *path_out, float *score_out)
 {
     if (!ctx) return FV_ERR_ARG;
-    if (ctx->csr) { ctx->detail = "fv_decode_beam: not available on a model set by fv_set_model_sparse (the beam kernels gather dense rows)"; return FV_ERR_UNSUPPORTED; }
+    if (ctx->csr && !ctx->opt_sparse_beam) { ctx->detail = "fv_decode_beam: not available on a model set by fv_set_model_sparse (the beam kernels gather dense rows)"; return FV_ERR_UNSUPPORTED; }
     if (ctx->group && ctx->group_rank == 0) {
         if (!path_out || T < 2) return FV_ERR_ARG;
         return fvi::group_run(ctx, T, path_out, score_out, [&](fv_ctx *m, int *path, float *score) {
@@ -334,6 +358,7 @@ int beam_admit(fv_ctx *ctx, int beam) { return beam_admit_k(ctx->K, beam); }
 // device by the first beam decode or test-hook call of a model.
 int beam_tables(fv_ctx *ctx)
 {
+    if (ctx->csr) return 0;          // FV_OPT_SPARSE_BEAM: the kernels read the rows fv_set_model_sparse uploaded; nothing to build
     if (!ctx->LA64R.p) {
         const int ld = beam_ld(ctx->K);
         FV_HIP(ctx->LA64R.ensure((size_t)ctx->K * ld));
@@ -371,12 +396,19 @@ int beam_workspace(fv_ctx *ctx, int T, int beam, int nseq)
     w.add(ctx->d_cut, t * fvb::CUT_W); w.add(ctx->d_cand_count, t);
     if (cap) w.add(ctx->d_cand, t * cap);
     w.add(ctx->d_dupwin, t); w.add(ctx->d_needfull, (size_t)std::max(4, nseq));
+    // a sparse-set model (FV_OPT_SPARSE_BEAM): the scatter accumulators, 12 bytes per (observation, state)
+    if (ctx->csr) { w.add(ctx->d_csr_acc, t * K); w.add(ctx->d_csr_tie, t * K); }
     if (nseq > 0) {
         w.add(ctx->d_seqof, t);
         w.what = "beam batch workspace";
-        w.dominant = "score rows, back-pointers and tie list: " + std::to_string(16ull * t * K);
+        w.dominant = ctx->csr ? "score rows, back-pointers, tie list and scatter accumulators: " + std::to_string(28ull * t * K)
+                              : "score rows, back-pointers and tie list: " + std::to_string(16ull * t * K);
     }
     if (int rc = fvi::ensure_workspace(ctx, T, 1, nseq > 0 ? std::max(nseq, 2) : 1, std::move(w))) return rc;
+    if (ctx->csr) {                  // once per decode: beam_finish_csr clears every cell it reads
+        FV_HIP(hipMemsetAsync(ctx->d_csr_acc.p, 0, t * K * sizeof(unsigned long long), ctx->stream));
+        FV_HIP(hipMemsetAsync(ctx->d_csr_tie.p, 0, t * K * sizeof(unsigned int), ctx->stream));
+    }
     FV_HIP(hipMemsetAsync(ctx->d_cut.p, 0xFF, t * fvb::CUT_W * sizeof(float), ctx->stream));      // NaN: no earlier pass has left a cut here
     FV_HIP(hipMemsetAsync(ctx->d_cand_count.p, 0, t * sizeof(int), ctx->stream));
     FV_HIP(hipMemsetAsync(ctx->d_dupwin.p, 0, t * sizeof(int), ctx->stream));
@@ -427,7 +459,9 @@ int run_beam_generations(fv_ctx *ctx, std::vector<std::vector<fv::Pass>> &gens, 
 // statistics of a beam decode about to start (the float64 rows of the beam's members per step; no density is reported)
 void start_beam_stats(fv_ctx *ctx, const fv::Plan &plan, int beam_width)
 {
-    ctx->start_stats(FV_KERNEL_F64_STREAM, plan.generations(), (long long)beam_width * ctx->K * 8, 0.0);
+    // (a sparse-set model: the float64 logs of the stored entries; an ESTIMATE — 12 bytes per entry of beam_width average rows)
+    if (ctx->csr) ctx->start_stats(FV_KERNEL_CSR_F64, plan.generations(), 12LL * beam_width * ctx->csr_nnz / ctx->K, 0.0);
+    else ctx->start_stats(FV_KERNEL_F64_STREAM, plan.generations(), (long long)beam_width * ctx->K * 8, 0.0);
 }
 
 int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_width, int mode, int *path_out, float *score_out)
@@ -489,7 +523,7 @@ extern "C" int fv_decode_beam_batch(fv_ctx *ctx, const int *ob, const long long 
                                     int mode, int *path_out, float *score_out, int *status_out)
 {
     if (!ctx) return FV_ERR_ARG;
-    if (ctx->csr) { ctx->detail = "fv_decode_beam_batch: not available on a model set by fv_set_model_sparse (the beam kernels gather dense rows)"; return FV_ERR_UNSUPPORTED; }
+    if (ctx->csr && !ctx->opt_sparse_beam) { ctx->detail = "fv_decode_beam_batch: not available on a model set by fv_set_model_sparse (the beam kernels gather dense rows)"; return FV_ERR_UNSUPPORTED; }
     if (ctx->group || ctx->comm || ctx->nranks > 1) {
         ctx->detail = "fv_decode_beam_batch: one device, no communicator and no partition (sequences are not dealt to ranks)";
         return FV_ERR_UNSUPPORTED;
@@ -548,6 +582,12 @@ int test_beam_step_impl(fv_ctx *ctx, int beam, const fv_test_beam_set *sets, int
     FV_HIP(ctx->d_counters.ensure(FV_NCOUNTERS));
     FV_HIP(ctx->d_cand_count.ensure(nsets));
     if (cand_cap) FV_HIP(ctx->d_cand.ensure((size_t)nsets * cand_cap));
+    if (ctx->csr) {
+        FV_HIP(ctx->d_csr_acc.ensure((size_t)nsets * K));
+        FV_HIP(ctx->d_csr_tie.ensure((size_t)nsets * K));
+        FV_HIP(hipMemsetAsync(ctx->d_csr_acc.p, 0, (size_t)nsets * K * sizeof(unsigned long long), ctx->stream));
+        FV_HIP(hipMemsetAsync(ctx->d_csr_tie.p, 0, (size_t)nsets * K * sizeof(unsigned int), ctx->stream));
+    }
     FV_HIP(hipMemcpyAsync(ctx->d_hval.p, hv.data(), hv.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     FV_HIP(hipMemcpyAsync(ctx->d_hstate.p, hs.data(), hs.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     FV_HIP(hipMemcpyAsync(ctx->d_cut.p, cut.data(), cut.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -606,7 +646,7 @@ extern "C" int fv_test_beam_step(fv_ctx *ctx, int beam, const fv_test_beam_set *
 {
     if (!ctx) return FV_ERR_ARG;
     if (fvi::group_size(ctx) > 1) { ctx->detail = "fv_test_beam_step: one device per context"; return FV_ERR_ARG; }
-    if (ctx->csr) { ctx->detail = "fv_test_beam_step: not available on a model set by fv_set_model_sparse"; return FV_ERR_UNSUPPORTED; }
+    if (ctx->csr && !ctx->opt_sparse_beam) { ctx->detail = "fv_test_beam_step: not available on a model set by fv_set_model_sparse"; return FV_ERR_UNSUPPORTED; }
     return fvi::drained(ctx, test_beam_step_impl(ctx, beam, sets, nsets, sym, speculative, theta, next_bound, cand_cap, scores_out,
                                                  bp_out, ties_out, tie_count_out, doubt_out, doubt_counts, cand_out, cand_counts,
                                                  variants_out));

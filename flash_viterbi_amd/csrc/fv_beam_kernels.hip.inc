@@ -70,6 +70,26 @@ __global__ void relayout_rows(const double *t4, double *rm, int K, int nrows, in
     }
 }
 
+// A model set by fv_set_model_sparse has no LA64R: its beam kernels (FV_OPT_SPARSE_BEAM) read the caller's rows by source
+// state — row k = entries ptr[k] .. ptr[k + 1], columns strictly ascending, float64 logs (-inf: a stored 0).
+struct CsrRows {
+    const long long *ptr = nullptr;    // [K + 1]
+    const int *col = nullptr;
+    const double *log = nullptr;
+};
+// log A[state][col] of such a model: the stored log, -inf where the entry is absent (or a stored 0)
+__device__ __forceinline__ double csr_log(const CsrRows &m, int state, int col)
+{
+    long long lo = m.ptr[state];
+    const long long end = m.ptr[state + 1];
+    long long hi = end;
+    while (lo < hi) {                   // first entry whose column is >= col
+        const long long mid = (lo + hi) >> 1;
+        if (m.col[mid] < col) lo = mid + 1; else hi = mid;
+    }
+    return (lo < end && m.col[lo] == col) ? m.log[lo] : -__builtin_huge_val();
+}
+
 struct BeamSlot {
     const float *sval;     // [B] beam values (any order)
     const int *sstate;     // [B] beam states
@@ -127,6 +147,32 @@ __device__ __forceinline__ void append_candidates(const BeamStepArgs &args, int 
         const int pos = off + (int)__popcll(m & ((1ull << (threadIdx.x & 63)) - 1ull));
         if (pos < args.cand_cap) args.cand[(size_t)j * args.cand_cap + pos] = HNode{ v, state };
     }
+}
+
+// What every step kernel does with a finished column (beam_step, beam_step_q16 after their wave combine, beam_finish_csr
+// after unpacking its accumulator), in one place so that the side outputs cannot drift: r = the column's maximum, a = the
+// lowest index of the previous step's list that attains it, t = more than one entry attains it; sval / sst = that list
+// (LDS or memory).  Writes the score and the provisional back-pointer, appends the tie list and the doubtful-column
+// list, and returns whether the score belongs in the step's candidate list (append_candidates, called by whole waves).
+__device__ __forceinline__ bool finish_column(const BeamStepArgs &args, const BeamSlot &ps, const int col, const float r, const int a,
+                                              const int t, const float *sval, const int *sst, const bool spec, const float cut_theta)
+{
+    const bool any = r > -FLT_MAX;                  // score starts at -FLT_MAX, arg = -1 (FLASH_BS:439)
+    ps.scores[col] = any ? r : -FLT_MAX;
+    ps.bp_row[col] = any ? (t ? (sst[a] | TIE_TAG) : sst[a]) : -1;     // arg = -1 reads heap slot 0: State = -1 (:448, :65-70)
+    if (any && t) {
+        const unsigned int at = atomicAdd(args.tie_count, 1u);
+        if (at < args.tie_cap) args.tie_list[at] = make_int2(ps.j, col);
+    }
+    // a column won by an entry that may not survive (a theta-valued duplicate of a speculative list): its score
+    // is an upper bound and its back-pointer provisional until the replay of the previous step has run
+    if (any && spec && sval[a] == cut_theta) {
+        const int at = atomicAdd(ps.doubt_count, 1);
+        if (at < DOUBT_CAP) ps.doubt[at] = col;
+        atomicAdd(&args.counters[3], 1ull);
+        if (atomicExch(ps.dupwin, 1) == 0) atomicAdd(&args.counters[4], 1ull);
+    }
+    return any && r >= ps.cut[CUT_NEXT];
 }
 
 // (a): score_i = max over beam entries of (float)((double)(tmp_i + val) + logA[state][i])  (FLASH_BS:443),
@@ -198,22 +244,7 @@ __global__ __launch_bounds__(NWV * 64) void beam_step(const BeamStepArgs args)
             else if (ov > r) t = ot;
             if (fvk::better(ov, ok, r, a)) { r = ov; a = ok; }
         }
-        const bool any = r > -FLT_MAX;                  // score starts at -FLT_MAX, arg = -1 (FLASH_BS:439)
-        ps.scores[col] = any ? r : -FLT_MAX;
-        ps.bp_row[col] = any ? (t ? (sst[a] | TIE_TAG) : sst[a]) : -1;     // arg = -1 reads heap slot 0: State = -1 (:448, :65-70)
-        if (any && t) {
-            const unsigned int at = atomicAdd(args.tie_count, 1u);
-            if (at < args.tie_cap) args.tie_list[at] = make_int2(ps.j, col);
-        }
-        // a column won by an entry that may not survive (a theta-valued duplicate of a speculative list): its score
-        // is an upper bound and its back-pointer provisional until the replay of the previous step has run
-        if (any && spec && sval[a] == cut_theta) {
-            const int at = atomicAdd(ps.doubt_count, 1);
-            if (at < DOUBT_CAP) ps.doubt[at] = col;
-            atomicAdd(&args.counters[3], 1ull);
-            if (atomicExch(ps.dupwin, 1) == 0) atomicAdd(&args.counters[4], 1ull);
-        }
-        cnd = any && r >= ps.cut[CUT_NEXT];
+        cnd = finish_column(args, ps, col, r, a, t, sval, sst, spec, cut_theta);
         }
         if (args.cand_cap) append_candidates(args, ps.j, cnd, r, col);
     }
@@ -418,20 +449,7 @@ __global__ __launch_bounds__(NWV * 64) void beam_step_q16(const BeamStepArgs arg
                 else if (ov > r) t = ot;
                 if (fvk::better(ov, ok, r, a)) { r = ov; a = ok; }
             }
-            const bool any = r > -FLT_MAX;              // score starts at -FLT_MAX, arg = -1 (FLASH_BS:439)
-            ps.scores[col] = any ? r : -FLT_MAX;
-            ps.bp_row[col] = any ? (t ? (sst[a] | TIE_TAG) : sst[a]) : -1;
-            if (any && t) {
-                const unsigned int at = atomicAdd(args.tie_count, 1u);
-                if (at < args.tie_cap) args.tie_list[at] = make_int2(ps.j, col);
-            }
-            if (any && spec && sval[a] == cut_theta) {          // doubtful column (see beam_step)
-                const int at = atomicAdd(ps.doubt_count, 1);
-                if (at < DOUBT_CAP) ps.doubt[at] = col;
-                atomicAdd(&args.counters[3], 1ull);
-                if (atomicExch(ps.dupwin, 1) == 0) atomicAdd(&args.counters[4], 1ull);
-            }
-            cnd = any && r >= ps.cut[CUT_NEXT];
+            cnd = finish_column(args, ps, col, r, a, t, sval, sst, spec, cut_theta);
         }
         if (args.cand_cap) append_candidates(args, ps.j, cnd, r, col);
     }
@@ -777,6 +795,7 @@ struct ResolveCtx {
     int *bp;                        // [T][K]
     int *doubt; int *doubt_count;   // [T][DOUBT_CAP], [T]
     BeamBase b;
+    CsrRows csr;                    // the CSR instantiations (patch_doubtful<true>) read these instead of LA64R
 };
 struct SelJob {
     const float *scores; float *sval; int *sstate;
@@ -1163,6 +1182,9 @@ __device__ __forceinline__ void replay_step(const ResolveCtx &c, int t, unsigned
 // The doubtful columns of step t against the exact members of step t - 1 (in slot order after replay_step, so the lowest
 // slot among equal maxima is the reference's own tie-break, FLASH_BS:440-446: score AND back-pointer come out exact).
 // If the list overflowed every column is re-evaluated.  One wave per column, NW waves.
+// CSR: the same over a model set by fv_set_model_sparse — log A[state][col] looked up in the state's row (csr_log), one
+// lookup per member and column; the dense instantiation is the code below the branch, as it was.
+template <bool CSR = false>
 __device__ __forceinline__ void patch_doubtful(const ResolveCtx &c, int t, int NW)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1173,6 +1195,31 @@ __device__ __forceinline__ void patch_doubtful(const ResolveCtx &c, int t, int N
     const float *sv = c.b.hval + (size_t)(t - 1) * BP;
     const int *ss = c.b.hstate + (size_t)(t - 1) * BP;
     const float *tmp_row = c.LB32T + (size_t)c.ob[t] * K;
+    if constexpr (CSR) {
+        for (int e = w; e < n; e += NW) {
+            const int col = all ? e : c.doubt[(size_t)t * DOUBT_CAP + e];
+            const float tmp = tmp_row[col];
+            float best = FV_NEG_INF;
+            int arg = INT_MAX;
+            for (int sl = lane; sl < B; sl += 64) {       // ascending slots per lane: the first of equals is kept
+                const float y = fvk::exact_cell(tmp, sv[sl], csr_log(c.csr, ss[sl], col));
+                if (y > best) { best = y; arg = sl; }
+            }
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) {
+                const float ov = __shfl_xor(best, m);
+                const int ok = __shfl_xor(arg, m);
+                if (fvk::better(ov, ok, best, arg)) { best = ov; arg = ok; }
+            }
+            if (lane == 0) {
+                const bool any = best > -FLT_MAX;
+                c.b.scores_all[(size_t)t * K + col] = any ? best : -FLT_MAX;
+                c.bp[(size_t)t * K + col] = any ? ss[arg] : -1;
+            }
+        }
+        wg_publish();
+        return;
+    }
     // the members are the same for every column: a lane's share of them (slots lane, lane + 64, ...) is fetched once, so that
     // a column costs one round of gathers instead of two dependent ones (B <= 1024; beyond that they are re-read)
     constexpr int HOLD = 16;
@@ -1239,6 +1286,7 @@ __device__ __forceinline__ void patch_doubtful(const ResolveCtx &c, int t, int N
 
 // For t = first .. last (ascending): if the scores of step t are not exact yet, decide step t - 1 (exact by then) and
 // re-evaluate step t's doubtful columns.  Every live wave of the workgroup calls this; `bcast` is a shared word.
+template <bool CSR = false>
 __device__ __forceinline__ void resolve_range(const ResolveCtx &c, int L, int first, int last, unsigned char *smem, unsigned int *bcast, int NW)
 {
     for (int t = first; t <= last; ++t) {
@@ -1247,7 +1295,7 @@ __device__ __forceinline__ void resolve_range(const ResolveCtx &c, int L, int fi
         __syncthreads();
         if (!*bcast) continue;
         replay_step(c, t - 1, smem);
-        patch_doubtful(c, t, NW);
+        patch_doubtful<CSR>(c, t, NW);
     }
 }
 
@@ -1305,6 +1353,7 @@ __device__ __forceinline__ bool replay_safe(const ResolveCtx &c, int t, unsigned
 // whole run back to a step with exact scores, or only back to a step whose replay does not depend on what is undecided
 // (replay_safe: that step's members are then decided from its scores as they stand; its own doubtful columns keep their
 // upper bounds, which is what any undecided step's hold).
+template <bool CSR = false>
 __device__ __forceinline__ void resolve_upto(const ResolveCtx &c, int L, int target, unsigned char *smem, unsigned int *bcast, int NW)
 {
     __syncthreads();
@@ -1324,7 +1373,7 @@ __device__ __forceinline__ void resolve_upto(const ResolveCtx &c, int L, int tar
             }
         }
     }
-    resolve_range(c, L, t0 + 1, target, smem, bcast, NW);
+    resolve_range<CSR>(c, L, t0 + 1, target, smem, bcast, NW);
 }
 
 // Does a doubtful column of this step lie inside its beam (score >= theta: its membership, or the value it brings
@@ -1350,7 +1399,7 @@ __device__ __forceinline__ bool doubtful_reach(const ResolveCtx &c, const SelJob
 //   * so does a step whose doubtful columns reach its beam: the undecided steps before it are decided now, the
 //     columns re-evaluated, and the selection repeated on the exact scores (all K of them: the candidate list holds the
 //     stale values).
-template <int R, bool REG, int NT = SEL_BLOCK>
+template <int R, bool REG, int NT = SEL_BLOCK, bool CSR = false>
 __device__ __forceinline__ void select_finish(const SelArgs &args, const SelJob &job, unsigned char *smem, SelShared &sh, int st, const bool dirty)
 {
     const ResolveCtx &c = args.rc;
@@ -1360,7 +1409,7 @@ __device__ __forceinline__ void select_finish(const SelArgs &args, const SelJob 
     const bool reach = dirty && (st == SEL_REPLAY || doubtful_reach(c, job, &sh.sh_sel[0], NT));
     const unsigned long long q1 = __builtin_amdgcn_s_memtime();
     if (reach) {
-        resolve_upto(c, job.L, job.j, smem, &sh.sh_sel[0], NT / 64);
+        resolve_upto<CSR>(c, job.L, job.j, smem, &sh.sh_sel[0], NT / 64);
         const unsigned long long q2 = __builtin_amdgcn_s_memtime();
         if (threadIdx.x == 0) atomicAdd(&c.counters[10], 1ull);
         st = select_body<R, REG, NT>(args, job, sh, 0, false, !args.eager);
@@ -1377,7 +1426,7 @@ __device__ __forceinline__ void select_finish(const SelArgs &args, const SelJob 
     return;
 #endif
     if (dirty && (st == SEL_REPLAY || doubtful_reach(c, job, &sh.sh_sel[0], NT))) {
-        resolve_upto(c, job.L, job.j, smem, &sh.sh_sel[0], NT / 64);
+        resolve_upto<CSR>(c, job.L, job.j, smem, &sh.sh_sel[0], NT / 64);
         if (threadIdx.x == 0) atomicAdd(&c.counters[10], 1ull);
         st = select_body<R, REG, NT>(args, job, sh, 0, false, !args.eager);
     }
@@ -1399,19 +1448,20 @@ __device__ __forceinline__ bool quad_ok(const SelArgs &args, const int C, const 
     // where four waves can repeat the selection at all: K <= 16384)
     return use_cand && C <= QUAD_SEL_ROUNDS * 256 && !args.no_wave && (!dirty || (args.quad_dirty && args.K <= SEL_MAX_ROUNDS * 256));
 }
+template <bool CSR = false>
 __device__ __forceinline__ void select_quad(const SelArgs &args, const SelJob &job, unsigned char *smem, SelShared &sh, const int C, const bool dirty)
 {
     __syncthreads();                                 // every thread has read C (the list's counter is reset below)
     if (threadIdx.x >= 256) return;
     const int st = select_body<QUAD_SEL_ROUNDS, true, 256>(args, job, sh, C, true, !args.eager);
-    select_finish<1, false, 256>(args, job, smem, sh, st, dirty);
+    select_finish<1, false, 256, CSR>(args, job, smem, sh, st, dirty);
 }
 
 // R = rounds held in registers (compile time).  Candidate list of this step (beam_step's epilogue: every score >= a
 // lower bound predicted for the cut): if it holds at least B entries and did not overflow, the B largest scores of
 // the step are the B largest entries of the list, and every score equal to the cut value is in it: the select then
 // reads the list instead of K scores.
-template <int R, bool LISTED>
+template <int R, bool LISTED, bool CSR = false>
 __global__ __launch_bounds__(SEL_BLOCK) void topb_select(const SelArgs args)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1420,15 +1470,15 @@ __global__ __launch_bounds__(SEL_BLOCK) void topb_select(const SelArgs args)
     const int C = (job.cand && args.cand_cap) ? *job.cand_count : 0;
     const bool use_cand = C >= args.beam && C <= args.cand_cap && C <= R * SEL_BLOCK;
     const bool dirty = step_dirty(args.rc, job.j, job.L);
-    if (quad_ok(args, C, use_cand, dirty)) { select_quad(args, job, smem, sh, C, dirty); return; }
+    if (quad_ok(args, C, use_cand, dirty)) { select_quad<CSR>(args, job, smem, sh, C, dirty); return; }
     const int st = select_body<R, true>(args, job, sh, C, use_cand, !args.eager);
-    select_finish<R, true>(args, job, smem, sh, st, dirty);
+    select_finish<R, true, SEL_BLOCK, CSR>(args, job, smem, sh, st, dirty);
 }
 
 // Lean form for the steps that have a candidate list when K needs the 64-round instantiation above (64 key registers
 // + bookkeeping per thread do not fit 128 VGPRs: it spills): RC rounds of registers for the list; if the list
 // turns out unusable (prediction off: rare), the same selection with the K scores re-read from memory in every pass.
-template <int RC, bool LISTED>
+template <int RC, bool LISTED, bool CSR = false>
 __global__ __launch_bounds__(SEL_BLOCK) void topb_select_cand(const SelArgs args)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1437,9 +1487,9 @@ __global__ __launch_bounds__(SEL_BLOCK) void topb_select_cand(const SelArgs args
     const int C = (job.cand && args.cand_cap) ? *job.cand_count : 0;
     const bool use_cand = C >= args.beam && C <= args.cand_cap && C <= RC * SEL_BLOCK;
     const bool dirty = step_dirty(args.rc, job.j, job.L);
-    if (quad_ok(args, C, use_cand, dirty)) { select_quad(args, job, smem, sh, C, dirty); return; }
+    if (quad_ok(args, C, use_cand, dirty)) { select_quad<CSR>(args, job, smem, sh, C, dirty); return; }
     const int st = use_cand ? select_body<RC, true>(args, job, sh, C, true, !args.eager) : select_body<1, false>(args, job, sh, C, false, !args.eager);
-    select_finish<1, false>(args, job, smem, sh, st, dirty);
+    select_finish<1, false, SEL_BLOCK, CSR>(args, job, smem, sh, st, dirty);
 }
 
 // End of a generation, before the pass ends are read (one workgroup of four waves per pass).
@@ -1458,6 +1508,7 @@ struct ResolveArgs {
     BeamEnd p[BEAM_CHUNK];
 };
 constexpr int RESOLVE_BLOCK = 256;
+template <bool CSR = false>
 __global__ __launch_bounds__(RESOLVE_BLOCK) void beam_resolve(const ResolveArgs args)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1467,10 +1518,10 @@ __global__ __launch_bounds__(RESOLVE_BLOCK) void beam_resolve(const ResolveArgs 
     constexpr int NW = RESOLVE_BLOCK / 64;
     if (args.mode == 1) {
         if (args.gate && args.gate[p.seq] == 0) return;
-        resolve_range(c, p.L, p.L + 1, p.R, smem, &bcast, NW);
+        resolve_range<CSR>(c, p.L, p.L + 1, p.R, smem, &bcast, NW);
         return;
     }
-    if (p.whole) { resolve_upto(c, p.L, p.R, smem, &bcast, NW); return; }
+    if (p.whole) { resolve_upto<CSR>(c, p.L, p.R, smem, &bcast, NW); return; }
     const int BP = beam_pitch(c.beam);
     const float *cut = c.b.cut + (size_t)p.R * CUT_W;
     if (threadIdx.x == 0) bcast = 0u;
@@ -1484,14 +1535,20 @@ __global__ __launch_bounds__(RESOLVE_BLOCK) void beam_resolve(const ResolveArgs 
     __syncthreads();
     if (!bcast) return;
     __syncthreads();
-    resolve_upto(c, p.L, p.R, smem, &bcast, NW);
+    resolve_upto<CSR>(c, p.L, p.R, smem, &bcast, NW);
     replay_step(c, p.R, smem);
 }
 
 // smallest instantiation that holds K (a candidate list is never longer than the scores it was taken from)
 typedef void (*SelKernel)(const SelArgs);
-static inline SelKernel sel_kernel_for(int K, bool listed)
+// (csr: the instantiations whose resolve code looks log A up in CSR rows, for models set by fv_set_model_sparse)
+static inline SelKernel sel_kernel_for(int K, bool listed, bool csr = false)
 {
+    if (csr) {
+        if (K <= 4 * SEL_BLOCK) return listed ? topb_select<4, true, true> : topb_select<4, false, true>;
+        if (K <= 16 * SEL_BLOCK) return listed ? topb_select<16, true, true> : topb_select<16, false, true>;
+        return listed ? topb_select<SEL_MAX_ROUNDS, true, true> : topb_select<SEL_MAX_ROUNDS, false, true>;
+    }
     if (K <= 4 * SEL_BLOCK) return listed ? topb_select<4, true> : topb_select<4, false>;
     if (K <= 16 * SEL_BLOCK) return listed ? topb_select<16, true> : topb_select<16, false>;
     return listed ? topb_select<SEL_MAX_ROUNDS, true> : topb_select<SEL_MAX_ROUNDS, false>;
@@ -1499,9 +1556,13 @@ static inline SelKernel sel_kernel_for(int K, bool listed)
 
 // lean kernel for steps with a candidate list, where the generic one would be the 64-round instantiation
 // (always: K beyond the register kernels' 64 rounds — every selection of such a model, listed or not, runs here)
-static inline SelKernel sel_cand_kernel_for(int K, int cand_cap, bool listed, bool always = false)
+static inline SelKernel sel_cand_kernel_for(int K, int cand_cap, bool listed, bool always = false, bool csr = false)
 {
     if (!always && (K <= 16 * SEL_BLOCK || cand_cap <= 0)) return nullptr;
+    if (csr) {
+        if (cand_cap <= 8 * SEL_BLOCK) return listed ? topb_select_cand<8, true, true> : topb_select_cand<8, false, true>;
+        return listed ? topb_select_cand<16, true, true> : topb_select_cand<16, false, true>;
+    }
     if (cand_cap <= 8 * SEL_BLOCK) return listed ? topb_select_cand<8, true> : topb_select_cand<8, false>;
     return listed ? topb_select_cand<16, true> : topb_select_cand<16, false>;
 }
@@ -1535,10 +1596,13 @@ struct FixArgs {
     const int *seq_of;         // batch decode: [total T] sequence of every absolute time — gate[seq_of[j]] decides per listed
                                // cell (j, i), and `total` counts the cells re-decided; nullptr: one sequence, one flag
     int K, ld, beam;
+    CsrRows csr;               // tie_fixup<true>: in place of LA64R
 };
 
 // For every listed (j, i): redo the reference's scan over the heap of step j-1 in SLOT order with
 // strict '>' (FLASH_BS:440-446) and store the state of the winning slot.  One wave per cell.
+// CSR: log A[slot's state][i] looked up in that state's row (csr_log) instead of gathered from LA64R.
+template <bool CSR = false>
 __global__ __launch_bounds__(256) void tie_fixup(const FixArgs args)
 {
     const bool per_seq = args.gate && args.seq_of;
@@ -1571,7 +1635,8 @@ __global__ __launch_bounds__(256) void tie_fixup(const FixArgs args)
             for (int u = 0; u < 4; ++u) {
                 const int s = s0 + 64 * u;
                 v[u] = s < B ? sv[s] : 0.0f;
-                L[u] = s < B ? Lt[(size_t)ss[s] * args.ld] : 0.0;
+                if constexpr (CSR) L[u] = s < B ? csr_log(args.csr, ss[s], i) : 0.0;
+                else L[u] = s < B ? Lt[(size_t)ss[s] * args.ld] : 0.0;
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -1697,6 +1762,88 @@ __global__ __launch_bounds__(64) void beam_end_backtrack(const BeamEndArgs args,
     if (met_tag && args.lazy && lane == 0) atomicExch(flag, 1);
 }
 
+// ---------------------------------------------------------------- beam step over CSR rows (FV_OPT_SPARSE_BEAM)
+
+// The step of a model set by fv_set_model_sparse: there is no row of K cells to gather, so the sweep is turned round.
+// Every entry s of the previous step's list scatters its row's stored transitions into a per-column accumulator, and a
+// K-wide finish turns the accumulators into what beam_step leaves (DESIGN.md 5.4c).  The cell is the reference
+// expression on the stored float64 log, so there is no condition on the values.
+//   acc[j][col]     max over the entries of (ordered(y) << 32) | (0xFFFFFFFF - s); 0: no entry reaches the column.  The
+//                   maximum does not depend on the order of the atomics, and among equal y the lowest s wins the low
+//                   word — beam_step's provisional arg.
+//   tieval[j][col]  max of ordered(y) over the entries that found their own y already in acc's high word.  Of two
+//                   entries that attain the column's maximum the later one finds it there, and an equal pair below the
+//                   maximum leaves a smaller value: the column is tied at its maximum iff tieval == high word of acc.
+// y is canonicalised (y + 0.0f) first: beam_step compares with ==, for which -0.0 equals +0.0, bit keys would not.
+struct BeamCsrArgs {
+    BeamStepArgs a;                // LA64R / LAQ16R / qpar unused
+    CsrRows m;
+    unsigned long long *acc;       // [T][K], all zero between launches (beam_finish_csr clears what it read)
+    unsigned int *tieval;          // [T][K]
+};
+constexpr int CSR_SCATTER_WAVES = 4;       // list entries per workgroup: one wave each
+constexpr int CSR_FINISH_BLOCK = 256;      // columns per workgroup of the finish
+
+// entries of the previous step's list the step sweeps: args.beam, or up to BEAM_EXTRA more while it is speculative (beam_step)
+__device__ __forceinline__ int step_list_len(const BeamStepArgs &args, const BeamSlot &ps)
+{
+    return max(args.beam, min((int)ps.cut[CUT_N], beam_pitch(args.beam)));
+}
+
+// grid = (entry groups, passes); a wave takes one list entry and walks its row with its lanes
+__global__ __launch_bounds__(CSR_SCATTER_WAVES * 64) void beam_scatter_csr(const BeamCsrArgs ca)
+{
+    const BeamStepArgs &args = ca.a;
+    const BeamSlot &ps = args.p[blockIdx.y];
+    const int lane = threadIdx.x & 63;
+    const int s = blockIdx.x * CSR_SCATTER_WAVES + (int)(threadIdx.x >> 6);      // wave-uniform
+    if (s >= step_list_len(args, ps)) return;
+    const int k = ps.sstate[s];
+    if (k < 0 || k >= args.K) return;                  // (a list holds states; never follow anything else into the row table)
+    const float v = ps.sval[s];
+    const long long e1 = ca.m.ptr[k + 1];
+    unsigned long long *acc = ca.acc + (size_t)ps.j * args.K;
+    unsigned int *tieval = ca.tieval + (size_t)ps.j * args.K;
+    for (long long e = ca.m.ptr[k] + lane; e < e1; e += 64) {
+        const double L = ca.m.log[e];
+        const int col = ca.m.col[e];
+        if (!(L > -__builtin_huge_val()) || col < 0 || col >= args.K) continue;      // a stored 0 never wins (FLASH:171)
+        const float y = fvk::exact_cell(ps.tmp_row[col], v, L) + 0.0f;
+        if (y > -FLT_MAX) {
+            const unsigned int hi = f2key(y);
+            const unsigned long long old = atomicMax(acc + col, ((unsigned long long)hi << 32) | (0xFFFFFFFFu - (unsigned int)s));
+            if ((unsigned int)(old >> 32) == hi) atomicMax(tieval + col, hi);
+        }
+    }
+}
+
+// grid = (K / CSR_FINISH_BLOCK, passes); lane = column
+__global__ __launch_bounds__(CSR_FINISH_BLOCK) void beam_finish_csr(const BeamCsrArgs ca)
+{
+    const BeamStepArgs &args = ca.a;
+    const BeamSlot &ps = args.p[blockIdx.y];
+    const int col = blockIdx.x * CSR_FINISH_BLOCK + threadIdx.x;
+    const float cut_state = ps.cut[CUT_STATE], cut_theta = ps.cut[CUT_THETA];
+    bool cnd = false;
+    float r = FV_NEG_INF;
+    if (col < args.K) {
+        const size_t at = (size_t)ps.j * args.K + col;
+        const unsigned long long key = ca.acc[at];
+        const unsigned int tv = ca.tieval[at];
+        int a = INT_MAX, t = 0;
+        if (key) {
+            const unsigned int hi = (unsigned int)(key >> 32);
+            r = key2f(hi);
+            a = (int)(0xFFFFFFFFu - (unsigned int)key);
+            t = tv == hi ? 1 : 0;
+            ca.acc[at] = 0ull;                         // one memset per decode, not per step
+            if (tv) ca.tieval[at] = 0u;
+        }
+        cnd = finish_column(args, ps, col, r, a, t, ps.sval, ps.sstate, cut_state == 1.0f, cut_theta);
+    }
+    if (args.cand_cap) append_candidates(args, ps.j, cnd, r, col);
+}
+
 static inline int allow_big_lds(std::string &detail)
 {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_step<16>),
@@ -1716,9 +1863,16 @@ static inline int allow_big_lds(std::string &detail)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(&heap_build_all),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_resolve),
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_resolve<false>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    const void *sel[] = { reinterpret_cast<const void *>(&topb_select<4, true>), reinterpret_cast<const void *>(&topb_select<4, false>),
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_resolve<true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    const void *sel[] = { reinterpret_cast<const void *>(&topb_select<4, true, true>), reinterpret_cast<const void *>(&topb_select<4, false, true>),
+                          reinterpret_cast<const void *>(&topb_select<16, true, true>), reinterpret_cast<const void *>(&topb_select<16, false, true>),
+                          reinterpret_cast<const void *>(&topb_select<SEL_MAX_ROUNDS, true, true>), reinterpret_cast<const void *>(&topb_select<SEL_MAX_ROUNDS, false, true>),
+                          reinterpret_cast<const void *>(&topb_select_cand<8, true, true>), reinterpret_cast<const void *>(&topb_select_cand<8, false, true>),
+                          reinterpret_cast<const void *>(&topb_select_cand<16, true, true>), reinterpret_cast<const void *>(&topb_select_cand<16, false, true>), reinterpret_cast<const void *>(&topb_select<4, true>), reinterpret_cast<const void *>(&topb_select<4, false>),
                           reinterpret_cast<const void *>(&topb_select<16, true>), reinterpret_cast<const void *>(&topb_select<16, false>),
                           reinterpret_cast<const void *>(&topb_select<SEL_MAX_ROUNDS, true>), reinterpret_cast<const void *>(&topb_select<SEL_MAX_ROUNDS, false>),
                           reinterpret_cast<const void *>(&topb_select_cand<8, true>), reinterpret_cast<const void *>(&topb_select_cand<8, false>),

@@ -535,7 +535,8 @@ static void drop_model(fv_ctx *ctx, bool keep_dense)
     ctx->LA64R.release(); ctx->LAQ16R.release();
     ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release();
     ctx->CSk.release(); ctx->CSq.release(); ctx->CS64.release(); ctx->CSoff.release(); ctx->CSnwb.release();
-    ctx->CRptr.release(); ctx->CRcol.release(); ctx->CRlog.release();
+    ctx->CRptr.release(); ctx->CRcol.release(); ctx->CRlog.release(); ctx->csr_nnz = 0;
+    ctx->d_csr_acc.release(); ctx->d_csr_tie.release();      // (sized by K; a dense-set model never reads them)
     ctx->EMap.release();
     if (!keep_dense) { ctx->LA32.release(); ctx->LA16.release(); ctx->LAQ16.release(); ctx->LA64.release(); }
 }
@@ -738,7 +739,7 @@ int upload_csr(fv_ctx *ctx, const HostCsr &h, const long long *row_ptr, const in
         FV_HIP(hipMemcpy(ctx->CRlog.p, h.rlog.data(), nnz * sizeof(double), hipMemcpyHostToDevice));
     }
     if (int rc = finish_upload(ctx, e)) return rc;
-    ctx->csr = true;
+    ctx->csr = true; ctx->csr_nnz = (long long)nnz;
     ctx->stats.density = ctx->density;
     return FV_OK;
 }
@@ -1039,6 +1040,9 @@ extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
     case FV_OPT_SEL_MARGIN:
         if (value < 0 || value > 100000) return FV_ERR_ARG;
         ctx->opt_sel_margin = (float)value * 1e-3f; return FV_OK;
+    case FV_OPT_SPARSE_BEAM:
+        if (value != 0 && value != 1) return FV_ERR_ARG;
+        ctx->opt_sparse_beam = (int)value; return FV_OK;
     case FV_OPT_DEBUG:
 #ifndef FV_TIMING_BUILD
         // bits 0, 4, 5, 11, 12 leave a part of a kernel out (to time the rest) and so change results: they exist in

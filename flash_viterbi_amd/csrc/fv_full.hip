@@ -889,6 +889,10 @@ int full_setup(fv_ctx *ctx)
 
 int launch_init_rows(fv_ctx *ctx, const fvk::PassChunk &ch, float *rows)
 {
+    if (ctx->csr)        // (a beam decode of a sparse-set model, FV_OPT_SPARSE_BEAM)
+        hipLaunchKernelGGL(fvk::init_rows_csr, dim3((ctx->K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->CRptr.p,
+                           ctx->CRcol.p, ctx->CRlog.p, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, rows, ctx->K);
+    else
     hipLaunchKernelGGL(fvk::init_rows, dim3((ctx->K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch,
                        ctx->LA64.p, ctx->nrows, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, rows, ctx->K,
                        static_cast<unsigned short *>(nullptr), static_cast<float *>(nullptr), 0.0f);

@@ -161,8 +161,14 @@ struct fv_ctx {
     DevBuf<int> d_passL;         // first position of every pass of the generation in flight (beam decodes)
     std::vector<int> h_passL;
     DevBuf<unsigned int> d_tie_count;
+    // FV_OPT_SPARSE_BEAM (beam_scatter_csr / beam_finish_csr): per (observation, state) the packed column maximum and the tie
+    // word, all zero outside a step launch; allocated only by beam decodes of a sparse-set model
+    DevBuf<unsigned long long> d_csr_acc;
+    DevBuf<unsigned int> d_csr_tie;
+    long long csr_nnz = 0;       // stored entries of the model set by fv_set_model_sparse
 
     // options
+    int opt_sparse_beam = 0; // FV_OPT_SPARSE_BEAM: the beam calls run on a model set by fv_set_model_sparse
     int opt_kernel = FV_KERNEL_AUTO;
     int opt_max_batch = fvk::MAX_BATCH;
     int opt_profile = 0;
@@ -219,7 +225,7 @@ struct fv_ctx {
         f(d_snap); f(d_flat_bp); f(d_chain); f(d_flat);
         f(d_hval); f(d_scores); f(d_slot_val); f(d_hstate); f(d_slot_state); f(d_flags); f(LA64R); f(LAQ16R); f(d_qaux);
         f(d_tie_list); f(d_cut); f(d_cand); f(d_cand_count); f(d_dupwin); f(d_doubt); f(d_doubt_count); f(d_needfull);
-        f(d_seqof); f(d_passL); f(d_tie_count);
+        f(d_seqof); f(d_passL); f(d_tie_count); f(d_csr_acc); f(d_csr_tie);
     }
 };
 

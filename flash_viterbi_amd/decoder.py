@@ -20,6 +20,7 @@ KERNEL_CSR_F64 = 8                     # models set by set_model_sparse: the flo
 OPT_KERNEL, OPT_MAX_BATCH, OPT_PROFILE, OPT_SEL_MARGIN, OPT_DEBUG = 1, 2, 3, 4, 100
 OPT_FLAT_GENERATIONS = 5               # 0 off, 1 auto (default), 2 on: all right-hand generations at once from the whole-sequence chain
 OPT_ROW_CODES = 6                      # 0 off, 1 auto (default), 2 on: the packed kernel's score codes come from the row's producer
+OPT_SPARSE_BEAM = 7                    # 0 (default) / 1: the beam calls run on a model set by set_model_sparse (refused under 0)
 FLAT_OFF, FLAT_AUTO, FLAT_ON = 0, 1, 2
 DEBUG_TIMING_ONLY = (1 << 0) | (1 << 4) | (1 << 5) | (1 << 11) | (1 << 12)      # refused by the shipped library
 DEBUG_BATCH_GEN0_SERIAL = 1 << 28      # decode_full_batch: the whole-sequence passes on one stream (speed only)
@@ -29,6 +30,7 @@ DEBUG_CSR_ROWS_IN_MEMORY = 1 << 31     # sparse-set models: the step kernel read
 # bit every launch that read its score rows from memory sets in addition
 TV_CSR64_NB = (1 << 58, 1 << 59, 1 << 60, 1 << 61)
 TV_CSR64_MEM = 1 << 62
+TV_BEAM_CSR = (1 << 46) | (1 << 47)    # FV_TV_BEAM_CSR: test_beam_step ran the CSR scatter + finish (OPT_SPARSE_BEAM); the pair of the W4 / W16 bits
 TV_ROW_CODES = 1 << 63                 # a packed-kernel launch copied its score codes from the producers (OPT_ROW_CODES)
 WARN_BEAM_MISS = 1
 ERR_ARG, ERR_NOMEM, ERR_NO_PRED, ERR_DEVICE, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6

@@ -83,6 +83,19 @@ enum {
                                win; the single-task launches of the whole-sequence pass lose on it and keep their prologue.  Smaller
                                models, fv_decode_full_batch and the test hooks take the route under 2 only.  3 / 4 (measurements):
                                only single-task / only batched launches take it.  Costs 2.25 bytes per score-row entry of device memory where taken */
+    FV_OPT_SPARSE_BEAM = 7, /* models set by fv_set_model_sparse: 0 (default) fv_decode_beam, fv_decode_beam_batch and fv_test_beam_step
+                               answer FV_ERR_UNSUPPORTED; 1 they run, on the stored transitions: every entry of a
+                               step's beam scatters its CSR row into per-column accumulators with vector atomics and a K-wide finish
+                               turns them into the step's scores, back-pointers and lists; the cells the resolve code and the tie
+                               fix-up re-evaluate are looked up in the rows.  Per sequence the path (with its -1 entries), the score
+                               and the return / status code are bit for bit those of the same model set by fv_set_model, in both
+                               modes, for every n_split and admitted beam width, ob != NULL and ob == NULL, any model values and
+                               staged scores (the cell is the float64 reference expression: no filter, no condition); admission
+                               is the dense-set model's.  fv_stats.kernel reports FV_KERNEL_CSR_F64, table_bytes_per_step the
+                               ESTIMATE 12 * beam * nnz / K (12 bytes per stored entry of an average row; the rows actually walked
+                               are the beam's).  Costs 12 bytes of device memory per (observation, state).  Any other value:
+                               FV_ERR_ARG.  On a model set by fv_set_model the option changes nothing.  The default is 0 because the
+                               refusals and their texts are pinned by the suite of the sparse-set model; a later change may flip it */
     FV_OPT_DEBUG = 100,     /* UNSTABLE: kernel-tuning switches (a bit mask) that select alternative forms of a kernel or of the
                                launch schedule.  Every bit the library accepts is speed-only — the parity tests run each
                                alternative against the same goldens (tests/test_boundary.py checks that no accepted value
@@ -237,7 +250,9 @@ int fv_set_model(fv_ctx *ctx, const float *A, const float *B, const float *Pi, i
  *     baseline's rounding order and delivers what fv_decode_vanilla delivers on the dense-set model.
  *   - fv_decode_beam, fv_decode_beam_batch, fv_test_beam_step and fv_decode_checkpoint answer FV_ERR_UNSUPPORTED before
  *     any device work under every FV_OPT_KERNEL value, FV_KERNEL_CSR_F64 included: their kernels gather rows of the
- *     dense table. */
+ *     dense table.
+ *   - FV_OPT_SPARSE_BEAM = 1 lifts that for the three beam calls (not for fv_decode_checkpoint): they then run on the
+ *     stored rows and deliver what the dense-set model delivers, whatever FV_OPT_KERNEL says; see the option. */
 int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const int *col, const float *val,
                         const float *B, const float *Pi, int K, int M);
 

@@ -194,6 +194,11 @@ int fv_test_beam_select(fv_ctx *ctx, int K, int beam, int s, const fv_test_selec
 #define FV_TV_BEAM_W16       (1ull << 47)   /* beam_step<16> */
 #define FV_TV_BEAM_Q16_W8    (1ull << 48)   /* beam_step_q16<8> */
 #define FV_TV_BEAM_Q16_W16   (1ull << 49)   /* beam_step_q16<16> */
+/* A model set by fv_set_model_sparse under FV_OPT_SPARSE_BEAM: beam_scatter_csr + beam_finish_csr, whatever the launch size
+ * (same outputs as documented for fv_test_beam_step).  Every position of the 64-bit mask is assigned, so the route is
+ * reported as the PAIR of the two float64 beam-step bits, which no launch of the dense kernels sets together (a launch
+ * runs one instantiation). */
+#define FV_TV_BEAM_CSR       (FV_TV_BEAM_W4 | FV_TV_BEAM_W16)
 /* Models set by fv_set_model_sparse: trellis_step_csr<NB, MEM> (MEM: score rows read from memory instead of LDS — K beyond
  * one LDS row, a batch whose NB rows do not fit, or FV_OPT_DEBUG bit 31).  No dense-set model launches them. */
 #define FV_TV_CSR_SHIFT      50
