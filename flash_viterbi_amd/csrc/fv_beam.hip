@@ -773,6 +773,108 @@ extern "C" int fv_test_beam_select(fv_ctx *ctx, int K, int beam, int s, const fv
                                                    slot_state_out, selects_out));
 }
 
+namespace {
+// fv_test_beam_forward (include/flashvit_testing.h): the caller's passes as one generation of run_beam_generations — the
+// decode's own prologue, driver and epilogue — then the per-step buffers of the passes' ranges copied out.
+int test_beam_forward_impl(fv_ctx *ctx, const int *ob, int T, int beam, const fv_test_beam_pass *tp, int np,
+                           const fv_test_beam_tables *out)
+{
+    static_assert(FV_TEST_TIE_TAG == fvb::TIE_TAG, "bp is copied out raw");
+    constexpr int MAX_PASSES = 64;
+    if (!tp || !out || T < 2 || np < 1 || np > MAX_PASSES) return FV_ERR_ARG;
+    int rc = fvi::emission_view(ctx, ob, T);
+    if (rc) return rc;
+    if (ctx->K == 0) return FV_ERR_STATE;
+    if ((rc = beam_admit(ctx, beam))) return rc;
+    for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
+    const int K = ctx->K;
+    const bool whole = np == 1 && tp[0].L == 0 && tp[0].R == T - 1 && tp[0].init_state < 0 && tp[0].end_state < 0;
+    std::vector<std::vector<fv::Pass>> gens(1);
+    std::vector<int> byL((size_t)np), ans((size_t)T, 0);
+    for (int q = 0; q < np; ++q) {
+        const fv_test_beam_pass &p = tp[q];
+        if (p.L < 0 || p.R <= p.L || p.R >= T) { ctx->detail = "fv_test_beam_forward: a pass needs 0 <= L < R < T"; return FV_ERR_ARG; }
+        if (p.init_state < -1 || p.init_state >= K || p.end_state < -1 || p.end_state >= K || (p.L == 0 && p.init_state >= 0)) {
+            ctx->detail = "fv_test_beam_forward: states in [-1, K), init_state < 0 at L = 0";
+            return FV_ERR_ARG;
+        }
+        gens[0].push_back(fv::Pass{ p.L, p.R, p.L == 0, whole, 0, -1, 0 });
+        byL[(size_t)q] = q;
+    }
+    std::sort(byL.begin(), byL.end(), [&](int a, int b) { return tp[a].L < tp[b].L; });
+    for (int q = 1; q < np; ++q) {
+        const fv_test_beam_pass &l = tp[byL[(size_t)q - 1]], &r = tp[byL[(size_t)q]];
+        if (r.L <= l.R) { ctx->detail = "fv_test_beam_forward: passes overlap"; return FV_ERR_ARG; }
+        if (r.L == l.R + 1 && r.init_state != l.end_state) {
+            ctx->detail = "fv_test_beam_forward: touching passes disagree on the answer entry they share";
+            return FV_ERR_ARG;
+        }
+    }
+    auto t0 = clk::now();
+    FV_HIP(hipSetDevice(ctx->device));
+    fv::Plan plan;                   // one generation; no segments: the epilogue gathers nothing
+    plan.gen_begin = { 0, np };
+    if ((rc = beam_workspace(ctx, T, beam, 0))) return rc;
+    if ((rc = beam_tables(ctx))) return rc;
+    start_beam_stats(ctx, plan, beam);
+    if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
+    if (!whole) {
+        // what the init rows (ans[L-1]) and the pass ends (ans[R]) read; `ans` lives until the epilogue has synchronised
+        for (int q = 0; q < np; ++q) {
+            ans[(size_t)tp[q].R] = tp[q].end_state;
+            if (tp[q].L > 0) ans[(size_t)tp[q].L - 1] = tp[q].init_state;
+        }
+        FV_HIP(hipMemcpyAsync(ctx->d_ans.p, ans.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    }
+    struct Restore { fv_ctx *c; ~Restore() { c->test_record = false; } } restore{ ctx };
+    ctx->test_record = true;
+    ctx->test_variants = 0;
+    ctx->test_selects = 0;
+    if ((rc = run_beam_generations(ctx, gens, beam, T, 1, nullptr))) return rc;
+    ctx->close_stats((long long)K * beam, 0);
+    std::vector<int> path((size_t)T);
+    float score = 0.0f;
+    const long long seq[2] = { 0, T };
+    if ((rc = fvi::finish_decode(ctx, plan, seq, 1, path.data(), &score, nullptr, t0, 0, true)) < 0) return rc;
+    // the generation has finished (finish_decode synchronised): plain copies of the passes' rows
+    const size_t BP = (size_t)fvb::beam_pitch(beam), B = (size_t)beam, Ks = (size_t)K;
+    auto rows = [&](auto *dst, const auto *src, size_t first, size_t n, size_t width) -> hipError_t {
+        if (!dst || n == 0) return hipSuccess;
+        return hipMemcpy(dst + first * width, src + first * width, n * width * sizeof(*dst), hipMemcpyDeviceToHost);
+    };
+    for (int q = 0; q < np; ++q) {
+        const size_t L = (size_t)tp[q].L, n = (size_t)(tp[q].R - tp[q].L + 1);
+        FV_HIP(rows(out->scores, ctx->d_scores.p, L, n, Ks));
+        FV_HIP(rows(out->bp, ctx->d_bp.p, L + 1, n - 1, Ks));
+        FV_HIP(rows(out->cut, ctx->d_cut.p, L, n, (size_t)fvb::CUT_W));
+        FV_HIP(rows(out->member_val, ctx->d_hval.p, L, n, BP));
+        FV_HIP(rows(out->member_state, ctx->d_hstate.p, L, n, BP));
+        FV_HIP(rows(out->doubt, ctx->d_doubt.p, L, n, (size_t)fvb::DOUBT_CAP));
+        FV_HIP(rows(out->doubt_count, ctx->d_doubt_count.p, L, n, (size_t)1));
+        FV_HIP(rows(out->slot_val, ctx->d_slot_val.p, L, n, B));
+        FV_HIP(rows(out->slot_state, ctx->d_slot_state.p, L, n, B));
+        if (out->path) std::copy(path.begin() + tp[q].L, path.begin() + tp[q].R + 1, out->path + tp[q].L);
+    }
+    if (out->gate) FV_HIP(hipMemcpy(out->gate, ctx->d_needfull.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (out->score && whole) *out->score = score;
+    if (out->variants) *out->variants = ctx->test_variants;
+    if (out->selects) *out->selects = ctx->test_selects;
+    return rc;
+}
+}  // namespace
+
+extern "C" int fv_test_beam_forward(fv_ctx *ctx, const int *ob, int T, int beam, const fv_test_beam_pass *passes, int npasses,
+                                    const fv_test_beam_tables *out)
+{
+    if (!ctx) return FV_ERR_ARG;
+    if (fvi::group_size(ctx) > 1 || ctx->comm || ctx->nranks > 1) {
+        ctx->detail = "fv_test_beam_forward: one device, no communicator and no partition";
+        return FV_ERR_ARG;
+    }
+    if (ctx->csr && !ctx->opt_sparse_beam) { ctx->detail = "fv_test_beam_forward: not available on a model set by fv_set_model_sparse"; return FV_ERR_UNSUPPORTED; }
+    return fvi::drained(ctx, test_beam_forward_impl(ctx, ob, T, beam, passes, npasses, out));
+}
+
 #ifdef FV_REPLAY_PROF
 // Experiment builds only: read and reset the replay profile (fv_beam_kernels.hip.inc, replay_prof).
 extern "C" int fv_debug_replay_prof(unsigned long long *out8)

@@ -82,7 +82,7 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_set_model_sparse", "fv_set_emissions", "fv_clear_emissions", "fv_plan_flat", "fv_set_emission_map"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select", "fv_test_device_alloc", "fv_test_device_free",
-                "fv_test_stage_emissions_ms", "fv_test_flat_poison"]
+                "fv_test_stage_emissions_ms", "fv_test_flat_poison", "fv_test_beam_forward"]
 TIE_TAG = 1 << 30
 # FV_TS_*: select-kernel instantiations reported by test_beam_select
 TS_BITS = {"topb_select<4,listed>": 1 << 0, "topb_select<4,derived>": 1 << 1, "topb_select<16,listed>": 1 << 2,
@@ -98,6 +98,20 @@ SELECT_COUNTERS = (2, 5, 7, 9, 10, 11, 12, 13)
 class ForwardPass(ctypes.Structure):
     """fv_test_pass: steps L+1 .. R from Pi (init_state < 0, L = 0) or from state init_state at time L - 1."""
     _fields_ = [("L", ctypes.c_int), ("R", ctypes.c_int), ("init_state", ctypes.c_int)]
+
+
+class BeamPass(ctypes.Structure):
+    """fv_test_beam_pass: one FLASH-BS pass [L, R] from init_state (< 0: Pi) to the fixed end state end_state."""
+    _fields_ = [("L", ctypes.c_int), ("R", ctypes.c_int), ("init_state", ctypes.c_int), ("end_state", ctypes.c_int)]
+
+
+class BeamTables(ctypes.Structure):
+    """fv_test_beam_tables: where fv_test_beam_forward copies the per-step buffers (NULL: not wanted)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("scores", "bp", "cut", "member_val", "member_state", "doubt", "doubt_count",
+                                               "slot_val", "slot_state", "path", "score", "gate", "variants", "selects")]
+
+
+DOUBT_CAP = 1024                       # doubtful columns a step lists
 
 
 class SelectSet(ctypes.Structure):
@@ -167,6 +181,7 @@ def load_library():
                                     vp, vp, vp, vp, ctypes.POINTER(ctypes.c_ulonglong)]
     L.fv_test_beam_select.argtypes = [vp, ci, ci, ci, ctypes.POINTER(SelectSet), ci, cf, cf, vp, ci, ctypes.POINTER(ci), vp,
                                       vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_ulonglong)]
+    L.fv_test_beam_forward.argtypes = [vp, vp, ci, ci, ctypes.POINTER(BeamPass), ci, ctypes.POINTER(BeamTables)]
     _lib = L
     return L
 
@@ -497,6 +512,31 @@ class FlashViterbi:
         variants = ctypes.c_ulonglong(0)
         self._check(self._L.fv_test_forward(self._h, ptr, T, pa, len(passes), _p(rows), _p(bp), ctypes.byref(variants)))
         return rows, bp, int(variants.value)
+
+    def test_beam_forward(self, ob, beam, passes, T=None):
+        """fv_test_beam_forward: passes = [(L, R, init_state, end_state)] run as one generation of FLASH-BS passes — the single
+        whole-sequence pass (0, T-1, -1, -1) as generation 0 runs, anything else as a right-hand generation.  Returns a dict
+        of the per-step buffers by absolute time, written in the passes' ranges only: scores[T, K] (rows outside: NaN),
+        bp[T, K] (raw, TIE_TAG where a cell is still tagged; outside: -2), cut[T, 8], member_val / member_state[T, beam + 32],
+        doubt[T, 1024], doubt_count[T], slot_val / slot_state[T, beam], path[T] (outside: -2), score, gate, variants, selects
+        and rc (0, or WARN_BEAM_MISS).  ob=None with T=...: on the rows staged by set_emissions."""
+        ob, ptr, T = _ob_arg(ob, T)
+        K, BP = self.K, int(beam) + BEAM_EXTRA
+        pa = (BeamPass * len(passes))(*[BeamPass(int(L), int(R), int(a), int(b)) for L, R, a, b in passes])
+        o = dict(scores=np.full((T, K), np.nan, np.float32), bp=np.full((T, K), -2, np.int32),
+                 cut=np.full((T, CUT_W), np.nan, np.float32), member_val=np.full((T, BP), np.nan, np.float32),
+                 member_state=np.full((T, BP), -2, np.int32), doubt=np.full((T, DOUBT_CAP), -2, np.int32),
+                 doubt_count=np.zeros(T, np.int32), slot_val=np.full((T, int(beam)), np.nan, np.float32),
+                 slot_state=np.full((T, int(beam)), -2, np.int32), path=np.full(T, -2, np.int32),
+                 score=np.full(1, np.nan, np.float32), gate=np.zeros(1, np.int32), variants=np.zeros(1, np.uint64),
+                 selects=np.zeros(1, np.uint64))
+        tab = BeamTables(**{k: _p(v).value for k, v in o.items()})
+        rc = self._check(self._L.fv_test_beam_forward(self._h, ptr, T, int(beam), pa, len(passes), ctypes.byref(tab)))
+        for k in ("gate", "variants", "selects"):
+            o[k] = int(o[k][0])
+        o["score"] = o["score"][0]
+        o["rc"] = rc
+        return o
 
     def test_beam_step(self, beam, sets, syms, speculative=False, theta=0.0, next_bound=float("inf"), cand_cap=0):
         """fv_test_beam_step: one launch of the beam step kernel over sets = [(values, states)] (beam <= n <= beam + 32),

@@ -115,13 +115,57 @@ typedef struct { const float *scores; const fv_test_cand *cand; int cand_count; 
  * FV_ERR_ARG / FV_ERR_UNSUPPORTED before any device work: beam < 2, beam > K, a beam the beam path does not admit, s
  * outside 0 .. 2, nsets outside 0 .. 64, a list where a decode has none, a negative count, a list state outside [0, K), a
  * multi-device context.
- * Out of scope (they need real consecutive steps of a model and stay covered by the decode-level suites): dirty steps,
- * doubtful_reach, resolve_upto, patch_doubtful, beam_resolve, tie_fixup, beam_end_backtrack.
+ * What needs real consecutive steps of a model — dirty steps, doubtful_reach, resolve_upto, patch_doubtful, beam_resolve,
+ * tie_fixup, beam_end_backtrack — is exposed by fv_test_beam_forward below.
  * Overwrites the decode's per-step beam buffers and statistics counters. */
 int fv_test_beam_select(fv_ctx *ctx, int K, int beam, int s, const fv_test_select_set *sets, int nsets, float prev_theta,
                         float prev_margin, const float *seed, int want_layout, int *cand_cap_out, float *cut_out,
                         float *member_val_out, int *member_state_out, unsigned long long *counters_out, float *slot_val_out,
                         int *slot_state_out, unsigned long long *selects_out);
+
+/* One FLASH-BS pass over [L, R].  init_state < 0: the init row starts from Pi (at L > 0 too: what a pass reads after a beam
+ * miss, Ans[L-1] == -1); else from row init_state of log A.  end_state: the fixed end state the pass back-tracks from
+ * (-1: none is a member, the pass misses); ignored by the whole-sequence form. */
+typedef struct { int L, R, init_state, end_state; } fv_test_beam_pass;
+
+/* What fv_test_beam_forward copies out.  Every pointer may be NULL; every array is indexed by absolute time t and is written
+ * in the passes' ranges only (P = beam + 32, the pitch of a member list):
+ *   scores[T*K]          rows L .. R: the init row, then every step's scores as the device holds them after the generation
+ *                        (upper bounds in the doubtful columns of a step that stayed dirty);
+ *   bp[T*K]              rows L+1 .. R, raw: | FV_TEST_TIE_TAG where the device still holds a tagged cell, -1 no predecessor;
+ *   cut[T*8]             rows L .. R, the cut records (layout as for fv_test_beam_select);
+ *   member_val[T*P], member_state[T*P]   rows L .. R, the member lists; cut[t][4] entries of row t are meaningful;
+ *   doubt[T*1024], doubt_count[T]        rows L .. R: the doubtful columns each step listed (the count may exceed 1024);
+ *   slot_val[T*beam], slot_state[T*beam] rows L .. R of the layout buffers: what heap_build_all left there — every row once
+ *                        the layouts ran (*gate != 0 or FV_OPT_DEBUG bit 19), the last row of a whole-sequence pass always,
+ *                        otherwise whatever an earlier call left;
+ *   path[T]              entries L .. R of the answer array (R: the end state, picked or given);
+ *   score                the whole-sequence pass's score (otherwise not written);
+ *   gate                 the tie gate after the generation: != 0 if a pass's walk met a tagged cell (or under bit 19);
+ *   variants, selects    the FV_TV_BEAM_* / FV_TS_* bits of the step and select kernels that launched. */
+typedef struct {
+    float *scores; int *bp; float *cut; float *member_val; int *member_state; int *doubt; int *doubt_count;
+    float *slot_val; int *slot_state; int *path; float *score; int *gate;
+    unsigned long long *variants, *selects;
+} fv_test_beam_tables;
+
+/* The caller's passes as ONE generation of the FLASH-BS driver (run_generation_beam, through the sorting, the dealing to
+ * stream groups and the pass-list upload a decode's generations get), then the per-step buffers copied out.  No kernel is
+ * launched that a decode would not launch; the copies are made after the generation has finished.  Admission, tables and
+ * workspace are fv_decode_beam's (same refusals, same symbol check; ob == NULL reads the rows staged by fv_set_emissions);
+ * FV_OPT_DEBUG, FV_OPT_SEL_MARGIN and FV_OPT_SPARSE_BEAM apply as they do to a decode.  Two forms:
+ *   whole        npasses == 1, L = 0, R = T - 1, init_state < 0, end_state < 0: run as generation 0 runs (end pick from the
+ *                last heap's layout, score written);
+ *   right-hand   1 .. 64 passes, 0 <= L < R < T, non-overlapping: run as a right-hand generation (sorted longest first,
+ *                dealt to the stream groups FV_OPT_DEBUG bits 16 / 17 choose; more than 24 passes split the step launches
+ *                and take the select's derived-job form).  Before the generation starts end_state is written to ans[R] and
+ *                init_state to ans[L-1] (L > 0), where the init rows and the pass ends read them; two passes whose ranges
+ *                touch must agree on the entry they share (the left one's end_state is the right one's init_state).
+ * Returns FV_OK, or FV_WARN_BEAM_MISS if a pass's answer entries hold -1.  FV_ERR_ARG: a bad range or overlap, a state outside
+ * [-1, K), init_state >= 0 at L = 0, touching passes that disagree, a symbol outside [0, M), or a multi-device, partitioned
+ * or communicator context.  fv_last_stats afterwards describes this call (the beam counters included). */
+int fv_test_beam_forward(fv_ctx *ctx, const int *ob, int T, int beam, const fv_test_beam_pass *passes, int npasses,
+                         const fv_test_beam_tables *out);
 
 /* Select-kernel instantiations (selects_out): recorded on the host, only during a hook call.  R = rounds of 1024 keys held in
  * registers; LISTED: job descriptors in the kernel arguments (<= 24 rows), DERIVED: from the pass list on the device. */

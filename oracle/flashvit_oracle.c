@@ -635,23 +635,28 @@ static int beam_final_slot(const hnode *h, int beam, float *score_out)
     return arg;
 }
 
+/* The init row of a beam pass and its heap, FLASH_BS:407-427: st < 0 starts from Pi, else from row st of
+ * log A; pushed in state order.  row (may be NULL) receives the K scores. */
+static void beam_init_heap(const fvo_model *m, int o, int st, int beam, hnode *h, float *row)
+{
+    const int K = m->K, M = m->M;
+    heap_reset(h);
+    for (int i = 0; i < K; ++i) {
+        double x = st < 0 ? m->logPi[i] : m->logA[(size_t)st * K + i];
+        float tmp = (float)(x + m->logB[(size_t)i * M + o]);
+        if (row) row[i] = tmp;
+        heap_offer(h, beam, tmp, i, -1);
+    }
+}
+
 /* nvviter (beam), FLASH_BS:401-473. */
 static void beam_bisect(beam_run *r, int L, int R, int mid, hnode *H[2], float *scr, int *argv)
 {
     const fvo_model *m = r->m;
-    const int K = m->K, M = m->M, beam = r->beam;
-    heap_reset(H[0]);
-    {
-        int o = r->ob[L];
-        /* After a beam miss Ans[L-1] is -1 and the reference reads A[-1][i], which in its VIT
-         * struct (FLASH_BS:27-30, Pi directly in front of A) is Pi[i]: same row as L == 0. */
-        int st = L == 0 ? -1 : r->ans[L - 1];
-        for (int i = 0; i < K; ++i) {
-            double x = st < 0 ? m->logPi[i] : m->logA[(size_t)st * K + i];
-            float tmp = (float)(x + m->logB[(size_t)i * M + o]);
-            heap_offer(H[0], beam, tmp, i, -1);
-        }
-    }
+    const int K = m->K, beam = r->beam;
+    /* After a beam miss Ans[L-1] is -1 and the reference reads A[-1][i], which in its VIT
+     * struct (FLASH_BS:27-30, Pi directly in front of A) is Pi[i]: same row as L == 0. */
+    beam_init_heap(m, r->ob[L], L == 0 ? -1 : r->ans[L - 1], beam, H[0], NULL);
     int cur = 0;
     for (int j = L + 1; j <= R; ++j) {
         int o = r->ob[j];
@@ -782,6 +787,48 @@ int fvo_beam_decode(const fvo_model *m, const int *ob, int T, int n_split, int b
 out:
     free(Q); free(midpoint); free(H[0]); free(H[1]); free(scr); free(argv);
     return rc;
+}
+
+/* One plain beam pass [L, R] that keeps its tables: the recurrence of beam_bisect (same init row, same
+ * beam_step_all + heap_offer per step, same end pick) without the t3 bookkeeping. */
+int fvo_beam_forward(const fvo_model *m, const int *ob, int L, int R, int init_state, int beam,
+                     float *scores, int *arg_state, float *hval, int *hstate, int *final_state, float *final_score)
+{
+    if (!m || !ob || L < 0 || R < L || beam < 2 || beam > m->K || init_state >= m->K) return FVO_ERR_ARG;
+    for (int j = L; j <= R; ++j) if (ob[j] < 0 || ob[j] >= m->M) return FVO_ERR_ARG;
+    const int K = m->K;
+    hnode *H[2] = { (hnode *)malloc(sizeof(hnode) * ((size_t)beam + 1)),
+                    (hnode *)malloc(sizeof(hnode) * ((size_t)beam + 1)) };
+    float *scr = (float *)malloc(sizeof(float) * K);
+    int *argv = (int *)malloc(sizeof(int) * K);
+    if (!H[0] || !H[1] || !scr || !argv) { free(H[0]); free(H[1]); free(scr); free(argv); return FVO_ERR_NOMEM; }
+    int cur = 0;
+    beam_init_heap(m, ob[L], init_state, beam, H[0], scr);
+    for (int j = L; j <= R; ++j) {
+        const size_t row = (size_t)(j - L);
+        if (j > L) {
+            const hnode *h = H[cur];
+            hnode *n = H[cur ^ 1];
+            heap_reset(n);
+            beam_step_all(m, h, beam, ob[j], scr, argv);
+            for (int i = 0; i < K; ++i) {
+                heap_offer(n, beam, scr[i], i, -1);
+                if (arg_state) arg_state[(row - 1) * K + i] = argv[i] < 0 ? -1 : h[argv[i] + 1].state;
+            }
+            cur ^= 1;
+        }
+        if (scores) memcpy(scores + row * K, scr, sizeof(float) * (size_t)K);
+        for (int k = 0; k < beam; ++k) {
+            if (hval) hval[row * beam + k] = H[cur][k + 1].value;
+            if (hstate) hstate[row * beam + k] = H[cur][k + 1].state;
+        }
+    }
+    float score;
+    int arg = beam_final_slot(H[cur], beam, &score);
+    if (final_state) *final_state = H[cur][arg + 1].state;
+    if (final_score) *final_score = score;
+    free(H[0]); free(H[1]); free(scr); free(argv);
+    return 0;
 }
 
 /* ---------------------------------------------------------------- memory -- */

@@ -72,6 +72,20 @@ long long fvo_checkpoint_memory_bytes(int K, int T, int step);
 int fvo_full_forward(const fvo_model *m, const int *ob, int L, int R, int init_state,
                      float *score_row, int *argtab);
 
+/* One plain FLASH-BS pass over [L,R] (nvviter's beam recurrence, FLASH_BS:401-455) that keeps its tables, for
+ * n = R - L + 1 rows.  The init row is the one the pass forms: init_state < 0 => from Pi (legal at L > 0 too: the
+ * reference reads Pi after a beam miss, Ans[L-1] == -1), else from row init_state of log A; every row is pushed
+ * through generate_state_heap in state order.  Each output may be NULL:
+ *   scores[n*K]          the init row, then the scores of steps L+1 .. R;
+ *   arg_state[(n-1)*K]   the STATE of the winning slot of every cell (slot order, strict '>'), -1 where no
+ *                        finite predecessor exists;
+ *   hval / hstate[n*beam]  the heap after each row, slots 1..beam in slot order;
+ *   final_state / final_score  the end pick (FLASH_BS:456-461) over the last heap: meaningful for a
+ *                        whole-sequence pass.
+ * No t3 bookkeeping: the caller back-tracks over arg_state. */
+int fvo_beam_forward(const fvo_model *m, const int *ob, int L, int R, int init_state, int beam,
+                     float *scores, int *arg_state, float *hval, int *hstate, int *final_state, float *final_score);
+
 /* The reference's memory_bytes formulas (FLASH:355,364-367 / FLASH_BS:564,573-576),
  * evaluated for the x86-64 glibc struct sizes the reference binary has. */
 long long fvo_full_memory_bytes(int K, int T, int n_split);

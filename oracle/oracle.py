@@ -52,6 +52,7 @@ def lib():
         L.fvo_checkpoint_memory_bytes.restype = ctypes.c_longlong
         L.fvo_beam_step_probe.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
         L.fvo_state_heap_probe.argtypes = [vp, ci, ci, vp, vp]
+        L.fvo_beam_forward.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
         L.fvo_set_threads.argtypes = [ci]
         L.fvo_full_memory_bytes.restype = ctypes.c_longlong
         L.fvo_full_memory_bytes.argtypes = [ci, ci, ci]
@@ -146,6 +147,24 @@ class OracleModel:
         if rc:
             raise OracleError(rc)
         return scr, arg
+
+    def beam_forward(self, ob, L, R, init_state, beam):
+        """One plain beam pass [L, R] with its tables: (scores float32[n, K], arg_state int32[n-1, K], hval
+        float32[n, beam], hstate int32[n, beam], final_state, final_score), n = R - L + 1.  init_state < 0: from Pi."""
+        ob = np.ascontiguousarray(ob, dtype=np.int32)
+        n = R - L + 1
+        scores = np.empty((max(n, 0), self.K), dtype=np.float32)
+        arg = np.empty((max(n - 1, 0), self.K), dtype=np.int32)
+        hval = np.empty((max(n, 0), int(beam)), dtype=np.float32)
+        hstate = np.empty((max(n, 0), int(beam)), dtype=np.int32)
+        fstate = ctypes.c_int(-1)
+        fscore = ctypes.c_float(0)
+        rc = 0 if 0 <= L <= R < ob.size else -1
+        rc = rc or lib().fvo_beam_forward(self._h, _p(ob), L, R, int(init_state), int(beam), _p(scores), _p(arg), _p(hval),
+                                          _p(hstate), ctypes.byref(fstate), ctypes.byref(fscore))
+        if rc:
+            raise OracleError(rc)
+        return scores, arg, hval, hstate, fstate.value, np.float32(fscore.value)
 
     def full_forward(self, ob, L, R, init_state=-1):
         ob = np.ascontiguousarray(ob, dtype=np.int32)
