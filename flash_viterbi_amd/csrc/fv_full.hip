@@ -252,6 +252,9 @@ int launch_csr_f64(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb)
     return launch_csr_f64_nb<8>(ctx, slots, nb);
 }
 
+// which task counts of trellis_step_u16 have a second instantiation without the FV_OPT_ROW_CODES code (CODES = false)
+template <int NB> constexpr bool U16_CODE_FREE = NB == 1;
+
 template <int NB, int U, bool DB, int NWV>
 int launch_u16_variant(fv_ctx *ctx, const fvk::StepArgs<NB> &a)
 {
@@ -259,7 +262,13 @@ int launch_u16_variant(fv_ctx *ctx, const fvk::StepArgs<NB> &a)
     fvk::StepArgs<NB> b = a;
     if (!fvk::u16_takes_codes<NB, DB, NWV>()) b.codes &= ~1;
     if (ctx->test_record) ctx->test_variants |= u16_variant<NB, DB, NWV>() | ((b.codes & 1) ? FV_TV_ROW_CODES : 0ull);
-    hipLaunchKernelGGL((fvk::trellis_step_u16<NB, U, DB, NWV>), dim3(a.tiles_per_xcd * 8), dim3(NWV * 64), lds, ctx->lstream ? ctx->lstream : ctx->stream, b);
+    hipStream_t st = ctx->lstream ? ctx->lstream : ctx->stream;
+    // a single-task launch that neither reads nor writes codes (under auto: every one) runs the form without the route's code;
+    // the batched forms have no such twin (U16_CODE_FREE: there the last argument is `true` again, the same instantiation)
+    if (U16_CODE_FREE<NB> && ctx->launch_codes == 0)
+        hipLaunchKernelGGL((fvk::trellis_step_u16<NB, U, DB, NWV, !U16_CODE_FREE<NB>>), dim3(a.tiles_per_xcd * 8), dim3(NWV * 64), lds, st, b);
+    else
+        hipLaunchKernelGGL((fvk::trellis_step_u16<NB, U, DB, NWV>), dim3(a.tiles_per_xcd * 8), dim3(NWV * 64), lds, st, b);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -883,6 +892,10 @@ int full_setup(fv_ctx *ctx)
         (rc = set_big_lds(ctx, &fvk::trellis_step_u16<2, 16, false, 8>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<2, U_DB16, true, 8>)) ||
         (rc = set_big_lds(ctx, &fvk::trellis_step_u16<4, 16, false, 8>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<4, U_DB16, true, 8>)) ||
         (rc = set_big_lds(ctx, &fvk::trellis_step_u16<8, 16, false, 8>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<8, U_DB16, true, 8>)))
+        return rc;
+    // the single-task forms without the FV_OPT_ROW_CODES code (launch_u16_variant)
+    if ((rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, 8, false, 16, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, U_DB16, true, 16, false>)) ||
+        (rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, 16, false, 8, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, U_DB16, true, 8, false>)))
         return rc;
     return 0;
 }

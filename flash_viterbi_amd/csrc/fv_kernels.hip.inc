@@ -633,6 +633,25 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step(const StepArgs<NB> args
 //     its unclamped sum z* >= 65534 with the table code: if such a cell can attain the exact maximum, Zc + (2.05 + ...) >=
 //     z* >= 65534, and with the two units of slack thr = Zc + W >= 65535 — the guard that walks every row exactly.  The
 //     guard therefore covers every cell whose code saturated, wherever it did.
+//
+// Second smallest.  The refine asks one thing of a lane beyond its smallest z (m1, row block a1, parity half par): does
+// the lane hold a SECOND cell with z <= thr (a tie counted as two cells)?  Then its rows are re-walked (kind 2).  The sweep
+// used to answer with the exact second smallest z per half, three packed instructions per pair of cells.  It now keeps, per
+// half h, the smallest and second smallest BLOCK MINIMUM bm_h(j) = min of the four z of half h in row block j: four adds, a
+// tree of three mins and three instructions of update per block and task.  m1p is what it was (a minimum of minima).  m2p_h
+// = the second smallest of the bm_h(j), a tie between two blocks counted twice = the smallest z of half h outside the
+// block a_h that gave m1p_h (a_h: the first block that reached it; a later block that ties has bm == m1p and sets m2p_h =
+// m1p_h).  A second cell with z <= thr lies, relative to the smallest cell (half par, block a1),
+//   * in the other half: then that half's minimum max(lo, hi) <= thr — the term m2' has always had (lo == hi included: two
+//     cells tie, m2' = m1, the rows are re-walked);
+//   * in the same half, another block: then m2p_par <= thr;
+//   * in the same half of block a1: the only place the sweep no longer sees.  `locate` decodes exactly that block to find
+//     the row, and returns the second smallest of the half's four z, equal sums counted twice, as `second`.
+// With m2' = min(max(lo, hi), m2p_lo, m2p_hi) (m2p of the other half is >= its minimum: never the smaller term) the old
+// m2 is min(m2', second), bit for bit: no pair of cells inside the window escapes, none is invented, and kinds, results and
+// the refine_near / refine_rescan / refine_saturated counts are what they were.  Where the located block is decoded before
+// the kinds are decided (SPEC below) `second` is folded into m2; elsewhere a lane first becomes a candidate from m2' and m1
+// and turns into kind 2 behind `locate` if second <= thr (a candidate has m1 <= thr < 65535, so a1 is a real block).
 typedef unsigned short fv_u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned int pk_adds(unsigned int a, unsigned int b)
 {
@@ -659,7 +678,9 @@ __device__ __forceinline__ unsigned int score_code(float mx, float v, float inv_
 // bit 0 of StepArgs::codes for it) and still writes the codes of its outgoing rows.
 template <int NB, bool DB, int NWV> constexpr bool u16_takes_codes() { return !(NB == 8 && NWV == 16 && !DB); }
 
-template <int NB, int U, bool DB, int NWV>
+// CODES = false: the form for launches that neither read nor write codes (StepArgs::codes == 0: under auto every single-task
+// launch) — the copying prologue and the code-writing tail are not compiled into it, StepArgs::c is never touched.
+template <int NB, int U, bool DB, int NWV, bool CODES = true>
 __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> args)
 {
     constexpr int R = 8, RBR = 32;
@@ -712,7 +733,7 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
     // ch lies in tile ch / 2), the first held in registers as v0 is on the other route, and every wave reads the tile maxima for
     // itself — four per lane cover 256 tiles, an index past the last tile repeats it, which a maximum does not mind.  (The
     // two routes are two whole branches, table request included: registers of the one are not live in the other.)
-    const bool coded = u16_takes_codes<NB, DB, NWV>() && (args.codes & 1) != 0;
+    const bool coded = CODES && u16_takes_codes<NB, DB, NWV>() && (args.codes & 1) != 0;
     const int nch = nrows >> 3;
     if (coded) {
         uint4 cv[NB];
@@ -842,12 +863,11 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
                     const uint4 ct4 = *reinterpret_cast<const uint4 *>(T1c + (size_t)t * npairs + pb);
                     const unsigned int ct[4] = { ct4.x, ct4.y, ct4.z, ct4.w };
                     const unsigned int old = m1p[t];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const unsigned int z = pk_adds(ca[i], ct[i]);
-                        m2p[t] = pk_minu(m2p[t], pk_maxu(z, m1p[t]));
-                        m1p[t] = pk_minu(m1p[t], z);
-                    }
+                    // the block's minimum per half, then (smallest, second smallest) over the block minima
+                    const unsigned int bm = pk_minu(pk_minu(pk_adds(ca[0], ct[0]), pk_adds(ca[1], ct[1])),
+                                                    pk_minu(pk_adds(ca[2], ct[2]), pk_adds(ca[3], ct[3])));
+                    m2p[t] = pk_minu(m2p[t], pk_maxu(bm, m1p[t]));
+                    m1p[t] = pk_minu(m1p[t], bm);
                     const unsigned int x = m1p[t] ^ old;                 // which half found a smaller z in this row block
                     alo[t] = (x & 0xffffu) ? qb : alo[t];
                     ahi[t] = (x >> 16) ? qb : ahi[t];
@@ -860,7 +880,8 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
         }
     }
 
-    // lane summary: smallest z, the half (row parity) and row block it came from, second smallest z
+    // lane summary: smallest z, the half (row parity) and row block it came from, and m2' = the second smallest z with the
+    // rest of block a1's own half left out (locate adds that: see "Second smallest" above pk_adds)
     unsigned int m1[NB], m2[NB];
     int a1[NB], par[NB];
 #pragma unroll
@@ -882,18 +903,24 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
     float tv[NB];
     const double *L64t = args.LA64 + (size_t)tile * nrows * TILE_W + c * 4;     // T4 layout of the f64 table
     const int blk0 = nj > 0 ? block_of(0) : 0;          // a wave without row blocks (tiny K) uses block 0: always inside the tile
-    auto locate = [&](int t, int blk, const uint4 &ce) -> int {    // row of block blk (parity par) whose z equals m1: unique when m2 > m1
+    // row of block blk (parity par) whose z equals m1: unique when m2 > m1.  second: the second smallest of the four z of that
+    // half of the block, a tie counted twice (the pair update the sweep used to make for every cell, here for one block)
+    auto locate = [&](int t, int blk, const uint4 &ce, unsigned int &second) -> int {
         const unsigned int ca[4] = { ce.x, ce.y, ce.z, ce.w };
         const uint4 ct4 = *reinterpret_cast<const uint4 *>(T1c + (size_t)t * npairs + blk * (RBR / 2) + rg * (R / 2));
         const unsigned int ct[4] = { ct4.x, ct4.y, ct4.z, ct4.w };
         const int k0 = blk * RBR + rg * R;
         int found = k0 + par[t];
+        unsigned int b1 = 0xffffffffu, b2 = 0xffffffffu;
 #pragma unroll
         for (int i = 3; i >= 0; --i) {
             const unsigned int z = pk_adds(ca[i], ct[i]);
+            b2 = pk_minu(b2, pk_maxu(z, b1));
+            b1 = pk_minu(b1, z);
             const unsigned int zh = par[t] ? (z >> 16) : (z & 0xffffu);
             found = zh == m1[t] ? k0 + 2 * i + par[t] : found;
         }
+        second = par[t] ? (b2 >> 16) : (b2 & 0xffffu);
         return found;
     };
     if constexpr (SPEC) {
@@ -908,7 +935,9 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
                 const bool hit = u == pos;
                 ce.x = hit ? cur[u].x : ce.x; ce.y = hit ? cur[u].y : ce.y; ce.z = hit ? cur[u].z : ce.z; ce.w = hit ? cur[u].w : ce.w;
             }
-            const int found = locate(t, blk, ce);
+            unsigned int second;
+            const int found = locate(t, blk, ce, second);
+            m2[t] = a1[t] >= 0 ? min(m2[t], second) : m2[t];      // (no block: blk0 need not be this wave's)
             a1[t] = a1[t] >= 0 ? found : -1;
         }
     }
@@ -953,9 +982,11 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
     int rk[NB];
     {
         int kind[NB];          // 0 nothing, 1 single candidate, 2 re-walk this lane's rows
+        unsigned int thrs[NB];
 #pragma unroll
         for (int t = 0; t < NB; ++t) {
             kind[t] = 0;
+            thrs[t] = 0;
             if (t < args.nb && col < K && !FV_TIMING_BIT(args.debug, 4096)) {       // FV_OPT_DEBUG bit 12: timing without the refine
                 // float spacing at the largest magnitude in play: no cell that matters lies further than the code
                 // range (65535 steps) below Mx + tmp
@@ -965,6 +996,7 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
                 const float wf = (2.0f * Uf + args.window) * inv_step + (coded ? 4.2f : 3.1f);     // (two roundings per score code on the row-codes route)
                 const unsigned int W = wf < 65535.0f ? (unsigned int)wf + 1u : 65535u;
                 const unsigned int thr = Zc[t] + W;
+                thrs[t] = thr;
                 if (thr >= 65535u) {                              // saturated sums could matter: exact walk of every row
                     kind[t] = 2;
                     if (w == 0 && rg == 0) atomicAdd(&args.counters[8], 1ull);      // statistics: columns that took this branch
@@ -984,15 +1016,19 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
                 }
             }
         } else {
-            // kind 1: the one cell of row block a1 (parity par) whose z equals m1 — unique, since m2 > m1.  The block's
-            // codes are re-read (lanes without a candidate read their first block: every load unconditional, all tasks'
-            // loads in flight together), then the float64 entry and the float score of that row are gathered.
+            // kind 1: the one cell of row block a1 (parity par) whose z equals m1 — unique, if m2' > m1 and the block's own
+            // half holds no second cell inside the window: that is known only here, where the block's codes are re-read
+            // (lanes without a candidate read their first block: every load unconditional, all tasks' loads in flight
+            // together); a lane that has one becomes kind 2.  Then the float64 entry and the float score of the row are
+            // gathered (for a lane that just became kind 2 too: unused).
             uint4 ce[NB];
 #pragma unroll
             for (int t = 0; t < NB; ++t) ce[t] = LAt[(size_t)(kind[t] == 1 ? a1[t] : blk0) * (4 * TILE_W)];
 #pragma unroll
             for (int t = 0; t < NB; ++t) {
-                const int found = locate(t, kind[t] == 1 ? a1[t] : blk0, ce[t]);
+                unsigned int second;
+                const int found = locate(t, kind[t] == 1 ? a1[t] : blk0, ce[t], second);
+                kind[t] = (kind[t] == 1 && second <= thrs[t]) ? 2 : kind[t];
                 a1[t] = found;
                 Lc[t] = L64t[(size_t)(found >> 2) * (TILE_W * 4) + (found & 3)];
                 tv[t] = args.t[t].t1_in[found];
@@ -1081,7 +1117,7 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
             args.t[w].t1_out[col] = any ? r : -FLT_MAX;
             args.t[w].bp_out[col] = any ? kb : -1;
         }
-        if (args.codes & 2) {
+        if (CODES && (args.codes & 2)) {
             // FV_OPT_ROW_CODES: the tile's maximum over its real columns and every column's code relative to it, beside the floats
             // (every lane holds its column's result after wave_best; pad columns count as unreachable)
             const float val = (col < K && any) ? r : -FLT_MAX;

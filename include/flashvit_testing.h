@@ -265,7 +265,10 @@ int fv_test_beam_forward(fv_ctx *ctx, const int *ob, int T, int beam, const fv_t
 #define FV_TV_CSR64_MEM      (1ull << (FV_TV_CSR64_SHIFT + 4))   /* trellis_step_csr_f64<*, true> */
 /* Not an instantiation but a route: set IN ADDITION by every trellis_step_u16 launch whose prologue copied the score codes
  * its producers left (FV_OPT_ROW_CODES) instead of quantising the float rows.  Never set while that option resolves to off,
- * as it does for fv_test_forward under auto. */
+ * as it does for fv_test_forward under auto.  While the option is off no launch reads or writes codes, and a single-task
+ * bit (FV_TV_U16_*_NB1) WITHOUT this one stands for the instantiation that has no code for the route at all
+ * (trellis_step_u16<1, *, *, *, false>); beside FV_TV_ROW_CODES the same bit stands for the form that holds both
+ * prologues and the code-writing tail. */
 #define FV_TV_ROW_CODES_SHIFT 63
 #define FV_TV_ROW_CODES      (1ull << FV_TV_ROW_CODES_SHIFT)
 
