@@ -274,7 +274,7 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
         for (int base = 0; base < np; base += fvb::BEAM_CHUNK) {
             fvb::BeamEndArgs e;
             e.K = K; e.beam = beam; e.n = std::min(fvb::BEAM_CHUNK, np - base);
-            e.lazy = lazy_walk; e.flag = ctx->d_needfull.p;
+            e.lazy = lazy_walk; e.flag = ctx->d_needfull.p; e.restarts = ctx->d_counters.p + fvk::BT_COUNTER;
             for (int q = 0; q < e.n; ++q)
                 e.p[q] = fvb::BeamEnd{ passes[base + q].L, passes[base + q].R, passes[base + q].whole ? 1 : 0, passes[base + q].seq };
             hipLaunchKernelGGL(fvb::beam_end_backtrack, dim3(e.n), dim3(64), 0, ctx->stream, e, ctx->d_slot_val.p,

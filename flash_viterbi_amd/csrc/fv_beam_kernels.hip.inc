@@ -1664,6 +1664,7 @@ struct BeamEndArgs {
                        //    sequence (flag[p.seq]) and ends the walk
                        // 0: after tie_fixup; runs only if that flag is up
     int *flag;         // one per sequence of the call
+    unsigned long long *restarts;      // counter fvk::BT_COUNTER: retries of the chunk walk
     BeamEnd p[BEAM_CHUNK];
 };
 
@@ -1756,6 +1757,7 @@ __global__ __launch_bounds__(64) void beam_end_backtrack(const BeamEndArgs args,
         const int f = bad ? __ffsll((long long)bad) - 1 : 64;          // chunks base .. f - 1 are final
         met_tag |= __any(tag && lane >= base && lane < f);
         if (!bad) break;
+        if (lane == 0) atomicAdd(args.restarts, 1ull);
         exact = __shfl(y, f - 1);
         base = f;
     }

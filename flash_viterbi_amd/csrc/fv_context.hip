@@ -228,6 +228,7 @@ static int read_stats(fv_ctx *ctx, const unsigned long long *counters, clk::time
     st.beam_list_long = (long long)counters[12];
     st.beam_list_entries = (long long)counters[13];
     st.beam_chain_cuts = (long long)counters[14];
+    st.bt_restarts = (long long)counters[fvk::BT_COUNTER];
     if (counters[fvk::FLAT_COUNTER]) {               // the resolver of a flat decode met a generation it could not commit
         st.flat_first_miss = (int)(counters[fvk::FLAT_COUNTER] >> 32);
         st.flat_missed = (int)(counters[fvk::FLAT_COUNTER] & 0xffffffffull);

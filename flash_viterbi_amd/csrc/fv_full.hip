@@ -662,7 +662,8 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
             const fv::Pass &p = passes[base + q];
             ch.p[q] = fvk::PassDesc{ p.L, p.R, p.from_pi ? 1 : 0, p.whole ? 1 : 0, 0 };
         }
-        hipLaunchKernelGGL(fvk::backtrack, dim3(ch.n), dim3(64), 0, ctx->stream, ch, ctx->d_bp.p, K, ctx->d_ans.p);
+        hipLaunchKernelGGL(fvk::backtrack, dim3(ch.n), dim3(64), 0, ctx->stream, ch, ctx->d_bp.p, K, ctx->d_ans.p,
+                           ctx->d_counters.p + fvk::BT_COUNTER);
         FV_HIP(hipGetLastError());
     }
     return 0;
@@ -847,7 +848,7 @@ int run_flat_full(fv_ctx *ctx, int kernel, int T)
     }
     // every chain in one launch, then the resolver
     hipLaunchKernelGGL(fvk::backtrack_flat, dim3(np), dim3(64), 0, ctx->stream, ctx->d_flat.p, ctx->d_bp.p, ctx->d_flat_bp.p, K,
-                       ctx->d_snap.p, ctx->d_chain.p);
+                       ctx->d_snap.p, ctx->d_chain.p, ctx->d_counters.p + fvk::BT_COUNTER);
     FV_HIP(hipGetLastError());
     fvk::FlatGens gens;
     gens.ngen = (int)fp.gen_begin.size() - 1;
@@ -1361,7 +1362,8 @@ int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *pat
         fvk::PassChunk ch;
         ch.n = 1;
         ch.p[0] = fvk::PassDesc{ 0, T - 1, 1, 1, 0 };
-        hipLaunchKernelGGL(fvk::backtrack, dim3(1), dim3(64), 0, ctx->stream, ch, ctx->d_bp.p, K, ctx->d_ans.p);
+        hipLaunchKernelGGL(fvk::backtrack, dim3(1), dim3(64), 0, ctx->stream, ch, ctx->d_bp.p, K, ctx->d_ans.p,
+                           ctx->d_counters.p + fvk::BT_COUNTER);
         FV_HIP(hipGetLastError());
     }
     ctx->close_stats((long long)K * K, 0);

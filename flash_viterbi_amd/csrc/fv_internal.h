@@ -238,7 +238,7 @@ struct fv_ctx {
         }                                                                                     \
     } while (0)
 
-constexpr int FV_NCOUNTERS = 16;   // device statistics words (fv_kernels.hip.inc / fv_beam_kernels.hip.inc say which is which)
+constexpr int FV_NCOUNTERS = 17;   // device statistics words (fv_kernels.hip.inc / fv_beam_kernels.hip.inc say which is which)
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline int fv_ldq(int K) { return round_up(K, 128); }         // pitch of the row-major 16-bit table

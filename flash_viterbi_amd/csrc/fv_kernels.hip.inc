@@ -1976,8 +1976,9 @@ __global__ __launch_bounds__(256) void last_column_csr(const CsrColArgs args)
 // restarts from the verified state, and the others are walked again behind it.
 //
 // One pass [L, R] walked by one wave: bp is the arg row of time L + 1 (the row of time j at bp + (j - L - 1) * K), `end` the
-// state at time R, out[j - L] receives c[j] for j = L .. R-1.
-__device__ __forceinline__ void backtrack_walk(int L, int R, const int *bp, int K, int end, int *out)
+// state at time R, out[j - L] receives c[j] for j = L .. R-1.  `restarts` (counter BT_COUNTER) counts the retries: one atomic of
+// lane 0 per failed verification, nothing on the way of a walk whose chunks all stand.
+__device__ __forceinline__ void backtrack_walk(int L, int R, const int *bp, int K, int end, int *out, unsigned long long *restarts)
 {
     const int lane = threadIdx.x, len = R - L;
     auto hop = [&](int st, int j) { return st >= 0 ? bp[(size_t)(j - L - 1) * K + st] : -1; };       // state at time j -> state at time j - 1
@@ -2005,16 +2006,17 @@ __device__ __forceinline__ void backtrack_walk(int L, int R, const int *bp, int 
         const bool ok = lane <= base || top(lane) <= L || min(top(base), top(lane) + BT_WARMUP) == top(base) || x == y_above;
         const unsigned long long bad = ~__ballot(ok);
         if (!bad) break;
+        if (lane == 0) atomicAdd(restarts, 1ull);
         const int f = __ffsll((long long)bad) - 1;       // first chunk that entered with the wrong state: everything above it is final
         exact = __shfl(y, f - 1);
         base = f;
     }
 }
 
-__global__ __launch_bounds__(64) void backtrack(const PassChunk ch, const int *bp, int K, int *ans)
+__global__ __launch_bounds__(64) void backtrack(const PassChunk ch, const int *bp, int K, int *ans, unsigned long long *restarts)
 {
     const PassDesc p = ch.p[blockIdx.x];
-    backtrack_walk(p.L, p.R, bp + (size_t)(p.L + 1) * K, K, ans[p.R], ans + p.L);
+    backtrack_walk(p.L, p.R, bp + (size_t)(p.L + 1) * K, K, ans[p.R], ans + p.L, restarts);
 }
 
 // ---------------------------------------------------------------- flat generations (FV_OPT_FLAT_GENERATIONS)
@@ -2031,11 +2033,12 @@ __global__ void flat_snapshot(const int *ans, int *S, int T, int poison, int K)
 
 // The back-track of every pass of the flat set in one launch, a wave each: arg rows at the pass's private rows (or, for a
 // generation-1 pass, at its own times of the by-time array), end state from S, chain into the pass's slot.
-__global__ __launch_bounds__(64) void backtrack_flat(const FlatDesc *desc, const int *bp, const int *flat_bp, int K, const int *S, int *chains)
+__global__ __launch_bounds__(64) void backtrack_flat(const FlatDesc *desc, const int *bp, const int *flat_bp, int K, const int *S, int *chains,
+                                                      unsigned long long *restarts)
 {
     const FlatDesc p = desc[blockIdx.x];
     const int *rows = p.arg_row < 0 ? bp + (size_t)(p.L + 1) * K : flat_bp + (size_t)p.arg_row * K;
-    backtrack_walk(p.L, p.R, rows, K, S[p.R], chains + p.chain);
+    backtrack_walk(p.L, p.R, rows, K, S[p.R], chains + p.chain, restarts);
 }
 
 // The resolver, one workgroup.  Generation by generation: a pass ran from S[L-1] and S[R]; the generation-by-generation

@@ -31,6 +31,7 @@ struct FlatDesc { int L, R, generation, chain; long long arg_row; };
 constexpr int FLAT_MAX_GENS = 40;          // (a generation halves the pass length: T < 2^31 has at most 32)
 struct FlatGens { int ngen; int begin[FLAT_MAX_GENS + 1]; };   // passes [begin[g], begin[g + 1]) are generation g + 1
 constexpr int FLAT_COUNTER = 15;           // device statistics word of the resolver: first-miss generation << 32 | missed passes
+constexpr int BT_COUNTER = 16;             // device statistics word of the back-tracks: passes through the retry branch of the chunk walk (fv_stats.bt_restarts)
 
 // LDS of one trellis_step / trellis_step_u16 workgroup (score rows + reduction scratch)
 template <int NB>

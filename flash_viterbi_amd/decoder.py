@@ -58,7 +58,8 @@ class Stats(ctypes.Structure):
                 ("beam_list_short", ctypes.c_longlong), ("beam_list_long", ctypes.c_longlong), ("beam_list_entries", ctypes.c_longlong),
                 ("beam_chain_cuts", ctypes.c_longlong),
                 ("flat_passes", ctypes.c_int), ("flat_missed", ctypes.c_int), ("flat_first_miss", ctypes.c_int),
-                ("set_emissions_ms", ctypes.c_double), ("emission_rows", ctypes.c_longlong)]
+                ("set_emissions_ms", ctypes.c_double), ("emission_rows", ctypes.c_longlong),
+                ("bt_restarts", ctypes.c_longlong)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

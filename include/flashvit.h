@@ -199,6 +199,10 @@ typedef struct {
                                    the other statistics cover both parts */
     double set_emissions_ms;    /* host wall time of the last fv_set_emissions (copy, staging kernel, its one sync), 0 after a refused one; kept across decodes */
     long long emission_rows;    /* rows staged by fv_set_emissions (0: none); kept across decodes */
+    long long bt_restarts;      /* back-tracks of 128 steps or more are walked by 64 lanes from guessed states and verified chunk by chunk:
+                                   the times a chunk had entered with the wrong state and the walk below it was run again, summed over every
+                                   back-track launch of the call (a flat decode's speculative passes, committed or not, and both walks of a
+                                   FLASH-BS pass included); 0 when every survivor path had merged inside the warm-up */
 } fv_stats;
 
 /* Device + stream + workspace owner.  Replaces `vit = create_vit()`'s allocation role

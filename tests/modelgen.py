@@ -77,6 +77,71 @@ def wide_model(kind, K, M, T, seed):
     return hostio.quantize_text16(A), hostio.quantize_text16(Bm), hostio.quantize_text16(Pi), ob
 
 
+def rotor(K, M, noise, seed):
+    """State k moves to k + 1 (mod K).  noise = 0: every column has exactly one predecessor, so no two back-track chains
+    ever merge — a guessed start is wrong for good (tests/test_gpu_pass_ends.py).  noise > 0: two more edges of that
+    weight per row (rows renormalised): chains merge, slowly.  B and Pi ~ U(0.1, 1), normalised.  float32 (A, B, Pi)."""
+    rs = np.random.RandomState(seed)
+    A = np.zeros((K, K))
+    A[np.arange(K), (np.arange(K) + 1) % K] = 1.0
+    if noise:
+        for k in range(K):
+            others = np.delete(np.arange(K), (k + 1) % K)
+            A[k, rs.choice(others, size=2, replace=False)] = noise
+        A /= A.sum(axis=1, keepdims=True)
+    Bm = rs.uniform(0.1, 1.0, (K, M))
+    Bm /= Bm.sum(axis=1, keepdims=True)
+    Pi = rs.uniform(0.1, 1.0, K)
+    Pi /= Pi.sum()
+    return hostio.quantize_text16(A), hostio.quantize_text16(Bm), hostio.quantize_text16(Pi)
+
+
+def rotor_tied_column(K=131, g=30):
+    """The rotor with weight 1 on every edge, one more edge g-1 -> g+1, uniform Pi, and two symbols every state emits with
+    1/2 — but state g-1 emits symbol 1 with 1/4 (rows not normalised).  Every state has the same score unless its chain
+    passed state g-1 under symbol 1, so column g+1 — the only one with two predecessors — is tied at every time except
+    the two after a symbol 1: a FLASH-BS decode tags that cell at almost every time, and only there.  float32 (A, B, Pi)."""
+    A = np.zeros((K, K))
+    A[np.arange(K), (np.arange(K) + 1) % K] = 1.0
+    A[g - 1, g + 1] = 1.0
+    Bm = np.full((K, 2), 0.5)
+    Bm[g - 1, 1] = 0.25
+    return hostio.quantize_text16(A), hostio.quantize_text16(Bm), hostio.quantize_text16(np.full(K, 1.0 / K))
+
+
+CIRCULANT_OFF = {2053: (255, 256, 257, 1023, 1024, 1025, 1500, 2000),
+                 1025: (100, 255, 256, 257, 500, 700, 900, 1001),
+                 257: (50, 100, 128, 150, 200, 230, 251, 255)}
+CIRCULANT_CUT = {2053: (1030, 300), 1025: (1000, 300), 257: (250, 60)}      # states below it cannot emit symbol 8 / symbol 9
+
+
+def circulant_ties(K=2053, OFF=None, cuts=None):
+    """State k moves to k + o (mod K) for the eight o of OFF, weight 1/8 each; Pi uniform; ten symbols: 0 .. 7 are emitted
+    by every state with 1/8, symbol 8 only by the states from cuts[0] on, symbol 9 only by those from cuts[1] on (the rows
+    of B are deliberately not normalised).  Every finite score of a step is the same float, so every back-pointer is the
+    lowest live predecessor and every end pick the lowest live state: after symbol 8 / 9 that is cuts[0] / cuts[1].  The
+    predecessors of a column lie up to 2000 states apart: tied candidates in different waves, workgroup trips and
+    1024-blocks of the kernels that pick among them.  float32 (A, B, Pi)."""
+    OFF = CIRCULANT_OFF[K] if OFF is None else OFF
+    cuts = CIRCULANT_CUT[K] if cuts is None else cuts
+    A = np.zeros((K, K), dtype=np.float32)
+    for o in OFF:
+        A[np.arange(K), (np.arange(K) + o) % K] = 0.125
+    Bm = np.full((K, 10), 0.125, dtype=np.float32)
+    Bm[:cuts[0], 8] = 0
+    Bm[:cuts[1], 9] = 0
+    return A, Bm, np.full(K, np.float32(1.0 / K))
+
+
+def circulant_observations(T, last, seed):
+    """symbols 0 .. 7 at random, `last` (8 or 9: a cut; anything else: none) at the last time and at T/3 and 2T/3"""
+    ob = np.random.RandomState(seed).randint(0, 8, T).astype(np.int32)
+    if last in (8, 9):
+        ob[T // 3] = ob[2 * T // 3] = last
+    ob[T - 1] = last
+    return ob
+
+
 def model64(spec):
     kind = spec["kind"]
     K, M = spec["K"], spec["M"]

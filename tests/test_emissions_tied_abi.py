@@ -1,6 +1,7 @@
 """fv_set_emission_map and the 16-bit score types without a GPU: the function is exported and listed in the drop-in
 ABI, the two constants equal the header's (a separate enum: the original two-member line stays as it was), and fv_stats
-gained no member."""
+gained no member with them (its one later member, bt_restarts, is listed)."""
+import ctypes
 import inspect
 import os
 import re
@@ -31,7 +32,8 @@ def test_constants_match_the_header():
 
 def test_stats_gained_no_member():
     names = [n for n, _ in decoder.Stats._fields_]
-    assert names[-2:] == ["set_emissions_ms", "emission_rows"]
+    assert names[-3:] == ["set_emissions_ms", "emission_rows", "bt_restarts"]      # (bt_restarts: appended later, for the back-tracks)
+    assert dict(decoder.Stats._fields_)["bt_restarts"] is ctypes.c_longlong
     text = header()
     body = re.sub(r"/\*.*?\*/", "", text[text.index("typedef struct {\n    double set_model_ms"):text.index("} fv_stats;")], flags=re.S)
     assert re.findall(r"\b(?:double|long long|int)\s+(\w+)\s*;", body) == names
