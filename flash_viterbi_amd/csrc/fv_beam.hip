@@ -332,6 +332,7 @@ extern "C" int fv_decode_beam(fv_ctx *ctx, const int *ob, int T, int n_split, in
                               int *path_out, float *score_out)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (ctx->csr && !ctx->opt_sparse_beam) { ctx->detail = "fv_decode_beam: not available on a model set by fv_set_model_sparse (the beam kernels gather dense rows)"; return FV_ERR_UNSUPPORTED; }
     if (ctx->group && ctx->group_rank == 0) {
         if (!path_out || T < 2) return FV_ERR_ARG;
@@ -523,6 +524,7 @@ extern "C" int fv_decode_beam_batch(fv_ctx *ctx, const int *ob, const long long 
                                     int mode, int *path_out, float *score_out, int *status_out)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (ctx->csr && !ctx->opt_sparse_beam) { ctx->detail = "fv_decode_beam_batch: not available on a model set by fv_set_model_sparse (the beam kernels gather dense rows)"; return FV_ERR_UNSUPPORTED; }
     if (ctx->group || ctx->comm || ctx->nranks > 1) {
         ctx->detail = "fv_decode_beam_batch: one device, no communicator and no partition (sequences are not dealt to ranks)";
@@ -645,6 +647,7 @@ extern "C" int fv_test_beam_step(fv_ctx *ctx, int beam, const fv_test_beam_set *
                                  unsigned long long *variants_out)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (fvi::group_size(ctx) > 1) { ctx->detail = "fv_test_beam_step: one device per context"; return FV_ERR_ARG; }
     if (ctx->csr && !ctx->opt_sparse_beam) { ctx->detail = "fv_test_beam_step: not available on a model set by fv_set_model_sparse"; return FV_ERR_UNSUPPORTED; }
     return fvi::drained(ctx, test_beam_step_impl(ctx, beam, sets, nsets, sym, speculative, theta, next_bound, cand_cap, scores_out,
@@ -767,6 +770,7 @@ extern "C" int fv_test_beam_select(fv_ctx *ctx, int K, int beam, int s, const fv
                                    float *slot_val_out, int *slot_state_out, unsigned long long *selects_out)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (fvi::group_size(ctx) > 1) { ctx->detail = "fv_test_beam_select: one device per context"; return FV_ERR_ARG; }
     return fvi::drained(ctx, test_beam_select_impl(ctx, K, beam, s, sets, nsets, prev_theta, prev_margin, seed, want_layout, cand_cap_out,
                                                    cut_out, member_val_out, member_state_out, counters_out, slot_val_out,
@@ -867,6 +871,7 @@ extern "C" int fv_test_beam_forward(fv_ctx *ctx, const int *ob, int T, int beam,
                                     const fv_test_beam_tables *out)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (fvi::group_size(ctx) > 1 || ctx->comm || ctx->nranks > 1) {
         ctx->detail = "fv_test_beam_forward: one device, no communicator and no partition";
         return FV_ERR_ARG;

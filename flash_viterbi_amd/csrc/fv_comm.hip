@@ -118,6 +118,7 @@ extern "C" int fv_comm_unique_id(void *id_out)
 extern "C" int fv_set_partition(fv_ctx *ctx, int rank, int nranks)
 {
     if (!ctx || nranks < 1 || rank < 0 || rank >= nranks) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (ctx->comm || ctx->group) return FV_ERR_STATE;
     ctx->rank = rank; ctx->nranks = nranks;
     return FV_OK;
@@ -126,6 +127,7 @@ extern "C" int fv_set_partition(fv_ctx *ctx, int rank, int nranks)
 extern "C" int fv_comm_init(fv_ctx *ctx, int rank, int nranks, const void *id)
 {
     if (!ctx || !id || nranks < 1 || rank < 0 || rank >= nranks) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (ctx->comm || ctx->group) return FV_ERR_STATE;
     FV_HIP(hipSetDevice(ctx->device));
     ncclUniqueId uid;

@@ -348,6 +348,7 @@ extern "C" void fv_destroy(fv_ctx *ctx)
     }
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    fvi::stream_drop(ctx);
     if (ctx->comm) ncclCommDestroy(ctx->comm);
     if (ctx->h_pin) { (void)hipHostFree(ctx->h_pin); ctx->h_pin = nullptr; ctx->h_pin_n = 0; }
     for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
@@ -751,6 +752,7 @@ extern "C" int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const 
                                    const float *Pi, int K, int M)
 {
     if (!ctx || !row_ptr || !B || !Pi || K < 1 || M < 1) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     auto t0 = clk::now();
     fvi::HostCsr h;
     int rc = FV_OK;
@@ -768,6 +770,7 @@ extern "C" int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const 
 extern "C" int fv_set_model(fv_ctx *ctx, const float *A, const float *B, const float *Pi, int K, int M)
 {
     if (!ctx || !A || !B || !Pi || K < 1 || M < 1) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     auto t0 = clk::now();
     fvi::HostTables h;
     int rc = fvi::build_host_tables(A, B, Pi, K, M, h, ctx->detail);
@@ -783,9 +786,6 @@ extern "C" int fv_set_model(fv_ctx *ctx, const float *A, const float *B, const f
 }
 
 namespace fvi {
-
-constexpr size_t emis_elem_size[4] = { 4, 8, 2, 2 };      // by FV_EMIS_LOG_F32, _F64, _F16, _BF16
-inline bool emis_dtype_ok(int dtype) { return dtype >= FV_EMIS_LOG_F32 && dtype <= FV_EMIS_LOG_BF16; }
 
 // fv_set_emissions on one device.  A block the kernel cannot read where it lies (host memory; a multi-device context,
 // whose members each take a copy) goes into a raw device buffer first, released before the call returns.
@@ -821,7 +821,7 @@ static int stage_emissions_on(fv_ctx *ctx, const void *scores, int dtype, int T,
     unsigned long long got[2] = { 0ull, ~0ull };
     FV_HIP(hipMemsetAsync(ctx->d_emflags.p, 0, sizeof(unsigned long long), ctx->stream));               // no flag
     FV_HIP(hipMemsetAsync(ctx->d_emflags.p + 1, 0xFF, sizeof(unsigned long long), ctx->stream));        // no refused index
-    if (int rc = launch_stage_emissions(ctx, src, dtype, ld, T, ctx->EMap.p, ctx->emis_P)) return rc;
+    if (int rc = launch_stage_emissions(ctx, src, dtype, ld, T, ctx->EMap.p, ctx->emis_P, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p)) return rc;
     FV_HIP(hipMemcpyAsync(got, ctx->d_emflags.p, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
     FV_HIP(hipStreamSynchronize(ctx->stream));              // the one sync of the call: copies and kernel are done, `raw` can go
     if (got[0] & FV_EMIS_BAD) {
@@ -845,6 +845,7 @@ static int stage_emissions_on(fv_ctx *ctx, const void *scores, int dtype, int T,
 extern "C" int fv_set_emissions(fv_ctx *ctx, const void *scores, int dtype, int T, long long ld)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     const int n = fvi::group_size(ctx);
     for (int r = 0; r < n; ++r) {                // whatever happens next, the rows staged before are gone
         fv_ctx *m = fvi::group_member(ctx, r);
@@ -886,6 +887,7 @@ extern "C" int fv_set_emissions(fv_ctx *ctx, const void *scores, int dtype, int 
 extern "C" int fv_set_emission_map(fv_ctx *ctx, const int *pdf_of_state, int P)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (ctx->K == 0) { ctx->detail = "fv_set_emission_map: no model (the map holds one entry per state of the model)"; return FV_ERR_STATE; }
     if (!pdf_of_state && P != 0) { ctx->detail = "fv_set_emission_map: pdf_of_state == NULL clears the map and takes P == 0"; return FV_ERR_ARG; }
     if (pdf_of_state) {
@@ -935,6 +937,7 @@ extern "C" int fv_set_emission_map(fv_ctx *ctx, const int *pdf_of_state, int P)
 extern "C" int fv_clear_emissions(fv_ctx *ctx)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     const int n = fvi::group_size(ctx);
     for (int r = 0; r < n; ++r) {
         fv_ctx *m = fvi::group_member(ctx, r);
@@ -977,6 +980,7 @@ extern "C" int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, i
     if (!ctx || !ms_out || !dev_scores || T < 1 || reps < 1 || ctx->K == 0 || ld < (ctx->emis_P ? ctx->emis_P : ctx->K) ||
         ld > (1ll << 59) / T || !fvi::emis_dtype_ok(dtype) || ctx->group)
         return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, dev_scores) != hipSuccess) { (void)hipGetLastError(); return FV_ERR_ARG; }
     if (at.type != hipMemoryTypeDevice || at.device != ctx->device) return FV_ERR_ARG;
@@ -993,10 +997,10 @@ extern "C" int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, i
     struct Ev { hipEvent_t &a, &b; ~Ev() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev{ e0, e1 };
     FV_HIP(hipEventCreate(&e0));
     FV_HIP(hipEventCreate(&e1));
-    if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T, ctx->EMap.p, ctx->emis_P)) return fvi::drained(ctx, rc);      // warm
+    if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T, ctx->EMap.p, ctx->emis_P, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p)) return fvi::drained(ctx, rc);      // warm
     FV_HIP(hipEventRecord(e0, ctx->stream));
     for (int r = 0; r < reps; ++r)
-        if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T, ctx->EMap.p, ctx->emis_P)) return fvi::drained(ctx, rc);
+        if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T, ctx->EMap.p, ctx->emis_P, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p)) return fvi::drained(ctx, rc);
     FV_HIP(hipEventRecord(e1, ctx->stream));
     FV_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0.0f;
@@ -1009,6 +1013,7 @@ extern "C" int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, i
 extern "C" int fv_test_flat_poison(fv_ctx *ctx, int t)
 {
     if (!ctx || t < -1) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     ctx->flat_poison = t;
     return FV_OK;
 }
@@ -1016,6 +1021,7 @@ extern "C" int fv_test_flat_poison(fv_ctx *ctx, int t)
 extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (ctx->group && ctx->group_rank == 0) {          // a multi-device context: the same option on every member
         for (int r = fvi::group_size(ctx) - 1; r >= 1; --r) {
             const int rc = fv_set_option(fvi::group_member(ctx, r), key, value);

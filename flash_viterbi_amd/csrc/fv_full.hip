@@ -916,29 +916,74 @@ int launch_init_rows(fv_ctx *ctx, const fvk::PassChunk &ch, float *rows)
 
 // Workgroups of EMIS_BLOCK states by rows, about 2048 in all (eight per CU); the kernel strides over the rest.
 template <typename TIN>
-static void launch_stage_as(fv_ctx *ctx, const void *src, long long ld, int T, const int *map, dim3 grid)
+static void launch_stage_as(fv_ctx *ctx, const void *src, long long ld, int T, const int *map, dim3 grid, float *E32, double *E64,
+                            unsigned long long *flags)
 {
     if (map)
         hipLaunchKernelGGL((fvk::stage_emissions<TIN, true>), grid, dim3(fvk::EMIS_BLOCK), 0, ctx->stream,
-                           static_cast<const TIN *>(src), ld, T, ctx->K, map, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p);
+                           static_cast<const TIN *>(src), ld, T, ctx->K, map, E32, E64, flags);
     else
         hipLaunchKernelGGL((fvk::stage_emissions<TIN, false>), grid, dim3(fvk::EMIS_BLOCK), 0, ctx->stream,
-                           static_cast<const TIN *>(src), ld, T, ctx->K, map, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p);
+                           static_cast<const TIN *>(src), ld, T, ctx->K, map, E32, E64, flags);
 }
 
 // map != NULL (P > 0): the tied form, rows of P scores gathered through the K entries of map
-int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T, const int *map, int P)
+int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T, const int *map, int P,
+                           float *E32, double *E64, unsigned long long *flags)
 {
     const int K = ctx->K;
     const int gx = std::min((K + fvk::EMIS_BLOCK - 1) / fvk::EMIS_BLOCK, 2048), gy = std::max(1, std::min(T, 2048 / gx));
     if (P <= 0) map = nullptr;
     switch (dtype) {
-    case FV_EMIS_LOG_F64: launch_stage_as<double>(ctx, src, ld, T, map, dim3(gx, gy)); break;
-    case FV_EMIS_LOG_F32: launch_stage_as<float>(ctx, src, ld, T, map, dim3(gx, gy)); break;
-    case FV_EMIS_LOG_F16: launch_stage_as<_Float16>(ctx, src, ld, T, map, dim3(gx, gy)); break;
-    case FV_EMIS_LOG_BF16: launch_stage_as<fvk::bf16_bits>(ctx, src, ld, T, map, dim3(gx, gy)); break;
+    case FV_EMIS_LOG_F64: launch_stage_as<double>(ctx, src, ld, T, map, dim3(gx, gy), E32, E64, flags); break;
+    case FV_EMIS_LOG_F32: launch_stage_as<float>(ctx, src, ld, T, map, dim3(gx, gy), E32, E64, flags); break;
+    case FV_EMIS_LOG_F16: launch_stage_as<_Float16>(ctx, src, ld, T, map, dim3(gx, gy), E32, E64, flags); break;
+    case FV_EMIS_LOG_BF16: launch_stage_as<fvk::bf16_bits>(ctx, src, ld, T, map, dim3(gx, gy), E32, E64, flags); break;
     default: ctx->detail = "fv_set_emissions: unknown dtype"; return FV_ERR_ARG;
     }
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- what fv_stream.hip takes from this file (fv_internal.h)
+
+int stream_init_row(fv_ctx *ctx, const double *lb64, const int *sym, float *row)
+{
+    fvk::PassChunk ch;
+    ch.n = 1;
+    ch.p[0] = fvk::PassDesc{ 0, 0, 1, 1, 0 };
+    if (ctx->csr)
+        hipLaunchKernelGGL(fvk::init_rows_csr, dim3((ctx->K + 255) / 256, 1), dim3(256), 0, ctx->stream, ch, ctx->CRptr.p,
+                           ctx->CRcol.p, ctx->CRlog.p, lb64, ctx->LPi64.p, sym, sym, row, ctx->K);
+    else
+        hipLaunchKernelGGL(fvk::init_rows, dim3((ctx->K + 255) / 256, 1), dim3(256), 0, ctx->stream, ch, ctx->LA64.p, ctx->nrows,
+                           lb64, ctx->LPi64.p, sym, sym, row, ctx->K, static_cast<unsigned short *>(nullptr),
+                           static_cast<float *>(nullptr), 0.0f);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+int stream_step(fv_ctx *ctx, int kernel, const float *t1_in, float *t1_out, const float *tmp_row, const double *tmp64_row,
+                int *bp_out, int reverse)
+{
+    fvk::TaskSlot sl;
+    sl.t1_in = t1_in; sl.t1_out = t1_out; sl.bp_out = bp_out; sl.tmp_row = tmp_row; sl.tmp64_row = tmp64_row;
+    return launch_step_kernel(ctx, kernel, &sl, 1, reverse);
+}
+
+int stream_end_pick(fv_ctx *ctx, const float *row, int *end, float *score)
+{
+    hipLaunchKernelGGL(fvk::final_argmax, dim3(1), dim3(1024), 0, ctx->stream, row, ctx->K, end, score);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+int stream_backtrack(fv_ctx *ctx, const int *bp, int R, int *path, unsigned long long *restarts)
+{
+    fvk::PassChunk ch;
+    ch.n = 1;
+    ch.p[0] = fvk::PassDesc{ 0, R, 1, 1, 0 };
+    hipLaunchKernelGGL(fvk::backtrack, dim3(1), dim3(64), 0, ctx->stream, ch, bp, ctx->K, path, restarts);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -953,6 +998,7 @@ int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *pat
 extern "C" int fv_decode_full(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, int *path_out, float *score_out)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (ctx->group && ctx->group_rank == 0 && !ctx->vanilla) {
         // multi-device context: every member decodes its share on its own device and host thread, one gather merges them
         if (!path_out || T < 2) return FV_ERR_ARG;
@@ -972,6 +1018,7 @@ extern "C" int fv_decode_full_batch(fv_ctx *ctx, const int *ob, const long long 
                                     int *path_out, float *score_out, int *status_out)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (ctx->group || ctx->comm || ctx->nranks > 1) {
         ctx->detail = "fv_decode_full_batch: one device, no communicator and no partition (sequences are not dealt to ranks)";
         return FV_ERR_UNSUPPORTED;
@@ -984,10 +1031,10 @@ namespace {
 // choice for the model and of the sequence, the kernel choice itself, the 16-bit table of a model beyond the float32
 // kernels' limit (built on the device on first use) and the workspace for `rows_needed` passes in flight.  (The LDS
 // attributes of every step kernel, fvi::full_setup, are set once by fv_create.)
-int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &kernel, int nscores = 1, bool auto_codes = false)
+// admit_full: the admission and the choice, in the order the refusals have always come in (ob == NULL: no sequence to
+// check — fvi::stream_admit, whose symbols arrive push by push).  prepare_full: that, then workspace and row codes.
+int admit_full(fv_ctx *ctx, const int *ob, int T, int &kernel)
 {
-    ctx->row_codes = 0;
-    ctx->row_coded.clear();
     // Beyond the float32 kernels' LDS limit (one score row of K floats) two routes remain:
     //   * the packed 16-bit kernel — a row of 16-bit score codes is half the bytes (K <= 65536); it needs every model entry
     //     in [0,1], and its table is built on the device on first use;
@@ -1002,14 +1049,13 @@ int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &ker
             return FV_ERR_UNSUPPORTED;
         }
         if (!f64 && !ctx->view.logs_nonpositive) {
-            ctx->detail = "fv_set_model_sparse: the walk over the stored entries is a filter kernel and needs every model entry in [0,1] "
-                          "(and every staged emission score <= 0); FV_KERNEL_CSR_F64 decodes such input";
+            ctx->detail = fvi::CSR_FILTER_RANGE_DETAIL;
             return FV_ERR_UNSUPPORTED;
         }
-        for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
+        for (int j = 0; ob && j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
         FV_HIP(hipSetDevice(ctx->device));
         kernel = f64 ? FV_KERNEL_CSR_F64 : FV_KERNEL_SPARSE_CSR;
-        return fvi::ensure_workspace(ctx, T, rows_needed, nscores);
+        return 0;
     }
     if (ctx->opt_kernel == FV_KERNEL_CSR_F64) {
         ctx->detail = "FV_KERNEL_CSR_F64 walks the stored entries of a model set by fv_set_model_sparse: this model was set by fv_set_model";
@@ -1026,9 +1072,9 @@ int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &ker
         ctx->detail = "full-state decode of K > ~40100: FV_KERNEL_AUTO, FV_KERNEL_U16_REFINE (K <= 65536), FV_KERNEL_Q16_REFINE (both: model entries in [0,1]) or FV_KERNEL_F64_STREAM";
         return FV_ERR_UNSUPPORTED;
     }
-    for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
+    for (int j = 0; ob && j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
     if (ctx->opt_kernel >= FV_KERNEL_F32_REFINE && !ctx->view.logs_nonpositive) {
-        ctx->detail = "the filter+refine kernels need every model entry in [0,1] (and every staged emission score <= 0)";
+        ctx->detail = fvi::FILTER_RANGE_DETAIL;
         return FV_ERR_UNSUPPORTED;
     }
     FV_HIP(hipSetDevice(ctx->device));
@@ -1053,7 +1099,16 @@ int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &ker
         ctx->qscale = -stepf;
         ctx->laq16_ready = true;
     }
+    return 0;
+}
+
+int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &kernel, int nscores = 1, bool auto_codes = false)
+{
+    ctx->row_codes = 0;
+    ctx->row_coded.clear();
+    if (int rc = admit_full(ctx, ob, T, kernel)) return rc;
     if (int rc = fvi::ensure_workspace(ctx, T, rows_needed, nscores)) return rc;
+    if (ctx->csr) return 0;
     // FV_OPT_ROW_CODES: which launch families of the packed kernel take their score codes from the producer (auto_codes: the
     // caller is a decode auto was measured on — fv_decode_full of one sequence; the others take the route under 2 only)
     if (kernel == FV_KERNEL_U16_REFINE && !ctx->vanilla) {
@@ -1063,6 +1118,23 @@ int prepare_full(fv_ctx *ctx, const int *ob, int T, size_t rows_needed, int &ker
     return ensure_row_codes(ctx, rows_needed);
 }
 
+}  // namespace
+
+// a stream's steps are single-task launches from rows of its own: the emission term is the model's log B until a
+// score push refuses what the chosen kernel cannot take; row codes stay off
+int fvi::stream_admit(fv_ctx *ctx, int &kernel)
+{
+    static const int none = 0;
+    const int *symbols = &none;                   // (any non-NULL sequence: the view of a decode by symbols)
+    if (int rc = fvi::emission_view(ctx, symbols, 0)) return rc;
+    ctx->row_codes = 0;
+    ctx->row_coded.clear();
+    ctx->lstream = nullptr;
+    ctx->forked_batches = false;
+    return admit_full(ctx, nullptr, 0, kernel);
+}
+
+namespace {
 // statistics of a full-state decode about to start: the table bytes a step of `kernel` streams
 void start_full_stats(fv_ctx *ctx, int kernel, int generations)
 {
@@ -1244,6 +1316,7 @@ extern "C" int fv_test_forward(fv_ctx *ctx, const int *ob, int T, const fv_test_
                                float *rows_out, int *bp_out, unsigned long long *variants_out)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (fvi::group_size(ctx) > 1) { ctx->detail = "fv_test_forward: one device per context"; return FV_ERR_ARG; }
     return fvi::drained(ctx, test_forward_impl(ctx, ob, T, passes, npasses, rows_out, bp_out, variants_out));
 }
@@ -1251,6 +1324,7 @@ extern "C" int fv_test_forward(fv_ctx *ctx, const int *ob, int T, const fv_test_
 extern "C" int fv_decode_vanilla(fv_ctx *ctx, const int *ob, int T, int *path_out, float *score_out)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     // (a model set by fv_set_model_sparse: the float64 walk carries the baseline's rounding order, the filter walk cannot)
     if (ctx->csr && ctx->opt_kernel != FV_KERNEL_CSR_F64) { ctx->detail = "fv_decode_vanilla: not available on a model set by fv_set_model_sparse (its kernel reads the dense table) unless FV_KERNEL_CSR_F64 is selected"; return FV_ERR_UNSUPPORTED; }
     const int keep_kernel = ctx->opt_kernel;
@@ -1271,6 +1345,7 @@ extern "C" int fv_decode_vanilla(fv_ctx *ctx, const int *ob, int T, int *path_ou
 extern "C" int fv_decode_checkpoint(fv_ctx *ctx, const int *ob, int T, int step, int *path_out, float *score_out)
 {
     if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
     if (ctx->csr) { ctx->detail = "fv_decode_checkpoint: not available on a model set by fv_set_model_sparse (its kernel reads the dense table)"; return FV_ERR_UNSUPPORTED; }
     return fvi::drained(ctx, decode_checkpoint_impl(ctx, ob, T, step, path_out, score_out));
 }

@@ -4,6 +4,7 @@
 //   fv_full.hip     full-state kernels and their decode drivers (FLASH, vanilla, checkpoint)
 //   fv_beam.hip     FLASH-BS kernels and their decode driver
 //   fv_comm.hip     multi-GPU: partition, RCCL all-gather, merge, the single-process multi-device context
+//   fv_stream.hip   fv_stream_*: the online decode — the ancestor kernels, the stream's own buffers and its entry points
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -195,6 +196,13 @@ struct fv_ctx {
     struct fv_group *group = nullptr;
     int group_rank = 0;
 
+    // fv_stream_* (fv_stream.hip): the open stream and its device buffers, which are its own — allocated at open and on
+    // growth, freed at close or abort, in no workspace request and not in each_buffer — and the statistics of the open or
+    // the last stream
+    struct fv_stream *strm = nullptr;
+    fv_stream_stats strm_stats{};
+    bool strm_any = false;
+
     fv_stats stats{};
     // statistics of a decode about to start: everything cleared but what the model and the staged emissions own
     void start_stats(int kernel, int generations, long long table_bytes_per_step, double density_reported)
@@ -236,6 +244,15 @@ struct fv_ctx {
             ctx->detail = std::string(#call) + ": " + hipGetErrorString(e_);                  \
             return e_ == hipErrorOutOfMemory ? FV_ERR_NOMEM : FV_ERR_DEVICE;                  \
         }                                                                                     \
+    } while (0)
+
+// every entry point that runs on the context's buffers or changes what a stream was opened on refuses while one is open
+#define FV_NO_STREAM(c)                                                                                        \
+    do {                                                                                                      \
+        if ((c)->strm) {                                                                                      \
+            (c)->detail = "a stream is open on this context: fv_stream_close or fv_stream_abort first";       \
+            return FV_ERR_STATE;                                                                              \
+        }                                                                                                     \
     } while (0)
 
 constexpr int FV_NCOUNTERS = 17;   // device statistics words (fv_kernels.hip.inc / fv_beam_kernels.hip.inc say which is which)
@@ -306,7 +323,13 @@ int emission_view(fv_ctx *ctx, const int *&ob, long long T);
 // fvk::stage_emissions lives with the full-state kernels (fv_full.hip); fv_set_emissions launches it through here
 enum { FV_EMIS_BAD = 1, FV_EMIS_POSITIVE = 2 };
 // (map: the device copy of the emission map and P its class count for the tied form; NULL / 0 without a map)
-int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T, const int *map, int P);
+// E32 / E64: the two tables the rows go to, flags: the two words the value rules report into (fv_set_emissions: the
+// context's; a stream: its own chunk tables)
+int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T, const int *map, int P,
+                           float *E32, double *E64, unsigned long long *flags);
+// fv_set_emissions' argument rules (dtype, element sizes), shared with fv_stream_push_emissions
+constexpr size_t emis_elem_size[4] = { 4, 8, 2, 2 };      // by FV_EMIS_LOG_F32, _F64, _F16, _BF16
+inline bool emis_dtype_ok(int dtype) { return dtype >= FV_EMIS_LOG_F32 && dtype <= FV_EMIS_LOG_BF16; }
 // decode prologue: observation sequence to the device (through the pinned block), counters and answers cleared
 int begin_decode(fv_ctx *ctx, const int *ob, int T);
 // big-LDS attributes of the kernels each translation unit owns
@@ -314,6 +337,25 @@ int full_setup(fv_ctx *ctx);
 int beam_setup(fv_ctx *ctx);
 // fvk::init_rows lives with the full-state kernels; the beam driver starts its passes from the same rows
 int launch_init_rows(fv_ctx *ctx, const fvk::PassChunk &ch, float *rows);
+// What a stream (fv_stream.hip) takes from the full-state path, whose kernels live in fv_full.hip.
+// stream_admit: the kernel fv_decode_full would run this model on under the options in force, refused as there.
+int stream_admit(fv_ctx *ctx, int &kernel);
+// time 0 from Pi: the init row, with the emission term lb64[sym[0] * K + i] (sym on the device)
+int stream_init_row(fv_ctx *ctx, const double *lb64, const int *sym, float *row);
+// one single-task step launch, the form the whole-sequence pass of a one-shot decode takes
+int stream_step(fv_ctx *ctx, int kernel, const float *t1_in, float *t1_out, const float *tmp_row, const double *tmp64_row,
+                int *bp_out, int reverse);
+// the end pick on `row` into *end / *score, and the back-track of local times 0 .. R from path[R] through the arg rows
+// (row j of `bp`: local time j; row 0 is never read) into path[0 .. R-1]
+int stream_end_pick(fv_ctx *ctx, const float *row, int *end, float *score);
+int stream_backtrack(fv_ctx *ctx, const int *bp, int R, int *path, unsigned long long *restarts);
+// what a filter kernel answers to input beyond [0,1] / above 0 (the one-shot decodes' admission and a stream's score push)
+constexpr const char *FILTER_RANGE_DETAIL = "the filter+refine kernels need every model entry in [0,1] (and every staged emission score <= 0)";
+constexpr const char *CSR_FILTER_RANGE_DETAIL =
+    "fv_set_model_sparse: the walk over the stored entries is a filter kernel and needs every model entry in [0,1] "
+    "(and every staged emission score <= 0); FV_KERNEL_CSR_F64 decodes such input";
+// frees an open stream's buffers (fv_destroy, close, abort)
+void stream_drop(fv_ctx *ctx);
 // fv_comm.hip
 // Multi-device context: one host thread per member runs the same decode on its own device (whole-sequence pass + the
 // segments the member owns), the members meet in ONE gather of their answer arrays.

@@ -65,6 +65,17 @@ class Stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class StreamStats(ctypes.Structure):
+    """fv_stream_stats: the open stream, or the last one closed or aborted."""
+    _fields_ = [("times", ctypes.c_longlong), ("committed", ctypes.c_longlong), ("pushes", ctypes.c_longlong),
+                ("checks", ctypes.c_longlong), ("commits", ctypes.c_longlong), ("lag_max", ctypes.c_longlong),
+                ("arg_rows_capacity", ctypes.c_longlong), ("regrows", ctypes.c_longlong), ("bt_restarts", ctypes.c_longlong),
+                ("push_ms_total", ctypes.c_double), ("kernel", ctypes.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FlatInfo(ctypes.Structure):
     """fv_flat_info: one right-hand pass of the flat schedule."""
     _fields_ = [("L", ctypes.c_int), ("R", ctypes.c_int), ("generation", ctypes.c_int), ("batch", ctypes.c_int),
@@ -80,7 +91,9 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_last_stats", "fv_strerror", "fv_last_error_detail", "fv_reference_memory_bytes",
            "fv_comm_unique_id", "fv_comm_init", "fv_plan_passes", "fv_merge_paths", "fv_set_partition",
            "fv_create_multi", "fv_device_count", "fv_decode_full_batch", "fv_plan_passes_batch", "fv_decode_beam_batch",
-           "fv_set_model_sparse", "fv_set_emissions", "fv_clear_emissions", "fv_plan_flat", "fv_set_emission_map"]
+           "fv_set_model_sparse", "fv_set_emissions", "fv_clear_emissions", "fv_plan_flat", "fv_set_emission_map",
+           "fv_stream_open", "fv_stream_push", "fv_stream_push_emissions", "fv_stream_pending", "fv_stream_close",
+           "fv_stream_abort", "fv_stream_last_stats"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select", "fv_test_device_alloc", "fv_test_device_free",
                 "fv_test_stage_emissions_ms", "fv_test_flat_poison", "fv_test_beam_forward"]
@@ -150,6 +163,14 @@ def load_library():
     L.fv_set_emissions.argtypes = [vp, vp, ci, ci, cll]
     L.fv_clear_emissions.argtypes = [vp]
     L.fv_set_emission_map.argtypes = [vp, vp, ci]
+    L.fv_stream_open.argtypes = [vp, cll, ci]
+    L.fv_stream_push.argtypes = [vp, vp, ci, vp, ctypes.POINTER(cll)]
+    L.fv_stream_push_emissions.argtypes = [vp, vp, ci, ci, cll, vp, ctypes.POINTER(cll)]
+    L.fv_stream_pending.argtypes = [vp]
+    L.fv_stream_pending.restype = cll
+    L.fv_stream_close.argtypes = [vp, vp, ctypes.POINTER(cll), ctypes.POINTER(ctypes.c_float)]
+    L.fv_stream_abort.argtypes = [vp]
+    L.fv_stream_last_stats.argtypes = [vp, ctypes.POINTER(StreamStats)]
     L.fv_test_device_alloc.argtypes = [vp, ctypes.c_size_t, vp, ctypes.POINTER(vp)]
     L.fv_test_device_free.argtypes = [vp, vp]
     L.fv_test_stage_emissions_ms.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
@@ -289,6 +310,37 @@ def _batch_arg(obs, lengths):
     return ob, ptr, offsets
 
 
+def _emission_arg(scores, ld, who):
+    """(keep-alive object, pointer, EMIS_LOG_* code, rows, pitch) of a block of emission scores in the three forms
+    set_emissions and stream_push document: a numpy array, a torch tensor, (device_pointer, dtype, T, ld)."""
+    if isinstance(scores, tuple):
+        ptr, dtype, T, pitch = scores
+        if ld is not None:
+            pitch = ld
+        if isinstance(dtype, (type, np.dtype, str)):
+            dtype = _EMIS_OF_NUMPY.get(np.dtype(dtype), -1)
+        return None, ctypes.c_void_p(int(ptr)), int(dtype), int(T), int(pitch)
+    if _is_torch_tensor(scores):
+        import torch
+        codes = {torch.float16: EMIS_LOG_F16, torch.bfloat16: EMIS_LOG_BF16, torch.float32: EMIS_LOG_F32, torch.float64: EMIS_LOG_F64}
+        if scores.dim() != 2 or scores.dtype not in codes or scores.stride(1) != 1 or scores.shape[0] < 1 or scores.shape[1] < 1:
+            raise TypeError(who + ": a torch tensor must be 2-D, float16 / bfloat16 / float32 / float64, with stride(1) == 1")
+        pitch = scores.stride(0) if ld is None else int(ld)
+        if scores.shape[0] == 1:
+            pitch = max(pitch, scores.shape[1])         # (one row: its stride is arbitrary and never used)
+        if scores.is_cuda:
+            torch.cuda.current_stream(scores.device).synchronize()      # the C contract: the producer has finished
+        return scores, ctypes.c_void_p(scores.data_ptr()), codes[scores.dtype], scores.shape[0], pitch
+    a = np.asarray(scores)
+    if a.ndim != 2 or a.dtype not in _EMIS_OF_NUMPY:
+        raise TypeError(who + ": a 2-D float16, float32 or float64 array, a torch tensor, or (device_pointer, dtype, T, ld)")
+    a = np.ascontiguousarray(a)
+    pitch = a.shape[1] if ld is None else int(ld)
+    if pitch > a.shape[1] and a.shape[0] > 1:
+        raise ValueError(who + ": ld exceeds the row length of the array")
+    return a, _p(a), _EMIS_OF_NUMPY[a.dtype], a.shape[0], pitch
+
+
 def dense_to_csr(A):
     """(indptr int64[K + 1], indices int32[nnz], data float32[nnz]) of a dense K x K matrix, by row with ascending
     columns: what set_model_sparse takes.  Entries equal to 0 are left out (NaN is kept, so that the library sees it)."""
@@ -384,38 +436,59 @@ class FlashViterbi:
         a tuple (device_pointer:int, dtype, T, ld) for a block already on this context's GPU (dtype: np.float16 /
         np.float32 / np.float64 or an EMIS_LOG_* code; its producer must have finished).  Afterwards every decode_* and
         test_forward takes ob=None."""
-        if isinstance(scores, tuple):
-            ptr, dtype, T, pitch = scores
-            if ld is not None:
-                pitch = ld
-            if isinstance(dtype, (type, np.dtype, str)):
-                dtype = _EMIS_OF_NUMPY.get(np.dtype(dtype), -1)
-            self._check(self._L.fv_set_emissions(self._h, ctypes.c_void_p(int(ptr)), int(dtype), int(T), int(pitch)))
-            return
-        if _is_torch_tensor(scores):
-            import torch
-            codes = {torch.float16: EMIS_LOG_F16, torch.bfloat16: EMIS_LOG_BF16, torch.float32: EMIS_LOG_F32, torch.float64: EMIS_LOG_F64}
-            if scores.dim() != 2 or scores.dtype not in codes or scores.stride(1) != 1 or scores.shape[0] < 1 or scores.shape[1] < 1:
-                raise TypeError("set_emissions: a torch tensor must be 2-D, float16 / bfloat16 / float32 / float64, with stride(1) == 1")
-            pitch = scores.stride(0) if ld is None else int(ld)
-            if scores.shape[0] == 1:
-                pitch = max(pitch, scores.shape[1])         # (one row: its stride is arbitrary and never used)
-            if scores.is_cuda:
-                torch.cuda.current_stream(scores.device).synchronize()      # the C contract: the producer has finished
-            self._check(self._L.fv_set_emissions(self._h, ctypes.c_void_p(scores.data_ptr()), codes[scores.dtype],
-                                                 scores.shape[0], pitch))
-            return
-        a = np.asarray(scores)
-        if a.ndim != 2 or a.dtype not in _EMIS_OF_NUMPY:
-            raise TypeError("set_emissions: a 2-D float16, float32 or float64 array, a torch tensor, or (device_pointer, dtype, T, ld)")
-        a = np.ascontiguousarray(a)
-        pitch = a.shape[1] if ld is None else int(ld)
-        if pitch > a.shape[1] and a.shape[0] > 1:
-            raise ValueError("set_emissions: ld exceeds the row length of the array")
-        self._check(self._L.fv_set_emissions(self._h, _p(a), _EMIS_OF_NUMPY[a.dtype], a.shape[0], pitch))
+        keep, ptr, code, T, pitch = _emission_arg(scores, ld, "set_emissions")
+        self._check(self._L.fv_set_emissions(self._h, ptr, code, T, pitch))
 
     def clear_emissions(self):
         self._check(self._L.fv_clear_emissions(self._h))
+
+    # ---- fv_stream_*: the online decode.  One stream per context; while it is open the other calls raise ERR_STATE.
+
+    def stream_open(self, lag_rows_hint=0, check_every=0):
+        """fv_stream_open: lag_rows_hint arg rows at first (0: a default), a check every check_every steps (1..64, 0: the default)."""
+        self._check(self._L.fv_stream_open(self._h, int(lag_rows_hint), int(check_every)))
+
+    def stream_push(self, ob=None, scores=None, ld=None):
+        """fv_stream_push (ob: the symbols of the next times) or fv_stream_push_emissions (scores: their score rows, in
+        the forms set_emissions takes — a numpy array, a torch tensor on the CPU or on this context's GPU, or
+        (device_pointer, dtype, n, ld)).  Returns the piece of the path this push committed, int32, possibly empty.  A
+        refused push raises FlashVitError and consumes nothing; ERR_NO_PRED means the stream is dead."""
+        if (ob is None) == (scores is None):
+            raise ValueError("stream_push: either ob or scores")
+        done = ctypes.c_longlong(0)
+        room = max(int(self._L.fv_stream_pending(self._h)), 0)
+        if ob is not None:
+            ob = np.ascontiguousarray(ob, dtype=np.int32).reshape(-1)
+            piece = np.empty(room + max(ob.size, 1), dtype=np.int32)
+            self._check(self._L.fv_stream_push(self._h, _p(ob), ob.size, _p(piece), ctypes.byref(done)))
+        else:
+            keep, ptr, code, n, pitch = _emission_arg(scores, ld, "stream_push")
+            piece = np.empty(room + max(n, 1), dtype=np.int32)
+            self._check(self._L.fv_stream_push_emissions(self._h, ptr, code, n, pitch, _p(piece), ctypes.byref(done)))
+        return piece[:done.value].copy()
+
+    def stream_pending(self):
+        """fv_stream_pending: times consumed and not yet committed (< 0: no stream)."""
+        return int(self._L.fv_stream_pending(self._h))
+
+    def stream_close(self):
+        """fv_stream_close: (the last piece, the score, rc).  ERR_NO_PRED is returned, not raised, as decode_full_batch
+        reports it: the piece then holds what the library delivered (nothing for a dead stream)."""
+        piece = np.empty(max(int(self._L.fv_stream_pending(self._h)), 1), dtype=np.int32)
+        n = ctypes.c_longlong(0)
+        score = ctypes.c_float(0)
+        rc = self._L.fv_stream_close(self._h, _p(piece), ctypes.byref(n), ctypes.byref(score))
+        if rc != ERR_NO_PRED:
+            self._check(rc)
+        return piece[:n.value].copy(), np.float32(score.value), rc
+
+    def stream_abort(self):
+        self._check(self._L.fv_stream_abort(self._h))
+
+    def stream_stats(self):
+        s = StreamStats()
+        self._check(self._L.fv_stream_last_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
 
     def decode_full(self, ob, n_split=1, mode=MODE_REFERENCE, T=None):
         """ob=None with T=...: decode the first T rows staged by set_emissions (so for every decode_* below)."""

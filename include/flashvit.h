@@ -369,6 +369,72 @@ int fv_decode_vanilla(fv_ctx *ctx, const int *ob, int T, int *path_out, float *s
 int fv_decode_checkpoint(fv_ctx *ctx, const int *ob, int T, int step, int *path_out, float *score_out);
 long long fv_checkpoint_memory_bytes(int K, int T, int step);
 
+/* Online full-state decode: one stream per context consumes a sequence in pushes of any length >= 1, given
+ * as symbols or as emission-score rows, and hands the decoded path back piece by piece, each piece as soon as no later
+ * input can change it.  The concatenation of all pieces (the pushes', then the close's), the final score and the final
+ * return code are bit for bit those of fv_decode_full(ctx, ob, T, 1, FV_MODE_SINGLE_PASS, ...) on the concatenated
+ * input whenever that call returns FV_OK — for every chunking, every check interval, every FV_OPT_KERNEL value the
+ * one-shot call admits for the model, dense-set and CSR-set models.  A piece, once returned, is final.  Device memory
+ * is O((largest push + lag) * K), lag = times consumed and not yet committed: never O(T * K).
+ *   The rule.  The device keeps the two score rows, the arg rows of the uncommitted times and one row anc[K]: the state
+ * at the anchor time a on the survivor path of every state of the current time (a = 0, anc[s] = s at first; after a
+ * step with arg row bp, anc'[s] = bp[s] >= 0 ? anc[bp[s]] : -1).  A check — every check_every steps counted from the
+ * check before, and after the last step of every push — looks at the set V of non-negative anc values.  One element v:
+ * every path that can still be decoded runs through (a, v), so the times up to a are committed by a back-track from
+ * (a, v), their arg rows are dropped, and the anchor moves to the current time.  V empty: no state has a predecessor
+ * (below).  Otherwise nothing happens.  The check runs on the device, between the steps of a push, without the host.
+ *   fv_stream_open: needs a model; the step kernel and its admission are fv_decode_full's for that model under the
+ * FV_OPT_KERNEL in force (FV_ERR_UNSUPPORTED with the same detail), fixed for the stream's life.  lag_rows_hint: arg
+ * rows to allocate at first (0: a default; the buffer doubles whenever a push needs more).  check_every: 1..64, 0: the
+ * default (16).  FV_ERR_STATE: no model, or a stream is already open.  FV_ERR_UNSUPPORTED: multi-device, partitioned
+ * and communicator contexts.  FV_ERR_ARG: lag_rows_hint < 0, check_every outside 0..64.
+ *   fv_stream_push: n >= 1 times given as symbols of [0, M).  fv_stream_push_emissions: n >= 1 times given as score
+ * rows — dtype, ld, host or device pointer, emission map (rows of P classes while one is set) and value rules exactly
+ * as fv_set_emissions; the context's staged emissions are left alone.  The first push fixes which of the two the stream
+ * takes; the other kind afterwards is FV_ERR_ARG.  path_out must hold fv_stream_pending(ctx) + n entries;
+ * *committed_out of them are written: the next piece of the path, possibly none.
+ *   A refused push consumes nothing, runs no step and leaves the stream as it was: FV_ERR_ARG for a bad pointer, n < 1,
+ * a symbol outside [0, M), ld or dtype as fv_set_emissions refuses them, a NaN / +inf / out-of-range score (the detail
+ * names its time, counted from the stream's start, and state); FV_ERR_UNSUPPORTED for a score above 0 when the stream's
+ * kernel is a filter kernel (select FV_KERNEL_F64_STREAM, or FV_KERNEL_CSR_F64 on a CSR-set model, before the open);
+ * FV_ERR_NOMEM, with the byte count, when the arg rows cannot grow.  FV_ERR_STATE without a stream.
+ *   V empty at a check: the push returns FV_ERR_NO_PRED, as the one-shot decode of any sequence with this prefix
+ * does.  The pieces already returned stand; the stream then accepts only fv_stream_close, which returns FV_ERR_NO_PRED
+ * and delivers nothing, and fv_stream_abort; a push answers FV_ERR_STATE.
+ *   fv_stream_pending: times consumed and not yet committed; < 0 without a stream.
+ *   fv_stream_close: the end of the input — the end pick (lowest index among the maxima of the current score row), the
+ * back-track of everything pending into path_out (fv_stream_pending entries, *n_out their number), *score_out as
+ * fv_decode_full's (score_out may be NULL).  A stream that consumed one time delivers that time's end pick on the
+ * init row; one that consumed nothing delivers nothing.  Frees the stream's buffers, whatever it returns.
+ *   fv_stream_abort: drops the stream and delivers nothing.  fv_destroy frees an open stream.
+ *   While a stream is open the decode calls, fv_set_model, fv_set_model_sparse, fv_set_option, fv_set_emissions,
+ * fv_clear_emissions, fv_set_emission_map, fv_set_partition, fv_comm_init and the test hooks (all but
+ * fv_test_device_alloc / fv_test_device_free, which a push from a device block needs) answer FV_ERR_STATE.
+ * fv_last_stats keeps reporting the last decode; the stream has its own statistics. */
+int fv_stream_open(fv_ctx *ctx, long long lag_rows_hint, int check_every);
+int fv_stream_push(fv_ctx *ctx, const int *ob, int n, int *path_out, long long *committed_out);
+int fv_stream_push_emissions(fv_ctx *ctx, const void *scores, int dtype, int n, long long ld,
+                             int *path_out, long long *committed_out);
+long long fv_stream_pending(const fv_ctx *ctx);
+int fv_stream_close(fv_ctx *ctx, int *path_out, long long *n_out, float *score_out);
+int fv_stream_abort(fv_ctx *ctx);
+
+/* Statistics of the open stream, or of the last one closed or aborted (FV_ERR_STATE: there never was one). */
+typedef struct {
+    long long times;             /* times consumed */
+    long long committed;         /* times whose path entry has been returned */
+    long long pushes;            /* accepted pushes */
+    long long checks;            /* checks run (a check is two small launches: the ancestor walk and its verdict) */
+    long long commits;           /* checks that found one ancestor and moved the anchor */
+    long long lag_max;           /* largest number of pending times at the end of a push */
+    long long arg_rows_capacity; /* arg rows allocated */
+    long long regrows;           /* times the arg rows were reallocated at twice the need */
+    long long bt_restarts;       /* as fv_stats.bt_restarts, summed over the stream's back-tracks */
+    double push_ms_total;        /* host wall time of the accepted pushes, their synchronisations included */
+    int kernel;                  /* FV_KERNEL_* the steps run on */
+} fv_stream_stats;
+int fv_stream_last_stats(const fv_ctx *ctx, fv_stream_stats *out);
+
 int fv_last_stats(const fv_ctx *ctx, fv_stats *out);
 const char *fv_strerror(int rc);
 const char *fv_last_error_detail(const fv_ctx *ctx);
