@@ -1849,17 +1849,17 @@ __global__ __launch_bounds__(CSR_FINISH_BLOCK) void beam_finish_csr(const BeamCs
 static inline int allow_big_lds(std::string &detail)
 {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_step<16>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, fvk::LDS_LIMIT);
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_step<4>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                hipFuncAttributeMaxDynamicSharedMemorySize, fvk::LDS_LIMIT);
 
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_step_q16<16>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                hipFuncAttributeMaxDynamicSharedMemorySize, fvk::LDS_LIMIT);
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(&beam_step_q16<8>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                hipFuncAttributeMaxDynamicSharedMemorySize, fvk::LDS_LIMIT);
 
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(&heap_build_all),

@@ -397,8 +397,8 @@ int build_host_tables(const float *A, const float *B, const float *Pi, int K, in
     const int ntiles = h.ntiles = (K + fvk::TILE_W - 1) / fvk::TILE_W;
     // the full-state step kernels keep one score row in LDS: beyond that K only the beam path is available
     // (it needs the float64 table alone, which also keeps the host footprint at 8 B per entry)
-    const bool full_ok = h.full_ok = fvk::step_lds_bytes<1>(nrows) <= 160 * 1024;
-    h.u16_ok = fvk::u16_lds_bytes<1, 8>(nrows) <= 160 * 1024 && K <= 65536;
+    const bool full_ok = h.full_ok = fvk::step_lds_bytes<1>(nrows) <= (size_t)fvk::LDS_LIMIT;
+    h.u16_ok = fvk::u16_lds_bytes<1, 8>(nrows) <= (size_t)fvk::LDS_LIMIT && K <= 65536;
 
     const size_t tab = h.tab = (size_t)ntiles * nrows * fvk::TILE_W;
     std::vector<double> &h64 = h.h64;

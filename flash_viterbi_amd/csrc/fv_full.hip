@@ -62,11 +62,50 @@ static_assert(step_variant<double, 8, true>() == FV_TV_F64_NB8 && step_variant<f
               csr_f64_variant<1, false>() == FV_TV_CSR64_NB1 && csr_f64_variant<8, true>() == (FV_TV_CSR64_NB8 | FV_TV_CSR64_MEM),
               "FV_TV_* bits of include/flashvit_testing.h");
 
+// One step launch as its caller describes it.  Everything else a launch reads is the context's model and options, which
+// hold for the whole decode.
+struct StepLaunch {
+    int kernel;             // the FV_KERNEL_* the decode runs on (admit_full)
+    hipStream_t stream;     // the queue the launch goes to
+    bool forked;            // one of a generation's launches dealt to several streams: co-resident workgroups wanted (the
+                            // packed 16-bit kernel in its double-buffered form, and for the batched launches as well)
+    int reverse;            // sweep direction (StepArgs::reverse): alternates from step to step
+};
+// FV_OPT_ROW_CODES: what launch_step_kernel found for a launch's rows — StepArgs::codes and one CodeSlot per task
+struct LaunchCodes { int codes; const fvk::CodeSlot *slots; };
+
+// The task counts the step kernels are instantiated for.  with_nb calls f(std::integral_constant<int, NB>) for the
+// smallest of them that holds nb tasks: the one place a run-time task count becomes a template argument.
+template <int... NB> struct NbList {};
+constexpr NbList<1, 2, 4, 8> STEP_NB{};
+template <typename F, int... NB>
+int with_nb(NbList<NB...>, int nb, F &&f)
+{
+    constexpr int all[] = { NB... }, last = all[sizeof...(NB) - 1];
+    static_assert(last == fvk::MAX_BATCH, "the largest instantiation holds MAX_BATCH tasks");
+    int rc = 0;
+    (void)((nb <= NB || NB == last ? (rc = f(std::integral_constant<int, NB>{}), true) : false) || ...);
+    return rc;
+}
+
+// what every argument struct has: the model's geometry and the task slots, the unused ones padded with slot 0
+template <typename Args>
+void fill_common(const fv_ctx *ctx, const fvk::TaskSlot *slots, int nb, Args &a)
+{
+    a.K = ctx->K;
+    a.nrows = ctx->nrows;
+    a.ntiles = (ctx->K + fvk::TILE_W - 1) / fvk::TILE_W;
+    a.tiles_per_xcd = (a.ntiles + 7) / 8;
+    a.nb = nb;
+    constexpr int NB = (int)(sizeof(a.t) / sizeof(a.t[0]));
+    for (int t = 0; t < NB; ++t) a.t[t] = slots[t < nb ? t : 0];
+}
+
 template <typename TA, int NB, int U, bool DB>
-int launch_variant(fv_ctx *ctx, const fvk::StepArgs<NB> &a, size_t lds)
+int launch_variant(fv_ctx *ctx, const StepLaunch &ln, const fvk::StepArgs<NB> &a, size_t lds)
 {
     if (ctx->test_record) ctx->test_variants |= step_variant<TA, NB, DB>();
-    hipLaunchKernelGGL((fvk::trellis_step<TA, NB, U, DB>), dim3(a.tiles_per_xcd * 8), dim3(fvk::BLOCK), lds, ctx->lstream ? ctx->lstream : ctx->stream, a);
+    hipLaunchKernelGGL((fvk::trellis_step<TA, NB, U, DB>), dim3(a.tiles_per_xcd * 8), dim3(fvk::BLOCK), lds, ln.stream, a);
     FV_HIP(hipGetLastError());
     return 0;
 }
@@ -77,31 +116,35 @@ int slab_rows(const fv_ctx *ctx)
 {
     int slab = ctx->nrows;
     if (ctx->opt_debug & (1 << 21)) slab = std::max(64, (ctx->nrows / 3 + 63) / 64 * 64);
-    while (slab > 64 && fvk::step_lds_bytes<NB>(slab) > 160 * 1024) slab = (slab / 2 + 63) / 64 * 64;
+    while (slab > 64 && fvk::step_lds_bytes<NB>(slab) > (size_t)fvk::LDS_LIMIT) slab = (slab / 2 + 63) / 64 * 64;
     return slab;
 }
 
+// the fields of StepArgs both of its kernels read (trellis_step, trellis_step_u16); LA and window are the caller's
+template <int NB>
+void fill_step_args(const fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot *slots, int nb, fvk::StepArgs<NB> &a)
+{
+    fill_common(ctx, slots, nb, a);
+    a.qscale = ctx->qscale;
+    a.LA64 = ctx->LA64.p;
+    a.counters = ctx->d_counters.p;
+    a.reverse = (ctx->opt_debug & 2) ? 0 : ln.reverse;
+    a.debug = ctx->opt_debug;
+    a.row_lo = 0; a.srows = ctx->nrows; a.merge = 0;
+}
+
 template <typename TA, int NB>
-int launch_step_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb, int reverse)
+int launch_step_nb(fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot *slots, int nb)
 {
     fvk::StepArgs<NB> a;
+    fill_step_args(ctx, ln, slots, nb, a);
     if constexpr (std::is_same<TA, double>::value) { a.LA = ctx->LA64.p; a.window = 0.0f; }
     else if constexpr (std::is_same<TA, float>::value) { a.LA = ctx->LA32.p; a.window = 0.0f; }
     else if constexpr (std::is_same<TA, fvk::q16_t>::value) { a.LA = ctx->LAQ16.p; a.window = ctx->windowq; }
     else { a.LA = ctx->LA16.p; a.window = ctx->window16; }
-    a.qscale = ctx->qscale;
     a.vanilla = ctx->vanilla;
-    a.LA64 = ctx->LA64.p;
-    a.counters = ctx->d_counters.p;
-    a.K = ctx->K;
-    a.reverse = (ctx->opt_debug & 2) ? 0 : reverse;
-    a.debug = ctx->opt_debug;
-    a.nrows = ctx->nrows;
-    a.ntiles = (ctx->K + fvk::TILE_W - 1) / fvk::TILE_W;
-    a.tiles_per_xcd = (a.ntiles + 7) / 8;
-    a.nb = nb;
-    a.row_lo = 0; a.srows = ctx->nrows; a.merge = 0; a.codes = 0;
-    for (int t = 0; t < NB; ++t) { a.t[t] = slots[t < nb ? t : 0]; a.c[t] = fvk::CodeSlot{ nullptr, nullptr, nullptr, nullptr }; }
+    a.codes = 0;
+    for (int t = 0; t < NB; ++t) a.c[t] = fvk::CodeSlot{ nullptr, nullptr, nullptr, nullptr };
     const size_t lds = fvk::step_lds_bytes<NB>(ctx->nrows);
     constexpr int RBR = 4 * fvk::Tab<TA>::R;
     const int nj_max = (ctx->nrows / RBR + fvk::NWAVES - 1) / fvk::NWAVES;
@@ -115,18 +158,18 @@ int launch_step_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb, int reverse)
         if (ctx->test_record) ctx->test_variants |= slab_variant<TA>();
         for (int lo = 0; lo < ctx->nrows; lo += slab) {
             a.row_lo = lo; a.srows = std::min(slab, ctx->nrows - lo); a.merge = lo > 0 ? 1 : 0;
-            const int rc = launch_variant<TA, NB, U, true>(ctx, a, fvk::step_lds_bytes<NB>(a.srows));
+            const int rc = launch_variant<TA, NB, U, true>(ctx, ln, a, fvk::step_lds_bytes<NB>(a.srows));
             if (rc) return rc;
         }
         return 0;
     }
     if constexpr (std::is_same<TA, double>::value) {
-        return launch_variant<TA, NB, U_DB64, true>(ctx, a, lds);
+        return launch_variant<TA, NB, U_DB64, true>(ctx, ln, a, lds);
     } else if constexpr (std::is_same<TA, float>::value) {
         if constexpr (NB <= 2) {
-            if (nj_max <= U_UP && (ctx->opt_debug & 4)) return launch_variant<TA, NB, U_UP, false>(ctx, a, lds);
+            if (nj_max <= U_UP && (ctx->opt_debug & 4)) return launch_variant<TA, NB, U_UP, false>(ctx, ln, a, lds);
         }
-        return launch_variant<TA, NB, U_DB32, true>(ctx, a, lds);
+        return launch_variant<TA, NB, U_DB32, true>(ctx, ln, a, lds);
     } else {
         // 16-bit tables: an XCD's slab (3.9 MB at K=3965) nearly fits its L2, so requesting the whole
         // tile before staging the score row wins (9.5 vs 9.8 us/step); FV_OPT_DEBUG bit 2 turns it off.
@@ -134,179 +177,120 @@ int launch_step_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb, int reverse)
         // double-buffered one (46 VGPRs, two workgroups per CU) keeps the grid in one round
         // (K=5632: 18.3 vs 25.3 us/step, K=8192: 25.8 vs 39.8).
         if constexpr (NB <= 2) {
-            if (nj_max <= U_UP && a.ntiles <= ctx->num_cus && !(ctx->opt_debug & 4)) return launch_variant<TA, NB, U_UP, false>(ctx, a, lds);
+            if (nj_max <= U_UP && a.ntiles <= ctx->num_cus && !(ctx->opt_debug & 4)) return launch_variant<TA, NB, U_UP, false>(ctx, ln, a, lds);
         }
         // (8-wave workgroups for the batched launches, as the packed 16-bit kernel uses, were measured: 2.14 vs 2.10 ms of
         // right-hand passes at cfg2, 65.6 vs 62.7 ms at cfg3 — the f32 sweep needs its four waves per SIMD)
-        return launch_variant<TA, NB, U_DB16, true>(ctx, a, lds);
+        return launch_variant<TA, NB, U_DB16, true>(ctx, ln, a, lds);
     }
 }
 
 template <typename TA>
-int launch_step(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb, int reverse)
+int launch_step(fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot *slots, int nb)
 {
-    if (nb <= 1) return launch_step_nb<TA, 1>(ctx, slots, nb, reverse);
-    if (nb <= 2) return launch_step_nb<TA, 2>(ctx, slots, nb, reverse);
-    if (nb <= 4) return launch_step_nb<TA, 4>(ctx, slots, nb, reverse);
-    return launch_step_nb<TA, 8>(ctx, slots, nb, reverse);
+    return with_nb(STEP_NB, nb, [&](auto NB) { return launch_step_nb<TA, NB()>(ctx, ln, slots, nb); });
 }
 
 template <int NB>
-int launch_sparse_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb)
+int launch_sparse_nb(fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot *slots, int nb)
 {
     fvk::SparseArgs<NB> a;
+    fill_common(ctx, slots, nb, a);
     a.data = ctx->SPdata.p; a.tile_off = ctx->SPoff.p; a.tile_nwb = ctx->SPnwb.p;
     a.LA64 = ctx->LA64.p; a.counters = ctx->d_counters.p;
-    a.K = ctx->K; a.nrows = ctx->nrows;
-    a.ntiles = (ctx->K + fvk::TILE_W - 1) / fvk::TILE_W;
-    a.tiles_per_xcd = (a.ntiles + 7) / 8;
-    a.nb = nb; a.debug = ctx->opt_debug;
+    a.debug = ctx->opt_debug;
     a.window = ctx->windowq; a.qscale = ctx->qscale;
-    for (int t = 0; t < NB; ++t) a.t[t] = slots[t < nb ? t : 0];
     if (ctx->test_record) ctx->test_variants |= sparse_variant<NB>();
     hipLaunchKernelGGL((fvk::trellis_step_sparse<NB>), dim3(a.tiles_per_xcd * 8), dim3(fvk::SP_BLOCK),
-                       fvk::sparse_lds_bytes<NB>(ctx->nrows), ctx->lstream ? ctx->lstream : ctx->stream, a);
+                       fvk::sparse_lds_bytes<NB>(ctx->nrows), ln.stream, a);
     FV_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_sparse(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb)
+// The two walks over a CSR-set model keep their score rows in LDS while NB of them fit (lds_form_bytes), else — or under
+// FV_OPT_DEBUG bit 31 — read them from memory: go(std::true_type) launches the memory form, go(std::false_type) the LDS form.
+template <typename Go>
+void launch_csr_form(const fv_ctx *ctx, size_t lds_form_bytes, Go &&go)
 {
-    if (nb <= 1) return launch_sparse_nb<1>(ctx, slots, nb);
-    if (nb <= 2) return launch_sparse_nb<2>(ctx, slots, nb);
-    if (nb <= 4) return launch_sparse_nb<4>(ctx, slots, nb);
-    return launch_sparse_nb<8>(ctx, slots, nb);
+    if (ctx->opt_csr_mem || lds_form_bytes > (size_t)fvk::LDS_LIMIT) go(std::true_type{});
+    else go(std::false_type{});
 }
 
-// trellis_step_csr: score rows in LDS while NB of them fit, else (or under FV_OPT_DEBUG bit 31) read from memory
+// trellis_step_csr (FV_KERNEL_SPARSE_CSR): the filter walk
 template <int NB>
-bool csr_rows_in_memory(const fv_ctx *ctx)
-{
-    return ctx->opt_csr_mem || fvk::csr_lds_bytes<NB>(ctx->nrows, false) > 160 * 1024;
-}
-
-template <int NB>
-int launch_csr_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb)
+int launch_csr_nb(fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot *slots, int nb)
 {
     fvk::CsrArgs<NB> a;
+    fill_common(ctx, slots, nb, a);
     a.ck = ctx->CSk.p; a.cq = ctx->CSq.p; a.c64 = ctx->CS64.p; a.tile_off = ctx->CSoff.p; a.tile_nwb = ctx->CSnwb.p;
     a.counters = ctx->d_counters.p;
-    a.K = ctx->K; a.nrows = ctx->nrows;
-    a.ntiles = (ctx->K + fvk::TILE_W - 1) / fvk::TILE_W;
-    a.tiles_per_xcd = (a.ntiles + 7) / 8;
-    a.nb = nb; a.debug = ctx->opt_debug;
+    a.debug = ctx->opt_debug;
     a.window = ctx->windowq; a.qscale = ctx->qscale;
-    for (int t = 0; t < NB; ++t) a.t[t] = slots[t < nb ? t : 0];
-    hipStream_t st = ctx->lstream ? ctx->lstream : ctx->stream;
-    if (csr_rows_in_memory<NB>(ctx)) {
-        if (ctx->test_record) ctx->test_variants |= csr_variant<NB, true>();
-        hipLaunchKernelGGL((fvk::trellis_step_csr<NB, true>), dim3(a.tiles_per_xcd * 8), dim3(fvk::SP_BLOCK),
-                           fvk::csr_lds_bytes<NB>(ctx->nrows, true), st, a);
-    } else {
-        if (ctx->test_record) ctx->test_variants |= csr_variant<NB, false>();
-        hipLaunchKernelGGL((fvk::trellis_step_csr<NB, false>), dim3(a.tiles_per_xcd * 8), dim3(fvk::SP_BLOCK),
-                           fvk::csr_lds_bytes<NB>(ctx->nrows, false), st, a);
-    }
+    launch_csr_form(ctx, fvk::csr_lds_bytes<NB>(ctx->nrows, false), [&](auto MEM) {
+        if (ctx->test_record) ctx->test_variants |= csr_variant<NB, MEM()>();
+        hipLaunchKernelGGL((fvk::trellis_step_csr<NB, MEM()>), dim3(a.tiles_per_xcd * 8), dim3(fvk::SP_BLOCK),
+                           fvk::csr_lds_bytes<NB>(ctx->nrows, MEM()), ln.stream, a);
+    });
     FV_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_csr(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb)
-{
-    if (nb <= 1) return launch_csr_nb<1>(ctx, slots, nb);
-    if (nb <= 2) return launch_csr_nb<2>(ctx, slots, nb);
-    if (nb <= 4) return launch_csr_nb<4>(ctx, slots, nb);
-    return launch_csr_nb<8>(ctx, slots, nb);
-}
-
-// trellis_step_csr_f64 (FV_KERNEL_CSR_F64): the same two forms of the score rows
+// trellis_step_csr_f64 (FV_KERNEL_CSR_F64): the float64 walk
 template <int NB>
-int launch_csr_f64_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb)
+int launch_csr_f64_nb(fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot *slots, int nb)
 {
     fvk::CsrF64Args<NB> a;
+    fill_common(ctx, slots, nb, a);
     a.ck = ctx->CSk.p; a.c64 = ctx->CS64.p; a.tile_off = ctx->CSoff.p; a.tile_nwb = ctx->CSnwb.p;
-    a.K = ctx->K; a.nrows = ctx->nrows;
-    a.ntiles = (ctx->K + fvk::TILE_W - 1) / fvk::TILE_W;
-    a.tiles_per_xcd = (a.ntiles + 7) / 8;
-    a.nb = nb; a.vanilla = ctx->vanilla;
-    for (int t = 0; t < NB; ++t) a.t[t] = slots[t < nb ? t : 0];
-    hipStream_t st = ctx->lstream ? ctx->lstream : ctx->stream;
-    if (ctx->opt_csr_mem || fvk::csr_f64_lds_bytes<NB>(ctx->nrows, false) > 160 * 1024) {
-        if (ctx->test_record) ctx->test_variants |= csr_f64_variant<NB, true>();
-        hipLaunchKernelGGL((fvk::trellis_step_csr_f64<NB, true>), dim3(a.tiles_per_xcd * 8), dim3(fvk::SP_BLOCK),
-                           fvk::csr_f64_lds_bytes<NB>(ctx->nrows, true), st, a);
-    } else {
-        if (ctx->test_record) ctx->test_variants |= csr_f64_variant<NB, false>();
-        hipLaunchKernelGGL((fvk::trellis_step_csr_f64<NB, false>), dim3(a.tiles_per_xcd * 8), dim3(fvk::SP_BLOCK),
-                           fvk::csr_f64_lds_bytes<NB>(ctx->nrows, false), st, a);
-    }
+    a.vanilla = ctx->vanilla;
+    launch_csr_form(ctx, fvk::csr_f64_lds_bytes<NB>(ctx->nrows, false), [&](auto MEM) {
+        if (ctx->test_record) ctx->test_variants |= csr_f64_variant<NB, MEM()>();
+        hipLaunchKernelGGL((fvk::trellis_step_csr_f64<NB, MEM()>), dim3(a.tiles_per_xcd * 8), dim3(fvk::SP_BLOCK),
+                           fvk::csr_f64_lds_bytes<NB>(ctx->nrows, MEM()), ln.stream, a);
+    });
     FV_HIP(hipGetLastError());
     return 0;
-}
-
-int launch_csr_f64(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb)
-{
-    if (nb <= 1) return launch_csr_f64_nb<1>(ctx, slots, nb);
-    if (nb <= 2) return launch_csr_f64_nb<2>(ctx, slots, nb);
-    if (nb <= 4) return launch_csr_f64_nb<4>(ctx, slots, nb);
-    return launch_csr_f64_nb<8>(ctx, slots, nb);
 }
 
 // which task counts of trellis_step_u16 have a second instantiation without the FV_OPT_ROW_CODES code (CODES = false)
 template <int NB> constexpr bool U16_CODE_FREE = NB == 1;
 
 template <int NB, int U, bool DB, int NWV>
-int launch_u16_variant(fv_ctx *ctx, const fvk::StepArgs<NB> &a)
+int launch_u16_variant(fv_ctx *ctx, const StepLaunch &ln, const fvk::StepArgs<NB> &a)
 {
     const size_t lds = fvk::u16_lds_bytes<NB, NWV>(ctx->nrows);
     fvk::StepArgs<NB> b = a;
     if (!fvk::u16_takes_codes<NB, DB, NWV>()) b.codes &= ~1;
     if (ctx->test_record) ctx->test_variants |= u16_variant<NB, DB, NWV>() | ((b.codes & 1) ? FV_TV_ROW_CODES : 0ull);
-    hipStream_t st = ctx->lstream ? ctx->lstream : ctx->stream;
     // a single-task launch that neither reads nor writes codes (under auto: every one) runs the form without the route's code;
     // the batched forms have no such twin (U16_CODE_FREE: there the last argument is `true` again, the same instantiation)
-    if (U16_CODE_FREE<NB> && ctx->launch_codes == 0)
-        hipLaunchKernelGGL((fvk::trellis_step_u16<NB, U, DB, NWV, !U16_CODE_FREE<NB>>), dim3(a.tiles_per_xcd * 8), dim3(NWV * 64), lds, st, b);
+    if (U16_CODE_FREE<NB> && a.codes == 0)
+        hipLaunchKernelGGL((fvk::trellis_step_u16<NB, U, DB, NWV, !U16_CODE_FREE<NB>>), dim3(a.tiles_per_xcd * 8), dim3(NWV * 64), lds, ln.stream, b);
     else
-        hipLaunchKernelGGL((fvk::trellis_step_u16<NB, U, DB, NWV>), dim3(a.tiles_per_xcd * 8), dim3(NWV * 64), lds, st, b);
+        hipLaunchKernelGGL((fvk::trellis_step_u16<NB, U, DB, NWV>), dim3(a.tiles_per_xcd * 8), dim3(NWV * 64), lds, ln.stream, b);
     FV_HIP(hipGetLastError());
     return 0;
 }
 
 template <int NB>
-int launch_u16_nb(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb, int reverse)
+int launch_u16_nb(fv_ctx *ctx, const StepLaunch &ln, const LaunchCodes &lc, const fvk::TaskSlot *slots, int nb)
 {
     fvk::StepArgs<NB> a;
-    a.LA = ctx->LAQ16.p; a.window = ctx->windowq; a.qscale = ctx->qscale; a.vanilla = 0;
-    a.LA64 = ctx->LA64.p; a.counters = ctx->d_counters.p;
-    a.K = ctx->K; a.reverse = (ctx->opt_debug & 2) ? 0 : reverse; a.debug = ctx->opt_debug;
-    a.nrows = ctx->nrows;
-    a.ntiles = (ctx->K + fvk::TILE_W - 1) / fvk::TILE_W;
-    a.tiles_per_xcd = (a.ntiles + 7) / 8;
-    a.nb = nb;
-    a.row_lo = 0; a.srows = ctx->nrows; a.merge = 0;
-    a.codes = ctx->launch_codes;          // FV_OPT_ROW_CODES: what launch_step_kernel found for this launch's rows
-    const fvk::CodeSlot *cs = static_cast<const fvk::CodeSlot *>(ctx->launch_code_slots);
-    for (int t = 0; t < NB; ++t) { a.t[t] = slots[t < nb ? t : 0]; a.c[t] = cs[t < nb ? t : 0]; }
+    fill_step_args(ctx, ln, slots, nb, a);
+    a.LA = ctx->LAQ16.p; a.window = ctx->windowq; a.vanilla = 0;
+    a.codes = lc.codes;
+    for (int t = 0; t < NB; ++t) a.c[t] = lc.slots[t < nb ? t : 0];
     const int nq = ctx->nrows / 32;
     // 8 waves per workgroup (FV_OPT_DEBUG bit 13: 16): everything outside the sweep — quantisation, reductions, refine —
     // is executed by every wave, so fewer, longer waves spend fewer issue slots on it
     if (ctx->opt_debug & 8192) {
-        if (a.ntiles <= ctx->num_cus && (nq + 15) / 16 <= 8 && !(ctx->opt_debug & 4)) return launch_u16_variant<NB, 8, false, 16>(ctx, a);
-        return launch_u16_variant<NB, U_DB16, true, 16>(ctx, a);
+        if (a.ntiles <= ctx->num_cus && (nq + 15) / 16 <= 8 && !(ctx->opt_debug & 4)) return launch_u16_variant<NB, 8, false, 16>(ctx, ln, a);
+        return launch_u16_variant<NB, U_DB16, true, 16>(ctx, ln, a);
     }
     // (forked batches: the double-buffered form, 81 VGPRs at NB = 4 — three 8-wave workgroups of three streams share a CU;
     // the whole-tile form's 137 would leave room for one)
-    if (a.ntiles <= ctx->num_cus && (nq + 7) / 8 <= 16 && !(ctx->opt_debug & 4) && !ctx->forked_batches) return launch_u16_variant<NB, 16, false, 8>(ctx, a);
-    return launch_u16_variant<NB, U_DB16, true, 8>(ctx, a);
-}
-
-int launch_u16(fv_ctx *ctx, const fvk::TaskSlot *slots, int nb, int reverse)
-{
-    if (nb <= 1) return launch_u16_nb<1>(ctx, slots, nb, reverse);
-    if (nb <= 2) return launch_u16_nb<2>(ctx, slots, nb, reverse);
-    if (nb <= 4) return launch_u16_nb<4>(ctx, slots, nb, reverse);
-    return launch_u16_nb<8>(ctx, slots, nb, reverse);
+    if (a.ntiles <= ctx->num_cus && (nq + 7) / 8 <= 16 && !(ctx->opt_debug & 4) && !ln.forked) return launch_u16_variant<NB, 16, false, 8>(ctx, ln, a);
+    return launch_u16_variant<NB, U_DB16, true, 8>(ctx, ln, a);
 }
 
 // FV_OPT_ROW_CODES — the packed 16-bit kernel leaves, beside every score row it writes, the row's 16-bit codes and tile
@@ -359,10 +343,16 @@ bool init_rows_coded(fv_ctx *ctx, int base, int n)
     return true;
 }
 
-int launch_step_kernel(fv_ctx *ctx, int kernel, const fvk::TaskSlot *slots, int nb, int reverse)
+// One step launch of `nb` tasks, as `ln` describes it.  (Bare: a decode's launches go through queue_step, which counts them.)
+int launch_step_kernel(fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot *slots, int nb)
 {
     fvk::CodeSlot cs[fvk::MAX_BATCH];
-    const bool packed = kernel == FV_KERNEL_U16_REFINE && (nb <= 1 || !ctx->full_ok || (ctx->opt_debug & 16384) || ctx->forked_batches);
+    // Both filters of FV_KERNEL_U16_REFINE read the same 16-bit table and give the same bits, so the choice is per launch: the
+    // packed 16-bit filter for single-task launches (the whole-sequence pass: 9.1 vs 9.3 us per step at K=3965/T=256,
+    // 10.4 vs 14.2 at T=4096 where its window is the narrower one), for models whose float32 rows do not fit LDS and for
+    // forked batches; the f32 filter for the other batched launches, where the 16-bit kernel's per-task prologue (row
+    // maximum, quantisation) costs what its cheaper sweep saves.  FV_OPT_DEBUG bit 14: packed 16-bit for every launch.
+    const bool packed = ln.kernel == FV_KERNEL_U16_REFINE && (nb <= 1 || !ctx->full_ok || (ctx->opt_debug & 16384) || ln.forked);
     bool all_in = packed && ctx->row_codes != 0, all_out = all_in;
     int rout[fvk::MAX_BATCH];
     for (int q = 0; q < nb; ++q) {
@@ -380,33 +370,37 @@ int launch_step_kernel(fv_ctx *ctx, int kernel, const fvk::TaskSlot *slots, int 
     // those take the route; a batched launch writes them for whichever family reads its rows next
     const int family = nb <= 1 ? 1 : 2;
     const bool produce = all_out && (nb > 1 || (ctx->row_codes & 1));
-    ctx->launch_codes = ((all_in && (ctx->row_codes & family)) ? 1 : 0) | (produce ? 2 : 0);
-    ctx->launch_code_slots = cs;
+    const LaunchCodes lc{ ((all_in && (ctx->row_codes & family)) ? 1 : 0) | (produce ? 2 : 0), cs };
     for (int q = 0; q < nb; ++q)
         if (rout[q] >= 0) ctx->row_coded[(size_t)rout[q]] = produce ? 1 : 0;
-    switch (kernel) {
+    switch (ln.kernel) {
     case FV_KERNEL_U16_REFINE:
-        // Both filters read the same 16-bit table and give the same bits, so the choice is per launch: the packed
-        // 16-bit filter for single-task launches (the whole-sequence pass: 9.1 vs 9.3 us per step at K=3965/T=256,
-        // 10.4 vs 14.2 at T=4096 where its window is the narrower one) and for models whose float32 rows do not fit
-        // LDS; the f32 filter for batched launches, where the 16-bit kernel's per-task prologue (row maximum,
-        // quantisation) costs what its cheaper sweep saves.  FV_OPT_DEBUG bit 14: packed 16-bit for every launch.
-        if (nb <= 1 || !ctx->full_ok || (ctx->opt_debug & 16384) || ctx->forked_batches) return launch_u16(ctx, slots, nb, reverse);
-        return launch_step<fvk::q16_t>(ctx, slots, nb, reverse);
-    case FV_KERNEL_SPARSE_Q16: return launch_sparse(ctx, slots, nb);
-    case FV_KERNEL_SPARSE_CSR: return launch_csr(ctx, slots, nb);
-    case FV_KERNEL_CSR_F64: return launch_csr_f64(ctx, slots, nb);
-    case FV_KERNEL_F64_STREAM: return launch_step<double>(ctx, slots, nb, reverse);
-    case FV_KERNEL_F32_REFINE: return launch_step<float>(ctx, slots, nb, reverse);
-    case FV_KERNEL_Q16_REFINE: return launch_step<fvk::q16_t>(ctx, slots, nb, reverse);
-    default: return launch_step<fvk::half_t>(ctx, slots, nb, reverse);
+        if (packed) return with_nb(STEP_NB, nb, [&](auto NB) { return launch_u16_nb<NB()>(ctx, ln, lc, slots, nb); });
+        return launch_step<fvk::q16_t>(ctx, ln, slots, nb);
+    case FV_KERNEL_SPARSE_Q16: return with_nb(STEP_NB, nb, [&](auto NB) { return launch_sparse_nb<NB()>(ctx, ln, slots, nb); });
+    case FV_KERNEL_SPARSE_CSR: return with_nb(STEP_NB, nb, [&](auto NB) { return launch_csr_nb<NB()>(ctx, ln, slots, nb); });
+    case FV_KERNEL_CSR_F64: return with_nb(STEP_NB, nb, [&](auto NB) { return launch_csr_f64_nb<NB()>(ctx, ln, slots, nb); });
+    case FV_KERNEL_F64_STREAM: return launch_step<double>(ctx, ln, slots, nb);
+    case FV_KERNEL_F32_REFINE: return launch_step<float>(ctx, ln, slots, nb);
+    case FV_KERNEL_Q16_REFINE: return launch_step<fvk::q16_t>(ctx, ln, slots, nb);
+    default: return launch_step<fvk::half_t>(ctx, ln, slots, nb);
     }
+}
+
+// a decode's step launch: queued and counted (fv_last_stats).  A stream's steps are not a decode's: fvi::stream_step
+// calls launch_step_kernel itself.
+int queue_step(fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot *slots, int nb)
+{
+    if (int rc = launch_step_kernel(ctx, ln, slots, nb)) return rc;
+    ctx->stats.step_launches += 1;
+    ctx->stats.task_steps += nb;
+    return 0;
 }
 
 template <typename K>
 int set_big_lds(fv_ctx *ctx, K kernel)
 {
-    FV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    FV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, fvk::LDS_LIMIT));
     return 0;
 }
 
@@ -425,25 +419,163 @@ int allow_big_lds(fv_ctx *ctx)
 }
 
 // largest batch whose score rows fit LDS next to the reduction scratch
+// (u16_only: models beyond the float32 kernels' limit — rows of 16-bit codes)
 int max_batch_for(int nrows, bool u16_only)
 {
-    if (u16_only) {             // models beyond the float32 kernels' limit: rows of 16-bit codes
-        if (fvk::u16_lds_bytes<8, 8>(nrows) <= 160 * 1024) return 8;
-        if (fvk::u16_lds_bytes<4, 8>(nrows) <= 160 * 1024) return 4;
-        if (fvk::u16_lds_bytes<2, 8>(nrows) <= 160 * 1024) return 2;
-        return 1;
-    }
     int nb = fvk::MAX_BATCH;
-    while (nb > 1) {
-        size_t need = nb == 8 ? fvk::step_lds_bytes<8>(nrows) : nb == 4 ? fvk::step_lds_bytes<4>(nrows)
-                                                                        : fvk::step_lds_bytes<2>(nrows);
-        if (need <= 160 * 1024) break;
-        nb >>= 1;
+    for (; nb > 1; nb >>= 1) {
+        const int fits = with_nb(STEP_NB, nb, [&](auto NB) {
+            return (u16_only ? fvk::u16_lds_bytes<NB(), 8>(nrows) : fvk::step_lds_bytes<NB()>(nrows)) <= (size_t)fvk::LDS_LIMIT ? 1 : 0;
+        });
+        if (fits) break;
     }
     return nb;
 }
 
-struct ProfRange { size_t first, count; };
+// The generation policy: how many tasks a step launch of a generation takes (cap) and how many streams its batches are
+// dealt to (nstreams; 1: not forked) — for the generation driver, the flat form's admission and the checkpoint decode.
+//
+// The batches of a lock-step are independent, and a step launch is latency-bound at both ends (staging the score
+// rows; reductions and refine): the right-hand generations of the packed 16-bit kernel therefore run as batches of
+// FORK_CAP tasks dealt to FORK_STREAMS streams, small enough (36 KB of LDS, 81 VGPRs, 8 waves) for three workgroups
+// of different launches to share a CU — one launch's head and tail run under the sweeps of the others.  cfg2
+// right-hand passes 2.10 -> 1.85 ms, cfg3 62.7 -> 44.7 ms; the f32 filter in two co-resident 8-wave workgroups gave
+// 1.96 / 53.0, batches of two tasks and four streams were slower, batches of three tasks too (2.16 / 54.9 ms).  The
+// sparse walk gains the same way (cfg3 right-hand 33.4 -> 23.1 ms; at cfg2's 31-step passes nothing, so short
+// generations stay on one stream and the host keeps running ahead).  FV_OPT_DEBUG bit 18: off.
+// (Round 3, measured and not kept: the co-resident batches in ONE launch, gridDim.y = three batches of four, instead
+// of three launches on three streams — no fork / join, a third of the host launches — cfg2 right-hand 1.64 -> 1.79 ms,
+// cfg3 43.8 -> 51.1 ms: workgroups of one launch run in phase, all in their prologue or all in their sweep; what the
+// streams provide is the stagger.)
+constexpr int FORK_STREAMS = 3, FORK_CAP = 4;
+struct GenShape { int cap, nstreams; };
+// maxlen: steps of the longest pass; nfork: the passes that would be dealt (a generation's passes; the flat form's passes
+// of more than one step); may_fork: nothing about the caller forbids a fork.
+// all_streams — the one point where the callers differ: a generation of 5 to 8 passes makes two batches of FORK_CAP, and the
+// generation driver (false) opens a stream per batch, two; the flat form (true) takes FORK_STREAMS whenever it forks,
+// which its plan (build_flat) and the plan's key are made for.  Whether two would serve it as well has not been measured.
+GenShape generation_shape(const fv_ctx *ctx, int kernel, int maxlen, int nfork, bool may_fork, bool all_streams)
+{
+    // (the float64 kernel beyond one LDS row sweeps slabs of source rows: four tasks per launch keep a slab at ~10000 rows)
+    const bool slabbed = (kernel == FV_KERNEL_F64_STREAM || kernel == FV_KERNEL_Q16_REFINE) && !ctx->full_ok;
+    const bool walk = kernel == FV_KERNEL_SPARSE_Q16 || kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64;
+    GenShape g{ std::max(1, std::min(ctx->opt_max_batch, slabbed ? 4 : max_batch_for(ctx->nrows, !ctx->full_ok))), 1 };
+    if (kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64) g.cap = ctx->opt_max_batch;     // (rows that do not fit LDS are read from memory)
+    if (may_fork && !(ctx->opt_debug & 262144) && nfork > FORK_CAP && ((kernel == FV_KERNEL_U16_REFINE && ctx->u16_ok) || (walk && maxlen >= 64))) {
+        g.cap = std::min(g.cap, FORK_CAP);
+        g.nstreams = all_streams ? FORK_STREAMS : std::min(FORK_STREAMS, (nfork + FORK_CAP - 1) / FORK_CAP);
+    }
+    return g;
+}
+
+inline hipStream_t stream_of(const fv_ctx *ctx, int sid) { return sid ? ctx->aux[sid - 1] : ctx->stream; }
+
+// Fork: streams 1 .. n - 1 wait for what the main stream holds so far.
+int fork_streams(fv_ctx *ctx, int n)
+{
+    // no packets may wait on the other queues while a serial generation runs (decode_beam_impl has the measurement)
+    // (polled: a blocking hipStreamSynchronize wakes the host ~30 us after the stream has drained, and the chip idles
+    // until the first forked launch arrives)
+    if (!ctx->fork_active) {
+        hipError_t qe;
+        while ((qe = hipStreamQuery(ctx->stream)) == hipErrorNotReady) std::this_thread::yield();
+        FV_HIP(qe);
+    }
+    ctx->fork_active = true;
+    FV_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
+    for (int q = 1; q < n; ++q) FV_HIP(hipStreamWaitEvent(stream_of(ctx, q), ctx->ev_fork, 0));
+    return 0;
+}
+
+// ... and the join: the main stream waits for each of them
+int join_streams(fv_ctx *ctx, int n)
+{
+    for (int q = 1; q < n; ++q) {
+        FV_HIP(hipEventRecord(ctx->ev_join[q - 1], stream_of(ctx, q)));
+        FV_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join[q - 1], 0));
+    }
+    return 0;
+}
+
+// init_rows / init_rows_csr over one chunk of passes, on the main stream: the first score row of each pass into
+// rows + PassDesc::row_off, from Pi or from the state `ans` holds at L - 1, with the emission term lb64[sym[L] * K + i]
+// (sym on the device).  coded: the rows' 16-bit codes and tile maxima beside them (init_rows_coded).
+int launch_init(fv_ctx *ctx, const fvk::PassChunk &ch, const int *ans, float *rows, const double *lb64, const int *sym, bool coded)
+{
+    const int K = ctx->K;
+    if (ctx->csr)
+        hipLaunchKernelGGL(fvk::init_rows_csr, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->CRptr.p,
+                           ctx->CRcol.p, ctx->CRlog.p, lb64, ctx->LPi64.p, sym, ans, rows, K);
+    else
+        hipLaunchKernelGGL(fvk::init_rows, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->LA64.p, ctx->nrows,
+                           lb64, ctx->LPi64.p, sym, ans, rows, K, coded ? ctx->d_rcodes.p : nullptr,
+                           coded ? ctx->d_rtmax.p : nullptr, -1.0f / ctx->qscale);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+// the slot of one task step: the rows it reads and writes, the emission rows of the symbol at time j, the arg row it leaves
+fvk::TaskSlot task_slot(const fv_ctx *ctx, const float *in, float *out, int j, int *arg_row)
+{
+    fvk::TaskSlot sl;
+    sl.t1_in = in; sl.t1_out = out; sl.bp_out = arg_row;
+    sl.tmp_row = ctx->view.lb32 + (size_t)ctx->h_ob[j] * ctx->K;
+    sl.tmp64_row = ctx->view.lb64 + (size_t)ctx->h_ob[j] * ctx->K;
+    return sl;
+}
+
+// Single-column last steps of passes that finish (fvk::last_column: the one column the back-track reads), collected and
+// flushed COL_CHUNK jobs per launch to one stream; `ans` holds the passes' end states (d_ans, or the flat form's snapshot).
+struct ColumnQueue {
+    fv_ctx *ctx;
+    hipStream_t stream;
+    fvk::ColArgs c;
+    ColumnQueue(fv_ctx *ctx_, hipStream_t st, const int *ans) : ctx(ctx_), stream(st)
+    {
+        c.LA64 = ctx->LA64.p; c.ans = ans; c.K = ctx->K; c.nrows = ctx->nrows; c.n = 0;
+    }
+    // the pass that ends at time R: its last row but one, the arg row its column goes to
+    int add(const float *row, int R, int *arg_row)
+    {
+        c.p[c.n++] = fvk::ColJob{ row, ctx->view.lb32 + (size_t)ctx->h_ob[R] * ctx->K, arg_row, R };
+        return c.n == fvk::COL_CHUNK ? flush() : 0;
+    }
+    int flush()
+    {
+        if (c.n == 0) return 0;
+        if (ctx->csr) {
+            fvk::CsrColArgs cc;
+            cc.ck = ctx->CSk.p; cc.c64 = ctx->CS64.p; cc.tile_off = ctx->CSoff.p; cc.tile_nwb = ctx->CSnwb.p;
+            cc.ans = c.ans; cc.K = c.K; cc.n = c.n;
+            std::copy(c.p, c.p + c.n, cc.p);
+            hipLaunchKernelGGL(fvk::last_column_csr, dim3(c.n), dim3(256), 0, stream, cc);
+        } else
+            hipLaunchKernelGGL(fvk::last_column, dim3(c.n), dim3(256), 0, stream, c);
+        FV_HIP(hipGetLastError());
+        ctx->stats.column_steps += c.n;
+        c.n = 0;
+        return 0;
+    }
+};
+
+// the end pick of a single whole-sequence pass on its last row, into *end / *score ...
+int end_pick(fv_ctx *ctx, const float *row, int *end, float *score)
+{
+    hipLaunchKernelGGL(fvk::final_argmax, dim3(1), dim3(1024), 0, ctx->stream, row, ctx->K, end, score);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+// ... and its back-track from path[R] through the arg rows (row j of `bp`: time j) into path[0 .. R - 1]
+int backtrack_whole(fv_ctx *ctx, const int *bp, int R, int *path, unsigned long long *restarts)
+{
+    fvk::PassChunk ch;
+    ch.n = 1;
+    ch.p[0] = fvk::PassDesc{ 0, R, 1, 1, 0 };
+    hipLaunchKernelGGL(fvk::backtrack, dim3(1), dim3(64), 0, ctx->stream, ch, bp, ctx->K, path, restarts);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
 
 int prof_event(fv_ctx *ctx, size_t idx, hipEvent_t *out)
 {
@@ -477,68 +609,16 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
             const fv::Pass &p = passes[base + q];
             ch.p[q] = fvk::PassDesc{ p.L, p.R, p.from_pi ? 1 : 0, p.whole ? 1 : 0, (long long)(base + q) * 2 * ctx->nrows };
         }
-        if (ctx->csr)
-            hipLaunchKernelGGL(fvk::init_rows_csr, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->CRptr.p,
-                               ctx->CRcol.p, ctx->CRlog.p, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, ctx->d_rows.p, K);
-        else {
-            const bool coded = init_rows_coded(ctx, base, ch.n);
-            hipLaunchKernelGGL(fvk::init_rows, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch,
-                               ctx->LA64.p, ctx->nrows, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p,
-                               ctx->d_rows.p, K, coded ? ctx->d_rcodes.p : nullptr, coded ? ctx->d_rtmax.p : nullptr, -1.0f / ctx->qscale);
-        }
-        FV_HIP(hipGetLastError());
+        if (int rc = launch_init(ctx, ch, ctx->d_ans.p, ctx->d_rows.p, ctx->view.lb64, ctx->d_ob.p, init_rows_coded(ctx, base, ch.n))) return rc;
     }
     const int maxlen = passes[0].R - passes[0].L;
-    // (the float64 kernel beyond one LDS row sweeps slabs of source rows: four tasks per launch keep a slab at ~10000 rows)
-    const bool slabbed = (kernel == FV_KERNEL_F64_STREAM || kernel == FV_KERNEL_Q16_REFINE) && !ctx->full_ok;
-    int cap = std::max(1, std::min(ctx->opt_max_batch, slabbed ? 4 : max_batch_for(ctx->nrows, !ctx->full_ok)));
-    if (kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64) cap = ctx->opt_max_batch;     // (rows that do not fit LDS are read from memory)
     const bool whole_gen = passes[0].whole;       // generation 0: bracket its step launches for the stats
-    // The batches of a lock-step are independent, and a step launch is latency-bound at both ends (staging the score
-    // rows; reductions and refine): the right-hand generations of the packed 16-bit kernel therefore run as batches of
-    // FORK_CAP tasks dealt to FORK_STREAMS streams, small enough (36 KB of LDS, 81 VGPRs, 8 waves) for three workgroups
-    // of different launches to share a CU — one launch's head and tail run under the sweeps of the others.  cfg2
-    // right-hand passes 2.10 -> 1.85 ms, cfg3 62.7 -> 44.7 ms; the f32 filter in two co-resident 8-wave workgroups gave
-    // 1.96 / 53.0, batches of two tasks and four streams were slower.  The sparse walk gains the same way (cfg3 right-hand
-    // 33.4 -> 23.1 ms; at cfg2's 31-step passes nothing, so short generations stay on one stream and the host keeps
-    // running ahead).  FV_OPT_DEBUG bit 18: off.
-    constexpr int FORK_STREAMS = 3, FORK_CAP = 4;
-    // (Round 3, measured and not kept: the co-resident batches in ONE launch, gridDim.y = three batches of four, instead
-    // of three launches on three streams — no fork / join, a third of the host launches — cfg2 right-hand 1.64 -> 1.79 ms,
-    // cfg3 43.8 -> 51.1 ms: workgroups of one launch run in phase, all in their prologue or all in their sweep; what the
-    // streams provide is the stagger.)
-    const bool two = ((kernel == FV_KERNEL_U16_REFINE && ctx->u16_ok) || ((kernel == FV_KERNEL_SPARSE_Q16 || kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64) && maxlen >= 64)) &&
-                     !(ctx->opt_debug & 262144) && (!whole_gen || batch == BATCH_FORK) && np > FORK_CAP &&
-                     !ctx->opt_profile && !(ctx->opt_debug & 64);
-    const int nbatches = (np + FORK_CAP - 1) / FORK_CAP;
-    const int nstreams = two ? std::min(FORK_STREAMS, nbatches) : 1;      // (batches of three tasks were slower: 2.16 / 54.9 ms)
-    auto fork = [&]() -> int {
-        FV_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-        for (int q = 1; q < nstreams; ++q) FV_HIP(hipStreamWaitEvent(ctx->aux[q - 1], ctx->ev_fork, 0));
-        return 0;
-    };
-    if (two) {
-        cap = std::min(cap, FORK_CAP);
-        // no packets may wait on the other queues while a serial generation runs (decode_beam_impl has the measurement)
-        // (polled: a blocking hipStreamSynchronize wakes the host ~30 us after the stream has drained, and the chip idles
-        // until the first forked launch arrives)
-        if (!ctx->fork_active) {
-            hipError_t qe;
-            while ((qe = hipStreamQuery(ctx->stream)) == hipErrorNotReady) std::this_thread::yield();
-            FV_HIP(qe);
-        }
-        ctx->fork_active = true;
-        { int rc = fork(); if (rc) return rc; }
-    }
-    ctx->forked_batches = two;
-    struct Unfork { fv_ctx *c; ~Unfork() { c->forked_batches = false; c->lstream = nullptr; } } unfork{ ctx };
-    auto join = [&]() -> int {
-        for (int q = 1; q < nstreams; ++q) {
-            FV_HIP(hipEventRecord(ctx->ev_join[q - 1], ctx->aux[q - 1]));
-            FV_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join[q - 1], 0));
-        }
-        return 0;
-    };
+    // (a generation 0 forks only as a batch's; nothing that brackets or captures single launches forks)
+    const bool may_fork = (!whole_gen || batch == BATCH_FORK) && !ctx->opt_profile && !(ctx->opt_debug & 64);
+    const GenShape shape = generation_shape(ctx, kernel, maxlen, np, may_fork, false);
+    const int cap = shape.cap, nstreams = shape.nstreams;
+    const bool two = nstreams > 1;
+    if (two) { if (int rc = fork_streams(ctx, nstreams)) return rc; }
     const bool col_last = !(ctx->opt_debug & 8);  // FV_OPT_DEBUG bit 3: run every last step as a full step
     // FV_OPT_DEBUG bit 6 (experiment): capture this generation's step launches into a hipGraph and replay it
     const bool use_graph = (ctx->opt_debug & 64) && !ctx->opt_profile;
@@ -556,12 +636,8 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
             const int nb = std::min(cap, full - base);
             fvk::TaskSlot slots[fvk::MAX_BATCH];
             for (int q = 0; q < nb; ++q) {
-                const fv::Pass &p = passes[base + q];
-                slots[q].t1_in = row(base + q, (s - 1) & 1);
-                slots[q].t1_out = row(base + q, s & 1);
-                slots[q].tmp_row = ctx->view.lb32 + (size_t)ctx->h_ob[p.L + s] * K;
-                slots[q].tmp64_row = ctx->view.lb64 + (size_t)ctx->h_ob[p.L + s] * K;
-                slots[q].bp_out = ctx->d_bp.p + (size_t)(p.L + s) * K;
+                const int j = passes[base + q].L + s;
+                slots[q] = task_slot(ctx, row(base + q, (s - 1) & 1), row(base + q, s & 1), j, ctx->d_bp.p + (size_t)j * K);
             }
             hipEvent_t e0 = nullptr, e1 = nullptr;
             if (ctx->opt_profile) {
@@ -570,47 +646,22 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
                 nprof += 2;
                 FV_HIP(hipEventRecord(e0, ctx->stream));
             }
-            const int other = two ? (base / cap) % nstreams : 0;         // batch b keeps its stream for the whole generation
-            ctx->lstream = other ? ctx->aux[other - 1] : ctx->stream;
-            int rc = launch_step_kernel(ctx, kernel, slots, nb, s & 1);
-            ctx->lstream = nullptr;
-            if (rc) return rc;
+            const int sid = two ? (base / cap) % nstreams : 0;           // batch b keeps its stream for the whole generation
+            if (int rc = queue_step(ctx, StepLaunch{ kernel, stream_of(ctx, sid), two, s & 1 }, slots, nb)) return rc;
             if (ctx->opt_profile) FV_HIP(hipEventRecord(e1, ctx->stream));
-            ctx->stats.step_launches += 1;
-            ctx->stats.task_steps += nb;
         }
         // Single-column last steps of the passes that finish at this lock-step.  A pass's row was written by the stream its
         // batch keeps for the whole generation (or, at lock-step 1, by init_rows on the main stream), so its last step goes
         // to that very stream: no cross-stream join in the middle of a generation (a join cost ~10 us of host time, and
         // the dependency between queues left the chip idle for 15-50 us at each of the 24 of a cfg2 decode).
-        for (int sid = 0; sid < nstreams; ++sid) {
-            fvk::ColArgs c;
-            c.LA64 = ctx->LA64.p; c.ans = ctx->d_ans.p; c.K = K; c.nrows = ctx->nrows; c.n = 0;
-            hipStream_t cst = sid ? ctx->aux[sid - 1] : ctx->stream;
-            auto flush = [&]() -> int {
-                if (c.n == 0) return 0;
-                if (ctx->csr) {
-                    fvk::CsrColArgs cc;
-                    cc.ck = ctx->CSk.p; cc.c64 = ctx->CS64.p; cc.tile_off = ctx->CSoff.p; cc.tile_nwb = ctx->CSnwb.p;
-                    cc.ans = ctx->d_ans.p; cc.K = K; cc.n = c.n;
-                    std::copy(c.p, c.p + c.n, cc.p);
-                    hipLaunchKernelGGL(fvk::last_column_csr, dim3(c.n), dim3(256), 0, cst, cc);
-                } else
-                hipLaunchKernelGGL(fvk::last_column, dim3(c.n), dim3(256), 0, cst, c);
-                FV_HIP(hipGetLastError());
-                ctx->stats.column_steps += c.n;
-                c.n = 0;
-                return 0;
-            };
+        for (int sid = 0; sid < nstreams && full < active; ++sid) {
+            ColumnQueue cols(ctx, stream_of(ctx, sid), ctx->d_ans.p);
             for (int q = full; q < active; ++q) {
                 const int owner = (two && s > 1) ? (q / cap) % nstreams : 0;
                 if (owner != sid) continue;
-                const fv::Pass &p = passes[q];
-                c.p[c.n++] = fvk::ColJob{ row(q, (s - 1) & 1), ctx->view.lb32 + (size_t)ctx->h_ob[p.R] * K, ctx->d_bp.p + (size_t)p.R * K, p.R };
-                if (c.n == fvk::COL_CHUNK) { int rc = flush(); if (rc) return rc; }
+                if (int rc = cols.add(row(q, (s - 1) & 1), passes[q].R, ctx->d_bp.p + (size_t)passes[q].R * K)) return rc;
             }
-            int rc = flush();
-            if (rc) return rc;
+            if (int rc = cols.flush()) return rc;
         }
     }
     if (use_graph) {
@@ -624,7 +675,7 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
         (void)hipGraphDestroy(g);
     }
     if (whole_gen && !two) FV_HIP(hipEventRecord(ctx->ev_s1, ctx->stream));
-    if (two) { int rc = join(); if (rc) return rc; }
+    if (two) { if (int rc = join_streams(ctx, nstreams)) return rc; }
     if (whole_gen && two) FV_HIP(hipEventRecord(ctx->ev_s1, ctx->stream));      // (a batch's forked generation 0: after the join)
     // end states + chains
     if (batch) {
@@ -651,9 +702,7 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
         if (!passes[q].whole) continue;
         const int len = passes[q].R - passes[q].L;
         const float *last = ctx->d_rows.p + (size_t)q * 2 * ctx->nrows + (size_t)(len & 1) * ctx->nrows;
-        hipLaunchKernelGGL(fvk::final_argmax, dim3(1), dim3(1024), 0, ctx->stream, last, K,
-                           ctx->d_ans.p + passes[q].R, ctx->d_score.p);
-        FV_HIP(hipGetLastError());
+        if (int rc = end_pick(ctx, last, ctx->d_ans.p + passes[q].R, ctx->d_score.p)) return rc;
     }
     for (int base = 0; base < np; base += fvk::PASS_CHUNK) {
         fvk::PassChunk ch;
@@ -679,31 +728,17 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
 // by generation while S agrees with the committed answers.  A pass is a deterministic function of (L, R, start state,
 // end state, observations): where the resolver commits, every bit is the generation-by-generation result; where it
 // stops (counter FLAT_COUNTER), decode_full_impl runs the remaining generations the old way.
-constexpr int FLAT_STREAMS = 3, FLAT_CAP = 4;      // today's winning form of a forked generation: batches of four, three streams
+// Its launches take the winning form of a forked generation (generation_shape: batches of FORK_CAP on FORK_STREAMS streams).
 // auto: from the smallest measured K at which the flat form wins, and up to the longest measured T at which it does — long
 // sequences keep their launch slots full generation by generation, have nothing to gain, and the more passes a decode
 // has the likelier one of them mis-speculates (cfg3, T = 4096: 2 of 4095, which costs the whole fall-back)
 constexpr int FLAT_AUTO_MIN_K = 512, FLAT_AUTO_MAX_T = 1024;
-
-// the batch size and stream count run_generation_full would take for a forked right-hand generation of this kernel
-// (maxlen: steps of the longest right-hand pass, nlong: right-hand passes of more than one step)
-void flat_shape(const fv_ctx *ctx, int kernel, int maxlen, int nlong, int &cap, int &nstreams)
-{
-    const bool slabbed = (kernel == FV_KERNEL_F64_STREAM || kernel == FV_KERNEL_Q16_REFINE) && !ctx->full_ok;
-    cap = std::max(1, std::min(ctx->opt_max_batch, slabbed ? 4 : max_batch_for(ctx->nrows, !ctx->full_ok)));
-    if (kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64) cap = ctx->opt_max_batch;
-    const bool walk = kernel == FV_KERNEL_SPARSE_Q16 || kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64;
-    const bool fork = ((kernel == FV_KERNEL_U16_REFINE && ctx->u16_ok) || (walk && maxlen >= 64)) && !(ctx->opt_debug & 262144) && nlong > FLAT_CAP;
-    nstreams = fork ? FLAT_STREAMS : 1;
-    if (fork) cap = std::min(cap, FLAT_CAP);
-}
 
 int run_flat_full(fv_ctx *ctx, int kernel, int T)
 {
     const fv::FlatPlan &fp = ctx->flat_plan;
     const int K = ctx->K, np = (int)fp.passes.size(), nstreams = fp.nstreams;
     const bool two = nstreams > 1;
-    hipStream_t streams[FLAT_STREAMS] = { ctx->stream, ctx->aux[0], ctx->aux[1] };
     auto row = [&](int i, int parity) { return ctx->d_rows.p + (size_t)i * 2 * ctx->nrows + (size_t)parity * ctx->nrows; };
     auto arg_rows = [&](const fv::FlatPass &p) { return p.arg_row < 0 ? ctx->d_bp.p + (size_t)(p.L + 1) * K : ctx->d_flat_bp.p + (size_t)p.arg_row * K; };
     // pass table (kept on the device across decodes of one plan)
@@ -721,63 +756,24 @@ int run_flat_full(fv_ctx *ctx, int kernel, int T)
         fvk::PassChunk ch;
         ch.n = std::min(fvk::PASS_CHUNK, np - base);
         for (int q = 0; q < ch.n; ++q) ch.p[q] = fvk::PassDesc{ fp.passes[base + q].L, fp.passes[base + q].R, 0, 0, (long long)(base + q) * 2 * ctx->nrows };
-        if (ctx->csr)
-            hipLaunchKernelGGL(fvk::init_rows_csr, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->CRptr.p,
-                               ctx->CRcol.p, ctx->CRlog.p, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_snap.p, ctx->d_rows.p, K);
-        else {
-            const bool coded = init_rows_coded(ctx, base, ch.n);
-            hipLaunchKernelGGL(fvk::init_rows, dim3((K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->LA64.p, ctx->nrows,
-                               ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_snap.p, ctx->d_rows.p, K,
-                               coded ? ctx->d_rcodes.p : nullptr, coded ? ctx->d_rtmax.p : nullptr, -1.0f / ctx->qscale);
-        }
-        FV_HIP(hipGetLastError());
+        if (int rc = launch_init(ctx, ch, ctx->d_snap.p, ctx->d_rows.p, ctx->view.lb64, ctx->d_ob.p, init_rows_coded(ctx, base, ch.n))) return rc;
     }
-    if (two) {
-        // (as run_generation_full: nothing may wait on the other queues while the serial generation 0 runs; polled)
-        if (!ctx->fork_active) {
-            hipError_t qe;
-            while ((qe = hipStreamQuery(ctx->stream)) == hipErrorNotReady) std::this_thread::yield();
-            FV_HIP(qe);
-        }
-        ctx->fork_active = true;
-        FV_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-        for (int q = 1; q < nstreams; ++q) FV_HIP(hipStreamWaitEvent(streams[q], ctx->ev_fork, 0));
-    }
-    ctx->forked_batches = two;
-    struct Unfork { fv_ctx *c; ~Unfork() { c->forked_batches = false; c->lstream = nullptr; } } unfork{ ctx };
+    if (two) { if (int rc = fork_streams(ctx, nstreams)) return rc; }
     const bool col_last = !(ctx->opt_debug & 8);
     // single-column last steps of a set of passes, on one stream
     auto columns = [&](const std::vector<int> &which, hipStream_t st) -> int {
-        for (size_t base = 0; base < which.size(); base += fvk::COL_CHUNK) {
-            const int n = (int)std::min((size_t)fvk::COL_CHUNK, which.size() - base);
-            fvk::ColJob jobs[fvk::COL_CHUNK];
-            for (int q = 0; q < n; ++q) {
-                const int i = which[base + q];
-                const fv::FlatPass &p = fp.passes[i];
-                const int len = p.R - p.L;
-                jobs[q] = fvk::ColJob{ row(i, (len - 1) & 1), ctx->view.lb32 + (size_t)ctx->h_ob[p.R] * K, arg_rows(p) + (size_t)(len - 1) * K, p.R };
-            }
-            if (ctx->csr) {
-                fvk::CsrColArgs cc;
-                cc.ck = ctx->CSk.p; cc.c64 = ctx->CS64.p; cc.tile_off = ctx->CSoff.p; cc.tile_nwb = ctx->CSnwb.p;
-                cc.ans = ctx->d_snap.p; cc.K = K; cc.n = n;
-                std::copy(jobs, jobs + n, cc.p);
-                hipLaunchKernelGGL(fvk::last_column_csr, dim3(n), dim3(256), 0, st, cc);
-            } else {
-                fvk::ColArgs c;
-                c.LA64 = ctx->LA64.p; c.ans = ctx->d_snap.p; c.K = K; c.nrows = ctx->nrows; c.n = n;
-                std::copy(jobs, jobs + n, c.p);
-                hipLaunchKernelGGL(fvk::last_column, dim3(n), dim3(256), 0, st, c);
-            }
-            FV_HIP(hipGetLastError());
-            ctx->stats.column_steps += n;
+        ColumnQueue cols(ctx, st, ctx->d_snap.p);
+        for (int i : which) {
+            const fv::FlatPass &p = fp.passes[i];
+            const int len = p.R - p.L;
+            if (int rc = cols.add(row(i, (len - 1) & 1), p.R, arg_rows(p) + (size_t)(len - 1) * K)) return rc;
         }
-        return 0;
+        return cols.flush();
     };
     // Every stream walks its batches one after the other (a batch keeps its stream); the host deals its launches to the
     // streams in turn, so that each queue always holds work.
     struct Cursor { size_t b = 0; int s = 1; };
-    Cursor cur[FLAT_STREAMS];
+    Cursor cur[FORK_STREAMS];
     for (bool any = true; any;) {
         any = false;
         for (int sid = 0; sid < nstreams; ++sid) {
@@ -797,22 +793,10 @@ int run_flat_full(fv_ctx *ctx, int kernel, int T)
                 const int len = p.R - p.L;
                 if (len < s) continue;
                 if (len == s && col_last) { done.push_back(i); continue; }
-                slots[nb].t1_in = row(i, (s - 1) & 1);
-                slots[nb].t1_out = row(i, s & 1);
-                slots[nb].tmp_row = ctx->view.lb32 + (size_t)ctx->h_ob[p.L + s] * K;
-                slots[nb].tmp64_row = ctx->view.lb64 + (size_t)ctx->h_ob[p.L + s] * K;
-                slots[nb].bp_out = arg_rows(p) + (size_t)(s - 1) * K;
-                ++nb;
+                slots[nb++] = task_slot(ctx, row(i, (s - 1) & 1), row(i, s & 1), p.L + s, arg_rows(p) + (size_t)(s - 1) * K);
             }
-            if (nb) {
-                ctx->lstream = streams[sid];
-                const int rc = launch_step_kernel(ctx, kernel, slots, nb, s & 1);
-                ctx->lstream = nullptr;
-                if (rc) return rc;
-                ctx->stats.step_launches += 1;
-                ctx->stats.task_steps += nb;
-            }
-            if (!done.empty()) { const int rc = columns(done, streams[sid]); if (rc) return rc; }
+            if (nb) { if (int rc = queue_step(ctx, StepLaunch{ kernel, stream_of(ctx, sid), two, s & 1 }, slots, nb)) return rc; }
+            if (!done.empty()) { if (int rc = columns(done, stream_of(ctx, sid))) return rc; }
             if (++c.s > bt.len) { ++c.b; c.s = 1; }
         }
     }
@@ -821,31 +805,19 @@ int run_flat_full(fv_ctx *ctx, int kernel, int T)
         std::vector<int> ones;
         for (int i = 0; i < np; ++i) if (fp.passes[i].batch < 0 && fp.passes[i].stream == sid) ones.push_back(i);
         if (ones.empty()) continue;
-        if (col_last) { const int rc = columns(ones, streams[sid]); if (rc) return rc; continue; }
+        if (col_last) { const int rc = columns(ones, stream_of(ctx, sid)); if (rc) return rc; continue; }
         const size_t cap = (size_t)std::max(1, ctx->flat_key[2]);
         for (size_t base = 0; base < ones.size(); base += cap) {      // FV_OPT_DEBUG bit 3: as full steps
             const int nb = (int)std::min(cap, ones.size() - base);
             fvk::TaskSlot slots[fvk::MAX_BATCH];
             for (int q = 0; q < nb; ++q) {
                 const int i = ones[base + q];
-                const fv::FlatPass &p = fp.passes[i];
-                slots[q].t1_in = row(i, 0); slots[q].t1_out = row(i, 1);
-                slots[q].tmp_row = ctx->view.lb32 + (size_t)ctx->h_ob[p.R] * K;
-                slots[q].tmp64_row = ctx->view.lb64 + (size_t)ctx->h_ob[p.R] * K;
-                slots[q].bp_out = arg_rows(p);
+                slots[q] = task_slot(ctx, row(i, 0), row(i, 1), fp.passes[i].R, arg_rows(fp.passes[i]));
             }
-            ctx->lstream = streams[sid];
-            const int rc = launch_step_kernel(ctx, kernel, slots, nb, 1);
-            ctx->lstream = nullptr;
-            if (rc) return rc;
-            ctx->stats.step_launches += 1;
-            ctx->stats.task_steps += nb;
+            if (int rc = queue_step(ctx, StepLaunch{ kernel, stream_of(ctx, sid), two, 1 }, slots, nb)) return rc;
         }
     }
-    for (int q = 1; q < nstreams; ++q) {
-        FV_HIP(hipEventRecord(ctx->ev_join[q - 1], streams[q]));
-        FV_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join[q - 1], 0));
-    }
+    if (int rc = join_streams(ctx, nstreams)) return rc;
     // every chain in one launch, then the resolver
     hipLaunchKernelGGL(fvk::backtrack_flat, dim3(np), dim3(64), 0, ctx->stream, ctx->d_flat.p, ctx->d_bp.p, ctx->d_flat_bp.p, K,
                        ctx->d_snap.p, ctx->d_chain.p, ctx->d_counters.p + fvk::BT_COUNTER);
@@ -865,53 +837,41 @@ int run_flat_full(fv_ctx *ctx, int kernel, int T)
 
 namespace fvi {
 
-// every full-state step kernel may use the whole 160 KB of LDS
-int full_setup(fv_ctx *ctx)
+// every full-state step kernel launched with its score rows in LDS may use the whole of it (LDS_LIMIT): per task count
+// the four dense tables' forms (allow_big_lds), the three walks in their LDS form and the packed kernel's four forms
+template <int NB>
+int setup_nb(fv_ctx *ctx)
 {
     int rc = 0;
-    if ((rc = allow_big_lds<float, 1>(ctx)) || (rc = allow_big_lds<float, 2>(ctx)) || (rc = allow_big_lds<float, 4>(ctx)) ||
-        (rc = allow_big_lds<float, 8>(ctx)) || (rc = allow_big_lds<double, 1>(ctx)) || (rc = allow_big_lds<double, 2>(ctx)) ||
-        (rc = allow_big_lds<double, 4>(ctx)) || (rc = allow_big_lds<double, 8>(ctx)) ||
-        (rc = allow_big_lds<fvk::half_t, 1>(ctx)) || (rc = allow_big_lds<fvk::half_t, 2>(ctx)) ||
-        (rc = allow_big_lds<fvk::half_t, 4>(ctx)) || (rc = allow_big_lds<fvk::half_t, 8>(ctx)) ||
-        (rc = allow_big_lds<fvk::q16_t, 1>(ctx)) || (rc = allow_big_lds<fvk::q16_t, 2>(ctx)) ||
-        (rc = allow_big_lds<fvk::q16_t, 4>(ctx)) || (rc = allow_big_lds<fvk::q16_t, 8>(ctx)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_sparse<1>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_sparse<2>)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_sparse<4>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_sparse<8>)))
+    if ((rc = allow_big_lds<float, NB>(ctx)) || (rc = allow_big_lds<double, NB>(ctx)) || (rc = allow_big_lds<fvk::half_t, NB>(ctx)) ||
+        (rc = allow_big_lds<fvk::q16_t, NB>(ctx)) || (rc = set_big_lds(ctx, &fvk::trellis_step_sparse<NB>)) ||
+        (rc = set_big_lds(ctx, &fvk::trellis_step_csr<NB, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_csr_f64<NB, false>)) ||
+        (rc = set_big_lds(ctx, &fvk::trellis_step_u16<NB, 8, false, 16>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<NB, U_DB16, true, 16>)) ||
+        (rc = set_big_lds(ctx, &fvk::trellis_step_u16<NB, 16, false, 8>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<NB, U_DB16, true, 8>)))
         return rc;
-    if ((rc = set_big_lds(ctx, &fvk::trellis_step_csr<1, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_csr<2, false>)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_csr<4, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_csr<8, false>)))
-        return rc;
-    if ((rc = set_big_lds(ctx, &fvk::trellis_step_csr_f64<1, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_csr_f64<2, false>)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_csr_f64<4, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_csr_f64<8, false>)))
-        return rc;
-    if ((rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, 8, false, 16>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, U_DB16, true, 16>)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_u16<2, 8, false, 16>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<2, U_DB16, true, 16>)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_u16<4, 8, false, 16>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<4, U_DB16, true, 16>)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_u16<8, 8, false, 16>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<8, U_DB16, true, 16>)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, 16, false, 8>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, U_DB16, true, 8>)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_u16<2, 16, false, 8>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<2, U_DB16, true, 8>)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_u16<4, 16, false, 8>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<4, U_DB16, true, 8>)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_u16<8, 16, false, 8>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<8, U_DB16, true, 8>)))
-        return rc;
-    // the single-task forms without the FV_OPT_ROW_CODES code (launch_u16_variant)
-    if ((rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, 8, false, 16, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, U_DB16, true, 16, false>)) ||
-        (rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, 16, false, 8, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<1, U_DB16, true, 8, false>)))
-        return rc;
+    // the forms without the FV_OPT_ROW_CODES code (launch_u16_variant)
+    if constexpr (U16_CODE_FREE<NB>) {
+        if ((rc = set_big_lds(ctx, &fvk::trellis_step_u16<NB, 8, false, 16, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<NB, U_DB16, true, 16, false>)) ||
+            (rc = set_big_lds(ctx, &fvk::trellis_step_u16<NB, 16, false, 8, false>)) || (rc = set_big_lds(ctx, &fvk::trellis_step_u16<NB, U_DB16, true, 8, false>)))
+            return rc;
+    }
     return 0;
 }
 
+template <int... NB>
+int setup_all(fv_ctx *ctx, NbList<NB...>)
+{
+    int rc = 0;
+    (void)(((rc = setup_nb<NB>(ctx)) != 0) || ...);
+    return rc;
+}
+
+int full_setup(fv_ctx *ctx) { return setup_all(ctx, STEP_NB); }
+
 int launch_init_rows(fv_ctx *ctx, const fvk::PassChunk &ch, float *rows)
 {
-    if (ctx->csr)        // (a beam decode of a sparse-set model, FV_OPT_SPARSE_BEAM)
-        hipLaunchKernelGGL(fvk::init_rows_csr, dim3((ctx->K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch, ctx->CRptr.p,
-                           ctx->CRcol.p, ctx->CRlog.p, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, rows, ctx->K);
-    else
-    hipLaunchKernelGGL(fvk::init_rows, dim3((ctx->K + 255) / 256, ch.n), dim3(256), 0, ctx->stream, ch,
-                       ctx->LA64.p, ctx->nrows, ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, rows, ctx->K,
-                       static_cast<unsigned short *>(nullptr), static_cast<float *>(nullptr), 0.0f);
-    FV_HIP(hipGetLastError());
-    return 0;
+    // (ctx->csr here: a beam decode of a sparse-set model, FV_OPT_SPARSE_BEAM)
+    return launch_init(ctx, ch, ctx->d_ans.p, rows, ctx->view.lb64, ctx->d_ob.p, false);
 }
 
 // Workgroups of EMIS_BLOCK states by rows, about 2048 in all (eight per CU); the kernel strides over the rest.
@@ -952,40 +912,23 @@ int stream_init_row(fv_ctx *ctx, const double *lb64, const int *sym, float *row)
     fvk::PassChunk ch;
     ch.n = 1;
     ch.p[0] = fvk::PassDesc{ 0, 0, 1, 1, 0 };
-    if (ctx->csr)
-        hipLaunchKernelGGL(fvk::init_rows_csr, dim3((ctx->K + 255) / 256, 1), dim3(256), 0, ctx->stream, ch, ctx->CRptr.p,
-                           ctx->CRcol.p, ctx->CRlog.p, lb64, ctx->LPi64.p, sym, sym, row, ctx->K);
-    else
-        hipLaunchKernelGGL(fvk::init_rows, dim3((ctx->K + 255) / 256, 1), dim3(256), 0, ctx->stream, ch, ctx->LA64.p, ctx->nrows,
-                           lb64, ctx->LPi64.p, sym, sym, row, ctx->K, static_cast<unsigned short *>(nullptr),
-                           static_cast<float *>(nullptr), 0.0f);
-    FV_HIP(hipGetLastError());
-    return 0;
+    return launch_init(ctx, ch, sym, row, lb64, sym, false);      // (from Pi: no answer is read)
 }
 
+// (the stream's own rows and emission tables; the bare launch — a stream's steps are not counted as a decode's)
 int stream_step(fv_ctx *ctx, int kernel, const float *t1_in, float *t1_out, const float *tmp_row, const double *tmp64_row,
                 int *bp_out, int reverse)
 {
     fvk::TaskSlot sl;
     sl.t1_in = t1_in; sl.t1_out = t1_out; sl.bp_out = bp_out; sl.tmp_row = tmp_row; sl.tmp64_row = tmp64_row;
-    return launch_step_kernel(ctx, kernel, &sl, 1, reverse);
+    return launch_step_kernel(ctx, StepLaunch{ kernel, ctx->stream, false, reverse }, &sl, 1);
 }
 
-int stream_end_pick(fv_ctx *ctx, const float *row, int *end, float *score)
-{
-    hipLaunchKernelGGL(fvk::final_argmax, dim3(1), dim3(1024), 0, ctx->stream, row, ctx->K, end, score);
-    FV_HIP(hipGetLastError());
-    return 0;
-}
+int stream_end_pick(fv_ctx *ctx, const float *row, int *end, float *score) { return end_pick(ctx, row, end, score); }
 
 int stream_backtrack(fv_ctx *ctx, const int *bp, int R, int *path, unsigned long long *restarts)
 {
-    fvk::PassChunk ch;
-    ch.n = 1;
-    ch.p[0] = fvk::PassDesc{ 0, R, 1, 1, 0 };
-    hipLaunchKernelGGL(fvk::backtrack, dim3(1), dim3(64), 0, ctx->stream, ch, bp, ctx->K, path, restarts);
-    FV_HIP(hipGetLastError());
-    return 0;
+    return backtrack_whole(ctx, bp, R, path, restarts);
 }
 
 }  // namespace fvi
@@ -1129,8 +1072,6 @@ int fvi::stream_admit(fv_ctx *ctx, int &kernel)
     if (int rc = fvi::emission_view(ctx, symbols, 0)) return rc;
     ctx->row_codes = 0;
     ctx->row_coded.clear();
-    ctx->lstream = nullptr;
-    ctx->forked_batches = false;
     return admit_full(ctx, nullptr, 0, kernel);
 }
 
@@ -1166,10 +1107,12 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
     bool flat = ctx->opt_flat != 0 && mode == FV_MODE_REFERENCE && plan.generations() >= 2 && plan.generations() - 1 <= fvk::FLAT_MAX_GENS &&
                 !ctx->group && !ctx->comm && ctx->nranks == 1 && !ctx->opt_profile && !ctx->vanilla && !(ctx->opt_debug & 64);
     if (flat) {
-        int cap = 1, nstreams = 1, maxlen = 0, nlong = 0;
+        // the shape of one forked generation holding every right-hand pass of more than one step (the others are column jobs)
+        int maxlen = 0, nlong = 0;
         for (const fv::Pass &p : plan.passes)
             if (!p.whole) { maxlen = std::max(maxlen, p.R - p.L); nlong += p.R - p.L > 1 ? 1 : 0; }
-        flat_shape(ctx, kernel, maxlen, nlong, cap, nstreams);
+        const GenShape shape = generation_shape(ctx, kernel, maxlen, nlong, true, true);
+        const int cap = shape.cap, nstreams = shape.nstreams;
         // auto: the measured form only — the packed 16-bit kernel's three streams, more than one right-hand generation
         if (ctx->opt_flat == 1 && !(kernel == FV_KERNEL_U16_REFINE && nstreams > 1 && ctx->K >= FLAT_AUTO_MIN_K && T <= FLAT_AUTO_MAX_T && plan.generations() >= 3)) flat = false;
         if (flat) {
@@ -1379,31 +1322,20 @@ int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *pat
     ctx->vanilla = 1;
     auto ckpt = [&](int c) { return ctx->d_ckpt.p + (size_t)c * nrows; };
     auto scratch = [&](int q, int parity) { return ctx->d_rows.p + ((size_t)q * 2 + parity) * nrows; };
-    auto slot_for = [&](const float *in, float *out, int j) {
-        fvk::TaskSlot sl;
-        sl.t1_in = in; sl.t1_out = out;
-        sl.tmp_row = ctx->view.lb32 + (size_t)ctx->h_ob[j] * K;
-        sl.tmp64_row = ctx->view.lb64 + (size_t)ctx->h_ob[j] * K;
-        sl.bp_out = ctx->d_bp.p + (size_t)j * K;
-        return sl;
-    };
+    auto slot_for = [&](const float *in, float *out, int j) { return task_slot(ctx, in, out, j, ctx->d_bp.p + (size_t)j * K); };
+    auto launch_at = [&](int parity) { return StepLaunch{ FV_KERNEL_F64_STREAM, ctx->stream, false, parity }; };
     {   // initT1 (:119) into checkpoint 0
         fvk::PassChunk ch;
         ch.n = 1;
         ch.p[0] = fvk::PassDesc{ 0, T - 1, 1, 1, 0 };
-        hipLaunchKernelGGL(fvk::init_rows, dim3((K + 255) / 256, 1), dim3(256), 0, ctx->stream, ch, ctx->LA64.p, nrows,
-                           ctx->view.lb64, ctx->LPi64.p, ctx->d_ob.p, ctx->d_ans.p, ctx->d_ckpt.p, K,
-                           static_cast<unsigned short *>(nullptr), static_cast<float *>(nullptr), 0.0f);
-        FV_HIP(hipGetLastError());
+        if ((rc = launch_init(ctx, ch, ctx->d_ans.p, ctx->d_ckpt.p, ctx->view.lb64, ctx->d_ob.p, false))) return rc;
     }
     // first pass (:213-232)
     auto row_after = [&](int j) -> float * { return j % step == 0 ? ckpt(j / step) : scratch(nck, j & 1); };
     FV_HIP(hipEventRecord(ctx->ev_s0, ctx->stream));
     for (int j = 1; j < T; ++j) {
         fvk::TaskSlot sl = slot_for(row_after(j - 1), row_after(j), j);
-        if ((rc = launch_step_kernel(ctx, FV_KERNEL_F64_STREAM, &sl, 1, j & 1))) return rc;
-        ctx->stats.step_launches += 1;
-        ctx->stats.task_steps += 1;
+        if ((rc = queue_step(ctx, launch_at(j & 1), &sl, 1))) return rc;
     }
     FV_HIP(hipEventRecord(ctx->ev_s1, ctx->stream));
     FV_HIP(hipEventRecord(ctx->ev_top, ctx->stream));
@@ -1412,8 +1344,8 @@ int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *pat
     for (int c = 0; c < nck; ++c) order[c] = c;
     auto seg_len = [&](int c) { return std::min((c + 1) * step, T - 1) - c * step; };
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return seg_len(a) > seg_len(b); });
-    const int cap = std::max(1, std::min(ctx->opt_max_batch, ctx->full_ok ? max_batch_for(nrows, false) : 4));
     const int maxlen = seg_len(order[0]);
+    const int cap = generation_shape(ctx, FV_KERNEL_F64_STREAM, maxlen, nck, false, false).cap;     // (one stream: no fork)
     int active = nck;
     for (int s = 1; s <= maxlen; ++s) {
         while (active > 0 && seg_len(order[active - 1]) < s) --active;
@@ -1424,23 +1356,12 @@ int decode_checkpoint_impl(fv_ctx *ctx, const int *ob, int T, int step, int *pat
                 const int c = order[base + q];
                 slots[q] = slot_for(s == 1 ? ckpt(c) : scratch(c, (s - 1) & 1), scratch(c, s & 1), c * step + s);
             }
-            if ((rc = launch_step_kernel(ctx, FV_KERNEL_F64_STREAM, slots, nb, s & 1))) return rc;
-            ctx->stats.step_launches += 1;
-            ctx->stats.task_steps += nb;
+            if ((rc = queue_step(ctx, launch_at(s & 1), slots, nb))) return rc;
         }
     }
     // end state (:152-165) from the first pass's last row, then the back-track through the kept arg rows (:167-171)
-    hipLaunchKernelGGL(fvk::final_argmax, dim3(1), dim3(1024), 0, ctx->stream, row_after(T - 1), K, ctx->d_ans.p + (T - 1),
-                       ctx->d_score.p);
-    FV_HIP(hipGetLastError());
-    {
-        fvk::PassChunk ch;
-        ch.n = 1;
-        ch.p[0] = fvk::PassDesc{ 0, T - 1, 1, 1, 0 };
-        hipLaunchKernelGGL(fvk::backtrack, dim3(1), dim3(64), 0, ctx->stream, ch, ctx->d_bp.p, K, ctx->d_ans.p,
-                           ctx->d_counters.p + fvk::BT_COUNTER);
-        FV_HIP(hipGetLastError());
-    }
+    if ((rc = end_pick(ctx, row_after(T - 1), ctx->d_ans.p + (T - 1), ctx->d_score.p))) return rc;
+    if ((rc = backtrack_whole(ctx, ctx->d_bp.p, T - 1, ctx->d_ans.p, ctx->d_counters.p + fvk::BT_COUNTER))) return rc;
     ctx->close_stats((long long)K * K, 0);
     const long long whole[2] = { 0, T };
     return fvi::finish_decode(ctx, plan, whole, 1, path_out, score_out, nullptr, t0, 0, false);

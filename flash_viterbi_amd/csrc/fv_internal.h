@@ -62,8 +62,6 @@ struct fv_ctx {
     hipStream_t aux[BEAM_AUX] = { nullptr, nullptr, nullptr };
     hipEvent_t ev_fork = nullptr, ev_join[BEAM_AUX] = { nullptr, nullptr, nullptr };
     bool fork_active = false;     // a forked generation of the current decode has been queued
-    hipStream_t lstream = nullptr; // stream the next full-state step launch goes to (nullptr: `stream`)
-    bool forked_batches = false;  // the launches of this generation alternate between streams: co-resident workgroups wanted
     int num_cus = 256;       // multiProcessorCount of the device (MI355X: 256)
     hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_top = nullptr, ev_s0 = nullptr, ev_s1 = nullptr;
     std::string detail;
@@ -126,8 +124,6 @@ struct fv_ctx {
     DevBuf<float> d_rtmax;
     std::vector<unsigned char> row_coded;
     int row_codes = 0;       // the decode in flight: bit 0 single-task launches take the route, bit 1 batched launches
-    int launch_codes = 0;    // StepArgs::codes of the launch launch_step_kernel is making
-    const void *launch_code_slots = nullptr;   // ... and its fvk::CodeSlot array (valid during that call)
     // FV_OPT_FLAT_GENERATIONS (fv_full.hip, run_flat_full): snapshot S of the whole-sequence chain, the private arg rows of
     // the generations >= 2, the chain of every right-hand pass and the pass table the back-track and the resolver read
     DevBuf<int> d_snap, d_flat_bp, d_chain;

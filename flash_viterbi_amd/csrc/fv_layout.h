@@ -14,6 +14,7 @@ constexpr int NWAVES = 16;
 constexpr int BLOCK = NWAVES * 64;         // 1024 threads: one workgroup per CU keeps 64+ KB of loads in flight
 constexpr int ROW_ALIGN = 32;              // nrows = roundup(K, 32): whole row blocks for every table type
 constexpr int MAX_BATCH = 8;               // independent tasks sharing one sweep of the table
+constexpr int LDS_LIMIT = 160 * 1024;      // bytes of LDS one workgroup may ask for (gfx950: all of a CU's 160 KB)
 
 // Tile-major layout with an R-row interleave: R = 4 for the f32 / f64 tables, 8 for the f16 table.
 template <int R>
