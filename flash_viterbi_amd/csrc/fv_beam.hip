@@ -13,40 +13,58 @@ int decode_beam_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets,
 inline int beam_ld(int K) { return (K + fvb::BEAM_COLS - 1) / fvb::BEAM_COLS * fvb::BEAM_COLS; }
 inline int beam_ldq(int K) { static_assert(fvb::BEAMQ_COLS == 128, "fv_ldq"); return fv_ldq(K); }   // ... of the 16-bit one
 
-// One generation of beam passes in lock-step (same shape as run_generation_full).  Buffers are indexed
-// by absolute time j (passes of one generation cover disjoint time ranges): scores_all[j] = the K
-// scores after consuming ob[j] (j = L: the init row), set_*[j] = the members of the heap built from
-// them (order-free), slot_*[j] = its exact array layout (rebuilt after the lock-step loop).
-// Streams a generation of np passes is dealt to (pass i of the length-sorted list goes to group i % n).
-// Only for big steps (cfg5: 64 M cells per pass and step; FV_OPT_DEBUG bit 17 forces it): once the auxiliary queues
-// have carried work, every dispatch on the main stream takes ~2 us longer (measured, also with the main stream at
+// Streams generation g (np passes) of a decode of nseq sequences is dealt to: pass i of the length-sorted list goes to
+// group i % n.  FV_OPT_DEBUG bits 16 / 17 force one stream / the groups.
+// A generation of one sequence's passes: only for big steps (cfg5: 64 M cells per pass and step) — once the auxiliary
+// queues have carried work, every dispatch on the main stream takes ~2 us longer (measured, also with the main stream at
 // high priority) — 1 ms over the whole-sequence pass of cfg4, more than the overlap returns there.
-inline int beam_groups(const fv_ctx *ctx, int np, int beam)
-{
-    if ((ctx->opt_debug & 65536) || np < 2) return 1;            // FV_OPT_DEBUG bit 16: one stream
-    if (!(ctx->opt_debug & 131072) && (double)beam * ctx->K < 16e6) return 1;
-    return std::min(1 + fv_ctx::BEAM_AUX, np);
-}
-
 // Generation 0 of fv_decode_beam_batch: np whole-sequence passes in lock-step.  A select launch lasts as long as its slowest
 // workgroup, and a workgroup that meets a reach event replays heaps for tens of microseconds: on one stream every pass
-// of the lock-step waits behind it, dealt to the stream groups only the passes of its group do — at the price of the
-// dispatch overhead queued auxiliary streams put on the main one (beam_groups).  DESIGN.md 5.4b has both forms' numbers;
-// FV_OPT_DEBUG bit 29 selects the form that is not the default, bits 16 / 17 force one stream / the groups as elsewhere.
+// of the lock-step waits behind it, dealt to the stream groups only the passes of its group do — at the price of that
+// dispatch overhead.  DESIGN.md 5.4b has both forms' numbers; FV_OPT_DEBUG bit 29 selects the form that is not the default.
 constexpr bool BATCH_GEN0_DEALT = true;
-inline int batch_gen0_groups(const fv_ctx *ctx, int np)
+int gen_groups(const fv_ctx *ctx, size_t g, int np, int beam, int nseq)
 {
-    if ((ctx->opt_debug & 65536) || np < 2) return 1;
-    const bool dealt = (ctx->opt_debug & 131072) || BATCH_GEN0_DEALT != !!(ctx->opt_debug & (1 << 29));
-    return dealt ? std::min(1 + fv_ctx::BEAM_AUX, np) : 1;
-}
-// stream groups of generation g of a decode of nseq sequences
-inline int gen_groups(const fv_ctx *ctx, size_t g, int np, int beam, int nseq)
-{
-    return (g == 0 && nseq > 1) ? batch_gen0_groups(ctx, np) : beam_groups(ctx, np, beam);
+    if ((ctx->opt_debug & FV_DBG_BEAM_ONE_STREAM) || np < 2) return 1;
+    const bool dealt = (g == 0 && nseq > 1) ? BATCH_GEN0_DEALT != !!(ctx->opt_debug & FV_DBG_BEAM_BATCH_GEN0_OTHER)
+                                            : (double)beam * ctx->K >= 16e6;
+    return (dealt || (ctx->opt_debug & FV_DBG_BEAM_GROUPS)) ? std::min(1 + fv_ctx::BEAM_AUX, np) : 1;
 }
 
-// The step kernel of one beam launch: the one rule run_generation_beam and fv_test_beam_step share.
+// The arguments every job of a step launch shares; the caller sets n and fills p[0 .. n) with beam_step_job.
+fvb::BeamStepArgs beam_step_args(const fv_ctx *ctx, int beam, int cand_cap)
+{
+    const int K = ctx->K;
+    fvb::BeamStepArgs a;
+    a.LA64R = ctx->LA64R.p; a.tie_count = ctx->d_tie_count.p; a.tie_list = ctx->d_tie_list.p;
+    a.tie_cap = (unsigned int)ctx->d_tie_list.n;
+    a.counters = ctx->d_counters.p;
+    a.K = K; a.ld = beam_ld(K); a.ldq = beam_ldq(K); a.beam = beam;
+    a.LAQ16R = ctx->LAQ16R.p; a.qpar = ctx->beam_q16_ready ? reinterpret_cast<const float *>(ctx->d_qaux.p + 2) : nullptr;
+    a.cand = ctx->d_cand.p; a.cand_count = ctx->d_cand_count.p; a.cand_cap = cand_cap;
+    a.n = 0;
+    return a;
+}
+// One job: from the members and the cut at index `in` of the per-step buffers, consuming symbol sym, the records of step
+// j at index j (a decode: in = j - 1; fv_test_beam_step: in = j, the caller's slot sets).
+fvb::BeamSlot beam_step_job(const fv_ctx *ctx, int beam, int j, int in, int sym)
+{
+    const size_t K = (size_t)ctx->K, BP = (size_t)fvb::beam_pitch(beam);
+    fvb::BeamSlot p;
+    p.sval = ctx->d_hval.p + in * BP;
+    p.sstate = ctx->d_hstate.p + in * BP;
+    p.doubt = ctx->d_doubt.p + (size_t)j * fvb::DOUBT_CAP;
+    p.doubt_count = ctx->d_doubt_count.p + j;
+    p.scores = ctx->d_scores.p + j * K;
+    p.bp_row = ctx->d_bp.p + j * K;
+    p.tmp_row = ctx->view.lb32 + sym * K;
+    p.j = j;
+    p.cut = ctx->d_cut.p + (size_t)in * fvb::CUT_W;
+    p.dupwin = ctx->d_dupwin.p + j;
+    return p;
+}
+
+// The step kernel of one beam launch: the one rule beam_forward and fv_test_beam_step share.
 int launch_beam_step(fv_ctx *ctx, const fvb::BeamStepArgs &a, hipStream_t st)
 {
     const int K = ctx->K, beam = a.beam;
@@ -71,13 +89,13 @@ int launch_beam_step(fv_ctx *ctx, const fvb::BeamStepArgs &a, hipStream_t st)
     // launch against 10.6 + 5.0 for the float64 kernel, so it is used from ~80 MB of float64 rows per
     // launch on (cfg5: 537 MB per pass).  FV_OPT_DEBUG bit 8: never, bit 9: always.
     // (emission scores above 0, fv_set_emissions: the float64 kernel, as for a model with an entry above 1)
-    const bool use_q16 = ctx->beam_q16_ready && ctx->view.logs_nonpositive && !(ctx->opt_debug & 256) &&
-                         ((ctx->opt_debug & 512) || (double)a.n * beam * K * 8.0 >= 80e6);
+    const bool use_q16 = ctx->beam_q16_ready && ctx->view.logs_nonpositive && !(ctx->opt_debug & FV_DBG_BEAM_F64) &&
+                         ((ctx->opt_debug & FV_DBG_BEAM_Q16) || (double)a.n * beam * K * 8.0 >= 80e6);
     // 8-wave workgroups once the launch has more 16-wave workgroups than fit the chip together (two per CU);
     // FV_OPT_DEBUG bit 25: never, bit 26: always
     const int panels = beam_ldq(K) / fvb::BEAMQ_COLS;
-    const bool narrow = !(ctx->opt_debug & (1 << 25)) &&
-                        ((ctx->opt_debug & (1 << 26)) || (long long)panels * a.n > 2LL * ctx->num_cus);
+    const bool narrow = !(ctx->opt_debug & FV_DBG_BEAM_WIDE) &&
+                        ((ctx->opt_debug & FV_DBG_BEAM_NARROW) || (long long)panels * a.n > 2LL * ctx->num_cus);
     // (4-wave workgroups for launches beyond four 8-wave workgroups per CU: cfg4 right-hand 3.51 -> 3.56 ms, cfg5 95.8 -> 97.1)
     if (use_q16 && narrow) {
         record(FV_TV_BEAM_Q16_W8);
@@ -87,7 +105,7 @@ int launch_beam_step(fv_ctx *ctx, const fvb::BeamStepArgs &a, hipStream_t st)
         hipLaunchKernelGGL(fvb::beam_step_q16<16>, dim3(panels, a.n), dim3(fvb::BEAM_BLOCK),
                            fvb::beam_step_q16_lds(beam), st, a);
     // (small beams: four waves per workgroup — K = 3965, B = 32: 4.55 -> 4.23 ms; eight waves at B = 256: 6.43 -> 6.50, not kept)
-    } else if (beam <= 64 && !(ctx->opt_debug & (1 << 25))) {
+    } else if (beam <= 64 && !(ctx->opt_debug & FV_DBG_BEAM_WIDE)) {
         record(FV_TV_BEAM_W4);
         hipLaunchKernelGGL(fvb::beam_step<4>, dim3(beam_ld(K) / fvb::BEAM_COLS, a.n), dim3(4 * 64), fvb::beam_step_lds(beam, 4), st, a);
     } else {
@@ -100,7 +118,7 @@ int launch_beam_step(fv_ctx *ctx, const fvb::BeamStepArgs &a, hipStream_t st)
 }
 
 // Capacity of a step's candidate list under the current options (0: no lists).  FV_OPT_DEBUG bit 10: never a list.
-inline int beam_cand_cap(const fv_ctx *ctx, int K, int beam) { return (ctx->opt_debug & 1024) ? 0 : fvb::cand_cap_for(K, beam); }
+inline int beam_cand_cap(const fv_ctx *ctx, int K, int beam) { return (ctx->opt_debug & FV_DBG_NO_CAND_LISTS) ? 0 : fvb::cand_cap_for(K, beam); }
 
 // FV_TS_* bit of a select-kernel instantiation (test hooks only)
 unsigned long long select_variant(fvb::SelKernel k)
@@ -122,7 +140,7 @@ unsigned long long select_variant(fvb::SelKernel k)
 }
 
 // The select of one lock-step — the members of the heaps of `count` passes at lock-step s, one launch: the one rule
-// run_generation_beam and fv_test_beam_select share.  K: states per score row; T: entries of the per-step buffers (which are
+// beam_forward and fv_test_beam_select share.  K: states per score row; T: entries of the per-step buffers (which are
 // the context's, indexed by absolute time); rcx.b.passL is ignored: passL[q] (device) and first_of(q) (host) both give the
 // first position of pass q of the launch.
 template <class FirstOf>
@@ -132,11 +150,11 @@ int launch_beam_select(fv_ctx *ctx, int K, int beam, int T, const fvb::ResolveCt
     const int cand_cap = beam_cand_cap(ctx, K, beam), BP = fvb::beam_pitch(beam);
     fvb::SelArgs a;
     a.counters = ctx->d_counters.p; a.K = K; a.beam = beam; a.s = s;
-    a.no_wave = (ctx->opt_debug & 32768) ? 1 : 0;
-    a.eager = (ctx->opt_debug & 1048576) ? 1 : 0;             // FV_OPT_DEBUG bit 20: replay every duplicate step at once
-    a.quad_dirty = (ctx->opt_debug & 16777216) ? 1 : 0;
-    a.sb_rounds = (ctx->opt_debug & (1 << 22)) ? 2 : fvb::SEL_MAX_ROUNDS;
-    a.T = T; a.own_pred = (ctx->opt_debug & (1 << 7)) ? 1 : 0;
+    a.no_wave = (ctx->opt_debug & FV_DBG_SELECT_WHOLE_GROUP) ? 1 : 0;
+    a.eager = (ctx->opt_debug & FV_DBG_EAGER_REPLAY) ? 1 : 0;
+    a.quad_dirty = (ctx->opt_debug & FV_DBG_SELECT4_DIRTY) ? 1 : 0;
+    a.sb_rounds = (ctx->opt_debug & FV_DBG_SELECT_IN_MEMORY) ? 2 : fvb::SEL_MAX_ROUNDS;
+    a.T = T; a.own_pred = (ctx->opt_debug & FV_DBG_OWN_CUTS) ? 1 : 0;
     a.margin = ctx->opt_sel_margin; a.cand_cap = cand_cap;
     a.cand = ctx->d_cand.p; a.cand_count = ctx->d_cand_count.p; a.rc = rcx;
     a.rc.b.passL = passL;
@@ -151,7 +169,7 @@ int launch_beam_select(fv_ctx *ctx, int K, int beam, int T, const fvb::ResolveCt
     // steps >= 2 of a pass have a candidate list (the predictor needs two cut values)
     // K > 65536 (FV_OPT_DEBUG bit 22: any K): beyond the 64 rounds the register kernels hold, every selection runs in the
     // lean kernel — on the candidate list where there is one, otherwise over the K scores in memory
-    const bool many = K > fvb::SEL_MAX_ROUNDS * fvb::SEL_BLOCK || (ctx->opt_debug & (1 << 22));
+    const bool many = K > fvb::SEL_MAX_ROUNDS * fvb::SEL_BLOCK || (ctx->opt_debug & FV_DBG_SELECT_IN_MEMORY);
     const bool csr = rcx.csr.ptr != nullptr;        // a sparse-set model's decode: the instantiations that resolve on its rows
     fvb::SelKernel lean = (s >= 2 || many) ? fvb::sel_cand_kernel_for(K, cand_cap, listed, many, csr) : nullptr;
     const fvb::SelKernel kernel = lean ? lean : fvb::sel_kernel_for(K, listed, csr);
@@ -161,30 +179,55 @@ int launch_beam_select(fv_ctx *ctx, int K, int beam, int T, const fvb::ResolveCt
     return 0;
 }
 
-// T: length of the time axis (a batch: all sequences end to end); ng: stream groups the passes were ordered for;
-// nseq / seq_of: fv_decode_beam_batch — the tie gates are per sequence (seq_of: the device's time -> sequence map).
-int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t pass_off, int beam, int T, int ng,
-                        int nseq = 1, const int *seq_of = nullptr)
+// What the resolve code works on, over K states per score row and the passes whose first positions passL (device) lists.
+// model = false (fv_test_beam_select, which takes K as an argument and needs no model): what only the resolve code reads
+// stays null — no row of the hook is a dirty step.
+fvb::ResolveCtx resolve_ctx(const fv_ctx *ctx, int K, int beam, const int *passL, bool model)
 {
-    const int K = ctx->K, np = (int)passes.size();
-    if (np == 0) return 0;
-    FV_HIP(hipMemsetAsync(ctx->d_tie_count.p, 0, sizeof(unsigned int), ctx->stream));
-    const int cand_cap = beam_cand_cap(ctx, K, beam);
-    // passes arrive group by group (decode_beam_impl), longest first inside a group; their first positions are in
-    // d_passL[pass_off ..] in the same order
-    const int BP = fvb::beam_pitch(beam);
-    FV_HIP(hipMemsetAsync(ctx->d_doubt_count.p, 0, (size_t)T * sizeof(int), ctx->stream));      // doubtful-column lists of this generation
+    fvb::ResolveCtx r;
+    r.counters = ctx->d_counters.p; r.K = K; r.beam = beam; r.ld = beam_ld(K);
+    r.no_cut = (model && (ctx->opt_debug & FV_DBG_DECIDE_IN_FULL)) ? 1 : 0;
+    r.LA64R = model ? ctx->LA64R.p : nullptr; r.LB32T = model ? ctx->view.lb32 : nullptr; r.ob = model ? ctx->d_ob.p : nullptr;
+    r.bp = model ? ctx->d_bp.p : nullptr; r.doubt = model ? ctx->d_doubt.p : nullptr; r.doubt_count = ctx->d_doubt_count.p;
+    r.b.scores_all = ctx->d_scores.p; r.b.hval = ctx->d_hval.p; r.b.hstate = ctx->d_hstate.p;
+    r.b.cut = ctx->d_cut.p; r.b.passL = passL;
+    if (model && ctx->csr) { r.csr.ptr = ctx->CRptr.p; r.csr.col = ctx->CRcol.p; r.csr.log = ctx->CRlog.p; }
+    return r;
+}
+
+// The arguments of a heap_build_all launch but its ranges: the caller appends them to p[0 .. n).
+fvb::HeapAllArgs heap_all_args(const fv_ctx *ctx, int K, int beam, const int *gate, const int *seq_of)
+{
+    fvb::HeapAllArgs h;
+    h.scores_all = ctx->d_scores.p; h.slot_val = ctx->d_slot_val.p; h.slot_state = ctx->d_slot_state.p;
+    h.err_counter = ctx->d_counters.p + 5; h.gate = gate; h.seq_of = seq_of;
+    h.K = K; h.beam = beam; h.n = 0;
+    return h;
+}
+
+// One generation of beam passes in flight (same shape as run_generation_full): what its forward part and its pass ends
+// work on.  Buffers are indexed by absolute time j (passes of one generation cover disjoint time ranges): scores_all[j] =
+// the K scores after consuming ob[j] (j = L: the init row), set_*[j] = the members of the heap built from them
+// (order-free), slot_*[j] = its exact array layout (rebuilt after the lock-step loop).
+struct BeamGen {
+    const std::vector<fv::Pass> &passes;    // group by group (run_beam_generations), longest first inside a group;
+                                            // rcx.b.passL: their first positions on the device, in the same order
+    int beam, T, ng;                        // T: length of the time axis (a batch: all sequences end to end); ng: stream groups
+    int nseq; const int *seq_of;            // the tie gates are per sequence (seq_of: fv_decode_beam_batch's time -> sequence map on the device)
     fvb::ResolveCtx rcx;
-    rcx.counters = ctx->d_counters.p; rcx.K = K; rcx.beam = beam;
-    rcx.no_cut = (ctx->opt_debug & (1 << 23)) ? 1 : 0;
-    rcx.LA64R = ctx->LA64R.p; rcx.ld = beam_ld(K); rcx.LB32T = ctx->view.lb32; rcx.ob = ctx->d_ob.p;
-    rcx.bp = ctx->d_bp.p; rcx.doubt = ctx->d_doubt.p; rcx.doubt_count = ctx->d_doubt_count.p;
-    rcx.b.scores_all = ctx->d_scores.p; rcx.b.hval = ctx->d_hval.p; rcx.b.hstate = ctx->d_hstate.p;
-    rcx.b.cut = ctx->d_cut.p; rcx.b.passL = ctx->d_passL.p + pass_off;
-    if (ctx->csr) { rcx.csr.ptr = ctx->CRptr.p; rcx.csr.col = ctx->CRcol.p; rcx.csr.log = ctx->CRlog.p; }
+    std::vector<fvb::BeamEnd> ends;         // the passes as the pass-end kernels take them, sliced per launch
+};
+
+// Forward part of a generation: init rows, then every stream group's passes in lock-step (step, select).
+int beam_forward(fv_ctx *ctx, const BeamGen &gen)
+{
+    const std::vector<fv::Pass> &passes = gen.passes;
+    const int K = ctx->K, np = (int)passes.size(), beam = gen.beam, ng = gen.ng;
+    FV_HIP(hipMemsetAsync(ctx->d_tie_count.p, 0, sizeof(unsigned int), ctx->stream));
+    FV_HIP(hipMemsetAsync(ctx->d_doubt_count.p, 0, (size_t)gen.T * sizeof(int), ctx->stream));      // doubtful-column lists of this generation
     // members of the heaps of passes [first, first + count) at lock-step s: one launch
     auto select = [&](int first, int count, int s, hipStream_t st) -> int {
-        return launch_beam_select(ctx, K, beam, T, rcx, rcx.b.passL + first, count, s,
+        return launch_beam_select(ctx, K, beam, gen.T, gen.rcx, gen.rcx.b.passL + first, count, s,
                                   [&](int q) { return passes[first + q].L; }, st);
     };
     // init scores (the same rows the full variant starts from, FLASH_BS:407-427)
@@ -203,6 +246,7 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
     // the other groups fill the rest of the chip meanwhile.
     if (ng > 1) FV_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
     int rc = 0;
+    fvb::BeamStepArgs a = beam_step_args(ctx, beam, beam_cand_cap(ctx, K, beam));
     for (int g = 0, first = 0; g < ng; ++g) {
         const int gn = (np - g + ng - 1) / ng;                 // passes g, g + ng, ... of the sorted list
         hipStream_t st = g == 0 ? ctx->stream : ctx->aux[g - 1];
@@ -213,26 +257,10 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
         for (int s = 1; s <= maxlen; ++s) {
             while (active > 0 && passes[first + active - 1].R - passes[first + active - 1].L < s) --active;
             for (int base = 0; base < active; base += fvb::BEAM_CHUNK) {
-                fvb::BeamStepArgs a;
-                a.LA64R = ctx->LA64R.p; a.tie_count = ctx->d_tie_count.p; a.tie_list = ctx->d_tie_list.p;
-                a.tie_cap = (unsigned int)ctx->d_tie_list.n;
-                a.counters = ctx->d_counters.p;
-                a.K = K; a.ld = beam_ld(K); a.ldq = beam_ldq(K); a.beam = beam;
-                a.LAQ16R = ctx->LAQ16R.p; a.qpar = ctx->beam_q16_ready ? reinterpret_cast<const float *>(ctx->d_qaux.p + 2) : nullptr;
-                a.cand = ctx->d_cand.p; a.cand_count = ctx->d_cand_count.p; a.cand_cap = cand_cap;
                 a.n = std::min(fvb::BEAM_CHUNK, active - base);
                 for (int q = 0; q < a.n; ++q) {
                     const int j = passes[first + base + q].L + s;
-                    a.p[q].sval = ctx->d_hval.p + (size_t)(j - 1) * BP;
-                    a.p[q].sstate = ctx->d_hstate.p + (size_t)(j - 1) * BP;
-                    a.p[q].doubt = ctx->d_doubt.p + (size_t)j * fvb::DOUBT_CAP;
-                    a.p[q].doubt_count = ctx->d_doubt_count.p + j;
-                    a.p[q].scores = ctx->d_scores.p + (size_t)j * K;
-                    a.p[q].bp_row = ctx->d_bp.p + (size_t)j * K;
-                    a.p[q].tmp_row = ctx->view.lb32 + (size_t)ctx->h_ob[j] * K;
-                    a.p[q].j = j;
-                    a.p[q].cut = ctx->d_cut.p + (size_t)(j - 1) * fvb::CUT_W;
-                    a.p[q].dupwin = ctx->d_dupwin.p + j;
+                    a.p[q] = beam_step_job(ctx, beam, j, j - 1, ctx->h_ob[j]);
                 }
                 if ((rc = launch_beam_step(ctx, a, st))) return rc;
                 ctx->stats.step_launches += 1;
@@ -246,20 +274,23 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
         }
         first += gn;
     }
-    // Pass ends.  First attempt on the provisional back-pointers (beam_end_backtrack); only the whole-sequence pass
-    // needs a layout for that — its last heap's.  The exact layouts of every step's heap and the tie fix-up are queued
-    // behind it but run only if the walk met a tied cell (FV_OPT_DEBUG bit 19: always).
-    const bool lazy = !(ctx->opt_debug & 524288);
-    FV_HIP(hipMemsetAsync(ctx->d_needfull.p, 0, (size_t)nseq * sizeof(int), ctx->stream));
+    return 0;
+}
+
+// Pass ends of a generation.  First attempt on the provisional back-pointers (beam_end_backtrack); only the
+// whole-sequence pass needs a layout for that — its last heap's.  The exact layouts of every step's heap and the tie
+// fix-up are queued behind it but run only if the walk met a tied cell (FV_OPT_DEBUG bit 19: always).
+int beam_pass_ends(fv_ctx *ctx, const BeamGen &gen)
+{
+    const int K = ctx->K, np = (int)gen.ends.size(), beam = gen.beam;
+    int *const needfull = ctx->d_needfull.p;
+    FV_HIP(hipMemsetAsync(needfull, 0, (size_t)gen.nseq * sizeof(int), ctx->stream));
     auto layouts = [&](bool last_only, const int *gate) -> int {
         for (int base = 0; base < np; base += fvb::HEAP_CHUNK) {
-            fvb::HeapAllArgs h;
-            h.scores_all = ctx->d_scores.p; h.slot_val = ctx->d_slot_val.p; h.slot_state = ctx->d_slot_state.p;
-            h.err_counter = ctx->d_counters.p + 5; h.gate = gate; h.seq_of = seq_of;
-            h.K = K; h.beam = beam; h.n = 0;
+            fvb::HeapAllArgs h = heap_all_args(ctx, K, beam, gate, gen.seq_of);
             int longest = 0;
             for (int q = 0; q < std::min(fvb::HEAP_CHUNK, np - base); ++q) {
-                const fv::Pass &p = passes[base + q];
+                const fvb::BeamEnd &p = gen.ends[(size_t)(base + q)];
                 if (last_only && !p.whole) continue;
                 h.p[h.n++] = fvb::HeapRange{ last_only ? p.R : p.L, p.R };
                 longest = std::max(longest, last_only ? 1 : p.R - p.L + 1);
@@ -274,9 +305,8 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
         for (int base = 0; base < np; base += fvb::BEAM_CHUNK) {
             fvb::BeamEndArgs e;
             e.K = K; e.beam = beam; e.n = std::min(fvb::BEAM_CHUNK, np - base);
-            e.lazy = lazy_walk; e.flag = ctx->d_needfull.p; e.restarts = ctx->d_counters.p + fvk::BT_COUNTER;
-            for (int q = 0; q < e.n; ++q)
-                e.p[q] = fvb::BeamEnd{ passes[base + q].L, passes[base + q].R, passes[base + q].whole ? 1 : 0, passes[base + q].seq };
+            e.lazy = lazy_walk; e.flag = needfull; e.restarts = ctx->d_counters.p + fvk::BT_COUNTER;
+            std::copy_n(gen.ends.data() + base, e.n, e.p);
             hipLaunchKernelGGL(fvb::beam_end_backtrack, dim3(e.n), dim3(64), 0, ctx->stream, e, ctx->d_slot_val.p,
                                ctx->d_slot_state.p, ctx->d_hstate.p, ctx->d_cut.p, ctx->d_bp.p, ctx->d_ans.p, ctx->d_score.p);
             FV_HIP(hipGetLastError());
@@ -288,42 +318,36 @@ int run_generation_beam(fv_ctx *ctx, const std::vector<fv::Pass> &passes, size_t
     auto resolve = [&](int mode, const int *gate) -> int {
         for (int base = 0; base < np; base += fvb::BEAM_CHUNK) {
             fvb::ResolveArgs r;
-            r.rc = rcx; r.mode = mode; r.gate = gate; r.ans = ctx->d_ans.p;
+            r.rc = gen.rcx; r.mode = mode; r.gate = gate; r.ans = ctx->d_ans.p;
             r.n = std::min(fvb::BEAM_CHUNK, np - base);
-            for (int q = 0; q < r.n; ++q)
-                r.p[q] = fvb::BeamEnd{ passes[base + q].L, passes[base + q].R, passes[base + q].whole ? 1 : 0, passes[base + q].seq };
+            std::copy_n(gen.ends.data() + base, r.n, r.p);
             hipLaunchKernelGGL(ctx->csr ? fvb::beam_resolve<true> : fvb::beam_resolve<false>, dim3(r.n), dim3(fvb::RESOLVE_BLOCK),
                                fvb::heap_lds(beam), ctx->stream, r);
             FV_HIP(hipGetLastError());
         }
         return 0;
     };
+    int rc = 0;
     if ((rc = resolve(0, nullptr))) return rc;
-    if (lazy) {
+    if (!(ctx->opt_debug & FV_DBG_ALL_LAYOUTS)) {
         if ((rc = layouts(true, nullptr))) return rc;
         if ((rc = ends(1))) return rc;
-    } else if (seq_of) {
-        FV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctx->d_needfull.p), 1, (size_t)nseq, ctx->stream));    // every flag up
     } else {
-        int one = 1;
-        FV_HIP(hipMemcpyAsync(ctx->d_needfull.p, &one, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        FV_HIP(hipStreamSynchronize(ctx->stream));       // (`one` is a local; this is the experiment path)
+        FV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(needfull), 1, (size_t)gen.nseq, ctx->stream));    // every flag up
     }
-    if ((rc = resolve(1, ctx->d_needfull.p))) return rc;
-    if ((rc = layouts(false, ctx->d_needfull.p))) return rc;
+    if ((rc = resolve(1, needfull))) return rc;
+    if ((rc = layouts(false, needfull))) return rc;
     {
         fvb::FixArgs f;
         f.LA64R = ctx->LA64R.p; f.LB32T = ctx->view.lb32; f.ob = ctx->d_ob.p;
         f.tie_count = ctx->d_tie_count.p; f.tie_list = ctx->d_tie_list.p; f.tie_cap = (unsigned int)ctx->d_tie_list.n;
         f.slot_val = ctx->d_slot_val.p; f.slot_state = ctx->d_slot_state.p; f.bp = ctx->d_bp.p;
-        f.K = K; f.ld = beam_ld(K); f.beam = beam; f.total = ctx->d_counters.p + 6; f.gate = ctx->d_needfull.p;
-        f.seq_of = seq_of; f.csr = rcx.csr;
+        f.K = K; f.ld = beam_ld(K); f.beam = beam; f.total = ctx->d_counters.p + 6; f.gate = needfull;
+        f.seq_of = gen.seq_of; f.csr = gen.rcx.csr;
         hipLaunchKernelGGL(ctx->csr ? fvb::tie_fixup<true> : fvb::tie_fixup<false>, dim3(512), dim3(256), 0, ctx->stream, f);
         FV_HIP(hipGetLastError());
     }
-    if ((rc = ends(0))) return rc;
-    (void)T;
-    return 0;
+    return ends(0);
 }
 
 }  // namespace
@@ -349,8 +373,8 @@ int beam_admit_k(int K, int beam)
 {
     // beam > K reads uninitialised heap slots in the reference
     if (beam < 2 || beam > K) return FV_ERR_ARG;
-    if (fvb::beam_step_lds(beam) > 150 * 1024 || fvb::beam_step_q16_lds(beam) > 150 * 1024 ||
-        fvb::heap_lds(beam) > 150 * 1024) return FV_ERR_UNSUPPORTED;
+    if (fvb::beam_step_lds(beam) > fvk::BEAM_LDS_LIMIT || fvb::beam_step_q16_lds(beam) > fvk::BEAM_LDS_LIMIT ||
+        fvb::heap_lds(beam) > fvk::BEAM_LDS_LIMIT) return FV_ERR_UNSUPPORTED;
     return 0;
 }
 int beam_admit(fv_ctx *ctx, int beam) { return beam_admit_k(ctx->K, beam); }
@@ -423,12 +447,13 @@ int run_beam_generations(fv_ctx *ctx, std::vector<std::vector<fv::Pass>> &gens, 
     // The passes of a generation run in lock-step, longest first (the active ones are a prefix); the kernels find a
     // pass's rows from its first position, so the whole plan's pass lists go to the device once, before the clock starts.
     std::vector<size_t> pass_off(gens.size(), 0);
+    std::vector<int> groups(gens.size(), 1);         // stream groups of every generation
     ctx->h_passL.clear();
     for (size_t g = 0; g < gens.size(); ++g) {
         std::stable_sort(gens[g].begin(), gens[g].end(),
                          [](const fv::Pass &a, const fv::Pass &b) { return a.R - a.L > b.R - b.L; });
         {   // group-major: the passes of stream group q (i % ng == q), longest first, then those of group q + 1
-            const int np = (int)gens[g].size(), ng = gen_groups(ctx, g, np, beam_width, nseq);
+            const int np = (int)gens[g].size(), ng = groups[g] = gen_groups(ctx, g, np, beam_width, nseq);
             std::vector<fv::Pass> byg;
             byg.reserve(gens[g].size());
             for (int q = 0; q < ng; ++q)
@@ -448,10 +473,13 @@ int run_beam_generations(fv_ctx *ctx, std::vector<std::vector<fv::Pass>> &gens, 
         // Work queued on the auxiliary streams slows every dispatch of the main one while it waits there for its fork
         // event (the command processor keeps re-examining the blocked queues: +2 us per launch, 1 ms over the
         // whole-sequence pass of cfg4).  The host therefore does not run ahead of a serial generation into a forked one.
-        if (g > 0 && gen_groups(ctx, g, (int)gens[g].size(), beam_width, nseq) > 1 &&
-            gen_groups(ctx, g - 1, (int)gens[g - 1].size(), beam_width, nseq) == 1)
-            FV_HIP(hipStreamSynchronize(ctx->stream));
-        if ((rc = run_generation_beam(ctx, gens[g], pass_off[g], beam_width, T, gen_groups(ctx, g, (int)gens[g].size(), beam_width, nseq), nseq, seq_of))) return rc;
+        if (g > 0 && groups[g] > 1 && groups[g - 1] == 1) FV_HIP(hipStreamSynchronize(ctx->stream));
+        if (!gens[g].empty()) {
+            BeamGen gen{ gens[g], beam_width, T, groups[g], nseq, seq_of,
+                         resolve_ctx(ctx, ctx->K, beam_width, ctx->d_passL.p + pass_off[g], true), {} };
+            for (const fv::Pass &p : gens[g]) gen.ends.push_back(fvb::BeamEnd{ p.L, p.R, p.whole ? 1 : 0, p.seq });
+            if ((rc = beam_forward(ctx, gen)) || (rc = beam_pass_ends(ctx, gen))) return rc;
+        }
         if (g == 0) { FV_HIP(hipEventRecord(ctx->ev_top, ctx->stream)); FV_HIP(hipEventRecord(ctx->ev_s1, ctx->stream)); }
     }
     return 0;
@@ -465,6 +493,30 @@ void start_beam_stats(fv_ctx *ctx, const fv::Plan &plan, int beam_width)
     else ctx->start_stats(FV_KERNEL_F64_STREAM, plan.generations(), (long long)beam_width * ctx->K * 8, 0.0);
 }
 
+// What fv_decode_beam, fv_decode_beam_batch and fv_test_beam_forward do once admitted and planned: workspace, tables,
+// statistics, prologue, generations, epilogue.  offsets: the sequences laid end to end — nseq + 1 entries of a batch
+// (whose request is checked against the free memory first, whose tie gates are per sequence), { 0, T } and nseq = 0 of a
+// single sequence.  after_begin (may be empty): what the caller uploads between the prologue and the generations.
+// record: a test hook's call, see FvTestRecording.
+int run_beam_decode(fv_ctx *ctx, const int *ob, const fv::Plan &plan, std::vector<std::vector<fv::Pass>> &gens,
+                    const long long *offsets, int nseq, int beam_width, int *path_out, float *score_out, int *status_out,
+                    clk::time_point t0, const std::function<int()> &after_begin, bool record)
+{
+    const int T = (int)offsets[std::max(nseq, 1)];
+    int rc = 0;
+    FV_HIP(hipSetDevice(ctx->device));
+    if ((rc = beam_workspace(ctx, T, beam_width, nseq))) return rc;
+    if ((rc = beam_tables(ctx))) return rc;
+    start_beam_stats(ctx, plan, beam_width);
+
+    if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
+    if (after_begin && (rc = after_begin())) return rc;
+    FvTestRecording recording(ctx, record);
+    if ((rc = run_beam_generations(ctx, gens, beam_width, T, std::max(nseq, 1), nseq ? ctx->d_seqof.p : nullptr))) return rc;
+    ctx->close_stats((long long)ctx->K * beam_width, 0);
+    return fvi::finish_decode(ctx, plan, offsets, std::max(nseq, 1), path_out, score_out, status_out, t0, 0, true);
+}
+
 int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_width, int mode, int *path_out, float *score_out)
 {
     if (!ctx || !path_out || T < 2 || n_split < 1) return FV_ERR_ARG;
@@ -474,19 +526,11 @@ int decode_beam_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int beam_wi
     if ((rc = beam_admit(ctx, beam_width))) return rc;
     for (int j = 0; j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
     auto t0 = clk::now();
-    FV_HIP(hipSetDevice(ctx->device));
     fv::Plan plan;
     if ((rc = fv::build_plan(T, n_split, mode, ctx->nranks, plan))) return rc;
     std::vector<std::vector<fv::Pass>> gens = fvi::deal_passes(ctx, plan);
-    if ((rc = beam_workspace(ctx, T, beam_width, 0))) return rc;
-    if ((rc = beam_tables(ctx))) return rc;
-    start_beam_stats(ctx, plan, beam_width);
-
-    if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
-    if ((rc = run_beam_generations(ctx, gens, beam_width, T, 1, nullptr))) return rc;
-    ctx->close_stats((long long)ctx->K * beam_width, 0);
     const long long whole[2] = { 0, T };
-    return fvi::finish_decode(ctx, plan, whole, 1, path_out, score_out, nullptr, t0, 0, true);
+    return run_beam_decode(ctx, ob, plan, gens, whole, 0, beam_width, path_out, score_out, nullptr, t0, nullptr, false);
 }
 
 // fv_decode_beam_batch: the forest plan (fv::build_forest, as fv_decode_full_batch) run by the beam generation driver.
@@ -504,19 +548,14 @@ int decode_beam_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets,
     fv::Plan plan;
     if ((rc = fvi::batch_plan(ctx, who, lengths, n_split, mode, plan))) return rc;
     std::vector<std::vector<fv::Pass>> gens = fvi::deal_passes(ctx, plan);
-    FV_HIP(hipSetDevice(ctx->device));
-    if ((rc = beam_workspace(ctx, sumT, beam_width, nseq))) return rc;           // (checks the whole working set first)
-    if ((rc = beam_tables(ctx))) return rc;
-    start_beam_stats(ctx, plan, beam_width);
-
-    if ((rc = fvi::begin_decode(ctx, ob, sumT))) return rc;
     // time -> sequence: how heap_build_all and tie_fixup find the gate of a step (4 bytes per observation)
-    ctx->h_seqof.resize((size_t)sumT);
-    for (int s = 0; s < nseq; ++s) std::fill(ctx->h_seqof.begin() + offsets[s], ctx->h_seqof.begin() + offsets[s + 1], s);
-    FV_HIP(hipMemcpyAsync(ctx->d_seqof.p, ctx->h_seqof.data(), (size_t)sumT * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = run_beam_generations(ctx, gens, beam_width, sumT, nseq, ctx->d_seqof.p))) return rc;
-    ctx->close_stats((long long)ctx->K * beam_width, 0);
-    return fvi::finish_decode(ctx, plan, offsets, nseq, path_out, score_out, status_out, t0, 0, true);
+    auto upload_seq_of = [&]() -> int {
+        ctx->h_seqof.resize((size_t)sumT);
+        for (int s = 0; s < nseq; ++s) std::fill(ctx->h_seqof.begin() + offsets[s], ctx->h_seqof.begin() + offsets[s + 1], s);
+        FV_HIP(hipMemcpyAsync(ctx->d_seqof.p, ctx->h_seqof.data(), (size_t)sumT * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        return 0;
+    };
+    return run_beam_decode(ctx, ob, plan, gens, offsets, nseq, beam_width, path_out, score_out, status_out, t0, upload_seq_of, false);
 }
 }  // namespace
 
@@ -571,22 +610,17 @@ int test_beam_step_impl(fv_ctx *ctx, int beam, const fv_test_beam_set *sets, int
     }
     FV_HIP(hipSetDevice(ctx->device));
     if ((rc = beam_tables(ctx))) return rc;
-    FV_HIP(ctx->d_hval.ensure((size_t)nsets * BP));
-    FV_HIP(ctx->d_hstate.ensure((size_t)nsets * BP));
-    FV_HIP(ctx->d_cut.ensure((size_t)nsets * fvb::CUT_W));
-    FV_HIP(ctx->d_scores.ensure((size_t)nsets * K));
-    FV_HIP(ctx->d_bp.ensure((size_t)nsets * K));
-    FV_HIP(ctx->d_dupwin.ensure(nsets));
-    FV_HIP(ctx->d_doubt.ensure((size_t)nsets * fvb::DOUBT_CAP));
-    FV_HIP(ctx->d_doubt_count.ensure(nsets));
-    FV_HIP(ctx->d_tie_list.ensure((size_t)nsets * K));
-    FV_HIP(ctx->d_tie_count.ensure(4));
-    FV_HIP(ctx->d_counters.ensure(FV_NCOUNTERS));
-    FV_HIP(ctx->d_cand_count.ensure(nsets));
-    if (cand_cap) FV_HIP(ctx->d_cand.ensure((size_t)nsets * cand_cap));
+    const size_t n = (size_t)nsets;
+    fvi::Wants w;
+    w.add(ctx->d_hval, n * BP); w.add(ctx->d_hstate, n * BP); w.add(ctx->d_cut, n * fvb::CUT_W);
+    w.add(ctx->d_scores, n * K); w.add(ctx->d_bp, n * K); w.add(ctx->d_dupwin, n);
+    w.add(ctx->d_doubt, n * fvb::DOUBT_CAP); w.add(ctx->d_doubt_count, n);
+    w.add(ctx->d_tie_list, n * K); w.add(ctx->d_tie_count, (size_t)4);
+    w.add(ctx->d_counters, (size_t)FV_NCOUNTERS); w.add(ctx->d_cand_count, n);
+    if (cand_cap) w.add(ctx->d_cand, n * cand_cap);
+    if (ctx->csr) { w.add(ctx->d_csr_acc, n * K); w.add(ctx->d_csr_tie, n * K); }
+    if ((rc = fvi::grant(ctx, w, false))) return rc;
     if (ctx->csr) {
-        FV_HIP(ctx->d_csr_acc.ensure((size_t)nsets * K));
-        FV_HIP(ctx->d_csr_tie.ensure((size_t)nsets * K));
         FV_HIP(hipMemsetAsync(ctx->d_csr_acc.p, 0, (size_t)nsets * K * sizeof(unsigned long long), ctx->stream));
         FV_HIP(hipMemsetAsync(ctx->d_csr_tie.p, 0, (size_t)nsets * K * sizeof(unsigned int), ctx->stream));
     }
@@ -598,29 +632,10 @@ int test_beam_step_impl(fv_ctx *ctx, int beam, const fv_test_beam_set *sets, int
     FV_HIP(hipMemsetAsync(ctx->d_cand_count.p, 0, (size_t)nsets * sizeof(int), ctx->stream));
     FV_HIP(hipMemsetAsync(ctx->d_tie_count.p, 0, sizeof(unsigned int), ctx->stream));
     FV_HIP(hipMemsetAsync(ctx->d_counters.p, 0, FV_NCOUNTERS * sizeof(unsigned long long), ctx->stream));
-    fvb::BeamStepArgs a;
-    a.LA64R = ctx->LA64R.p; a.tie_count = ctx->d_tie_count.p; a.tie_list = ctx->d_tie_list.p;
-    a.tie_cap = (unsigned int)ctx->d_tie_list.n;
-    a.counters = ctx->d_counters.p;
-    a.K = K; a.ld = beam_ld(K); a.ldq = beam_ldq(K); a.beam = beam;
-    a.LAQ16R = ctx->LAQ16R.p; a.qpar = ctx->beam_q16_ready ? reinterpret_cast<const float *>(ctx->d_qaux.p + 2) : nullptr;
-    a.cand = ctx->d_cand.p; a.cand_count = ctx->d_cand_count.p; a.cand_cap = cand_cap;
+    fvb::BeamStepArgs a = beam_step_args(ctx, beam, cand_cap);
     a.n = nsets;
-    for (int q = 0; q < nsets; ++q) {
-        a.p[q].sval = ctx->d_hval.p + (size_t)q * BP;
-        a.p[q].sstate = ctx->d_hstate.p + (size_t)q * BP;
-        a.p[q].doubt = ctx->d_doubt.p + (size_t)q * fvb::DOUBT_CAP;
-        a.p[q].doubt_count = ctx->d_doubt_count.p + q;
-        a.p[q].scores = ctx->d_scores.p + (size_t)q * K;
-        a.p[q].bp_row = ctx->d_bp.p + (size_t)q * K;
-        a.p[q].tmp_row = ctx->LB32T.p + (size_t)sym[q] * K;
-        a.p[q].j = q;
-        a.p[q].cut = ctx->d_cut.p + (size_t)q * fvb::CUT_W;
-        a.p[q].dupwin = ctx->d_dupwin.p + q;
-    }
-    struct Restore { fv_ctx *c; ~Restore() { c->test_record = false; } } restore{ ctx };
-    ctx->test_record = true;
-    ctx->test_variants = 0;
+    for (int q = 0; q < nsets; ++q) a.p[q] = beam_step_job(ctx, beam, q, q, sym[q]);      // (the view is the model's log B)
+    FvTestRecording recording(ctx);
     if ((rc = launch_beam_step(ctx, a, ctx->stream))) return rc;
     unsigned int nties = 0;
     FV_HIP(hipMemcpyAsync(scores_out, ctx->d_scores.p, (size_t)nsets * K * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -684,16 +699,14 @@ int test_beam_select_impl(fv_ctx *ctx, int K, int beam, int s, const fv_test_sel
     }
     FV_HIP(hipSetDevice(ctx->device));
     auto slot = [](int q) { return (size_t)(3 * q + 2); };
-    FV_HIP(ctx->d_scores.ensure((size_t)Tn * K));
-    FV_HIP(ctx->d_hval.ensure((size_t)Tn * BP));
-    FV_HIP(ctx->d_hstate.ensure((size_t)Tn * BP));
-    FV_HIP(ctx->d_cut.ensure((size_t)Tn * fvb::CUT_W));
-    FV_HIP(ctx->d_doubt_count.ensure(Tn));
-    FV_HIP(ctx->d_cand_count.ensure(Tn));
-    if (cap) FV_HIP(ctx->d_cand.ensure((size_t)Tn * cap));
-    FV_HIP(ctx->d_counters.ensure(FV_NCOUNTERS));
-    FV_HIP(ctx->d_passL.ensure(nsets));
-    if (want_layout) { FV_HIP(ctx->d_slot_val.ensure((size_t)Tn * beam)); FV_HIP(ctx->d_slot_state.ensure((size_t)Tn * beam)); }
+    const size_t n = (size_t)Tn;
+    fvi::Wants w;
+    w.add(ctx->d_scores, n * K); w.add(ctx->d_hval, n * BP); w.add(ctx->d_hstate, n * BP); w.add(ctx->d_cut, n * fvb::CUT_W);
+    w.add(ctx->d_doubt_count, n); w.add(ctx->d_cand_count, n);
+    if (cap) w.add(ctx->d_cand, n * cap);
+    w.add(ctx->d_counters, (size_t)FV_NCOUNTERS); w.add(ctx->d_passL, (size_t)nsets);
+    if (want_layout) { w.add(ctx->d_slot_val, n * beam); w.add(ctx->d_slot_state, n * beam); }
+    if ((rc = fvi::grant(ctx, w, false))) return rc;
     std::vector<float> cut((size_t)Tn * fvb::CUT_W, std::nanf(""));
     std::vector<int> counts((size_t)Tn, 0), first((size_t)nsets);
     static_assert(sizeof(fv_test_cand) == sizeof(fvb::HNode), "fv_test_cand mirrors HNode");
@@ -721,22 +734,13 @@ int test_beam_select_impl(fv_ctx *ctx, int K, int beam, int s, const fv_test_sel
     FV_HIP(hipMemsetAsync(ctx->d_hstate.p, 0xFF, (size_t)Tn * BP * sizeof(int), ctx->stream));
     FV_HIP(hipMemsetAsync(ctx->d_doubt_count.p, 0, (size_t)Tn * sizeof(int), ctx->stream));
     FV_HIP(hipMemsetAsync(ctx->d_counters.p, 0, FV_NCOUNTERS * sizeof(unsigned long long), ctx->stream));
-    fvb::ResolveCtx rcx;        // what only the resolve code reads stays null: no row is a dirty step
-    rcx.counters = ctx->d_counters.p; rcx.K = K; rcx.beam = beam; rcx.no_cut = 0;
-    rcx.LA64R = nullptr; rcx.ld = beam_ld(K); rcx.LB32T = nullptr; rcx.ob = nullptr; rcx.bp = nullptr;
-    rcx.doubt = nullptr; rcx.doubt_count = ctx->d_doubt_count.p;
-    rcx.b.scores_all = ctx->d_scores.p; rcx.b.hval = ctx->d_hval.p; rcx.b.hstate = ctx->d_hstate.p;
-    rcx.b.cut = ctx->d_cut.p; rcx.b.passL = ctx->d_passL.p;
-    struct Restore { fv_ctx *c; ~Restore() { c->test_record = false; } } restore{ ctx };
-    ctx->test_record = true;
-    ctx->test_selects = 0;
+    const fvb::ResolveCtx rcx = resolve_ctx(ctx, K, beam, ctx->d_passL.p, false);
+    FvTestRecording recording(ctx);
     if ((rc = launch_beam_select(ctx, K, beam, Tn, rcx, ctx->d_passL.p, nsets, s, [&](int q) { return first[(size_t)q]; }, ctx->stream)))
         return rc;
     if (want_layout) {
-        fvb::HeapAllArgs h;
-        h.scores_all = ctx->d_scores.p; h.slot_val = ctx->d_slot_val.p; h.slot_state = ctx->d_slot_state.p;
-        h.err_counter = ctx->d_counters.p + 5; h.gate = nullptr; h.seq_of = nullptr;
-        h.K = K; h.beam = beam; h.n = nsets;
+        fvb::HeapAllArgs h = heap_all_args(ctx, K, beam, nullptr, nullptr);
+        h.n = nsets;
         for (int q = 0; q < nsets; ++q) h.p[q] = fvb::HeapRange{ (int)slot(q), (int)slot(q) };
         ctx->test_selects |= FV_TS_HEAP_BUILD_ALL;
         hipLaunchKernelGGL(fvb::heap_build_all, dim3(1, nsets), dim3(128), fvb::heap_lds(beam), ctx->stream, h);
@@ -815,31 +819,22 @@ int test_beam_forward_impl(fv_ctx *ctx, const int *ob, int T, int beam, const fv
         }
     }
     auto t0 = clk::now();
-    FV_HIP(hipSetDevice(ctx->device));
     fv::Plan plan;                   // one generation; no segments: the epilogue gathers nothing
     plan.gen_begin = { 0, np };
-    if ((rc = beam_workspace(ctx, T, beam, 0))) return rc;
-    if ((rc = beam_tables(ctx))) return rc;
-    start_beam_stats(ctx, plan, beam);
-    if ((rc = fvi::begin_decode(ctx, ob, T))) return rc;
-    if (!whole) {
-        // what the init rows (ans[L-1]) and the pass ends (ans[R]) read; `ans` lives until the epilogue has synchronised
+    // what the init rows (ans[L-1]) and the pass ends (ans[R]) read; `ans` lives until the epilogue has synchronised
+    auto upload_ans = [&]() -> int {
+        if (whole) return 0;
         for (int q = 0; q < np; ++q) {
             ans[(size_t)tp[q].R] = tp[q].end_state;
             if (tp[q].L > 0) ans[(size_t)tp[q].L - 1] = tp[q].init_state;
         }
         FV_HIP(hipMemcpyAsync(ctx->d_ans.p, ans.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    }
-    struct Restore { fv_ctx *c; ~Restore() { c->test_record = false; } } restore{ ctx };
-    ctx->test_record = true;
-    ctx->test_variants = 0;
-    ctx->test_selects = 0;
-    if ((rc = run_beam_generations(ctx, gens, beam, T, 1, nullptr))) return rc;
-    ctx->close_stats((long long)K * beam, 0);
+        return 0;
+    };
     std::vector<int> path((size_t)T);
     float score = 0.0f;
     const long long seq[2] = { 0, T };
-    if ((rc = fvi::finish_decode(ctx, plan, seq, 1, path.data(), &score, nullptr, t0, 0, true)) < 0) return rc;
+    if ((rc = run_beam_decode(ctx, ob, plan, gens, seq, 0, beam, path.data(), &score, nullptr, t0, upload_ans, true)) < 0) return rc;
     // the generation has finished (finish_decode synchronised): plain copies of the passes' rows
     const size_t BP = (size_t)fvb::beam_pitch(beam), B = (size_t)beam, Ks = (size_t)K;
     auto rows = [&](auto *dst, const auto *src, size_t first, size_t n, size_t width) -> hipError_t {

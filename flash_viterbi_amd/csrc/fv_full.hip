@@ -115,7 +115,7 @@ template <int NB>
 int slab_rows(const fv_ctx *ctx)
 {
     int slab = ctx->nrows;
-    if (ctx->opt_debug & (1 << 21)) slab = std::max(64, (ctx->nrows / 3 + 63) / 64 * 64);
+    if (ctx->opt_debug & FV_DBG_SLABS) slab = std::max(64, (ctx->nrows / 3 + 63) / 64 * 64);
     while (slab > 64 && fvk::step_lds_bytes<NB>(slab) > (size_t)fvk::LDS_LIMIT) slab = (slab / 2 + 63) / 64 * 64;
     return slab;
 }
@@ -128,7 +128,7 @@ void fill_step_args(const fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot
     a.qscale = ctx->qscale;
     a.LA64 = ctx->LA64.p;
     a.counters = ctx->d_counters.p;
-    a.reverse = (ctx->opt_debug & 2) ? 0 : ln.reverse;
+    a.reverse = (ctx->opt_debug & FV_DBG_NO_REVERSE) ? 0 : ln.reverse;
     a.debug = ctx->opt_debug;
     a.row_lo = 0; a.srows = ctx->nrows; a.merge = 0;
 }
@@ -167,7 +167,7 @@ int launch_step_nb(fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot *slots
         return launch_variant<TA, NB, U_DB64, true>(ctx, ln, a, lds);
     } else if constexpr (std::is_same<TA, float>::value) {
         if constexpr (NB <= 2) {
-            if (nj_max <= U_UP && (ctx->opt_debug & 4)) return launch_variant<TA, NB, U_UP, false>(ctx, ln, a, lds);
+            if (nj_max <= U_UP && (ctx->opt_debug & FV_DBG_ALT_LOADS)) return launch_variant<TA, NB, U_UP, false>(ctx, ln, a, lds);
         }
         return launch_variant<TA, NB, U_DB32, true>(ctx, ln, a, lds);
     } else {
@@ -177,7 +177,7 @@ int launch_step_nb(fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot *slots
         // double-buffered one (46 VGPRs, two workgroups per CU) keeps the grid in one round
         // (K=5632: 18.3 vs 25.3 us/step, K=8192: 25.8 vs 39.8).
         if constexpr (NB <= 2) {
-            if (nj_max <= U_UP && a.ntiles <= ctx->num_cus && !(ctx->opt_debug & 4)) return launch_variant<TA, NB, U_UP, false>(ctx, ln, a, lds);
+            if (nj_max <= U_UP && a.ntiles <= ctx->num_cus && !(ctx->opt_debug & FV_DBG_ALT_LOADS)) return launch_variant<TA, NB, U_UP, false>(ctx, ln, a, lds);
         }
         // (8-wave workgroups for the batched launches, as the packed 16-bit kernel uses, were measured: 2.14 vs 2.10 ms of
         // right-hand passes at cfg2, 65.6 vs 62.7 ms at cfg3 — the f32 sweep needs its four waves per SIMD)
@@ -283,13 +283,13 @@ int launch_u16_nb(fv_ctx *ctx, const StepLaunch &ln, const LaunchCodes &lc, cons
     const int nq = ctx->nrows / 32;
     // 8 waves per workgroup (FV_OPT_DEBUG bit 13: 16): everything outside the sweep — quantisation, reductions, refine —
     // is executed by every wave, so fewer, longer waves spend fewer issue slots on it
-    if (ctx->opt_debug & 8192) {
-        if (a.ntiles <= ctx->num_cus && (nq + 15) / 16 <= 8 && !(ctx->opt_debug & 4)) return launch_u16_variant<NB, 8, false, 16>(ctx, ln, a);
+    if (ctx->opt_debug & FV_DBG_U16_W16) {
+        if (a.ntiles <= ctx->num_cus && (nq + 15) / 16 <= 8 && !(ctx->opt_debug & FV_DBG_ALT_LOADS)) return launch_u16_variant<NB, 8, false, 16>(ctx, ln, a);
         return launch_u16_variant<NB, U_DB16, true, 16>(ctx, ln, a);
     }
     // (forked batches: the double-buffered form, 81 VGPRs at NB = 4 — three 8-wave workgroups of three streams share a CU;
     // the whole-tile form's 137 would leave room for one)
-    if (a.ntiles <= ctx->num_cus && (nq + 7) / 8 <= 16 && !(ctx->opt_debug & 4) && !ln.forked) return launch_u16_variant<NB, 16, false, 8>(ctx, ln, a);
+    if (a.ntiles <= ctx->num_cus && (nq + 7) / 8 <= 16 && !(ctx->opt_debug & FV_DBG_ALT_LOADS) && !ln.forked) return launch_u16_variant<NB, 16, false, 8>(ctx, ln, a);
     return launch_u16_variant<NB, U_DB16, true, 8>(ctx, ln, a);
 }
 
@@ -352,7 +352,7 @@ int launch_step_kernel(fv_ctx *ctx, const StepLaunch &ln, const fvk::TaskSlot *s
     // 10.4 vs 14.2 at T=4096 where its window is the narrower one), for models whose float32 rows do not fit LDS and for
     // forked batches; the f32 filter for the other batched launches, where the 16-bit kernel's per-task prologue (row
     // maximum, quantisation) costs what its cheaper sweep saves.  FV_OPT_DEBUG bit 14: packed 16-bit for every launch.
-    const bool packed = ln.kernel == FV_KERNEL_U16_REFINE && (nb <= 1 || !ctx->full_ok || (ctx->opt_debug & 16384) || ln.forked);
+    const bool packed = ln.kernel == FV_KERNEL_U16_REFINE && (nb <= 1 || !ctx->full_ok || (ctx->opt_debug & FV_DBG_U16_BATCHED) || ln.forked);
     bool all_in = packed && ctx->row_codes != 0, all_out = all_in;
     int rout[fvk::MAX_BATCH];
     for (int q = 0; q < nb; ++q) {
@@ -461,7 +461,7 @@ GenShape generation_shape(const fv_ctx *ctx, int kernel, int maxlen, int nfork, 
     const bool walk = kernel == FV_KERNEL_SPARSE_Q16 || kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64;
     GenShape g{ std::max(1, std::min(ctx->opt_max_batch, slabbed ? 4 : max_batch_for(ctx->nrows, !ctx->full_ok))), 1 };
     if (kernel == FV_KERNEL_SPARSE_CSR || kernel == FV_KERNEL_CSR_F64) g.cap = ctx->opt_max_batch;     // (rows that do not fit LDS are read from memory)
-    if (may_fork && !(ctx->opt_debug & 262144) && nfork > FORK_CAP && ((kernel == FV_KERNEL_U16_REFINE && ctx->u16_ok) || (walk && maxlen >= 64))) {
+    if (may_fork && !(ctx->opt_debug & FV_DBG_FULL_ONE_STREAM) && nfork > FORK_CAP && ((kernel == FV_KERNEL_U16_REFINE && ctx->u16_ok) || (walk && maxlen >= 64))) {
         g.cap = std::min(g.cap, FORK_CAP);
         g.nstreams = all_streams ? FORK_STREAMS : std::min(FORK_STREAMS, (nfork + FORK_CAP - 1) / FORK_CAP);
     }
@@ -614,14 +614,14 @@ int run_generation_full(fv_ctx *ctx, std::vector<fv::Pass> &passes, int kernel, 
     const int maxlen = passes[0].R - passes[0].L;
     const bool whole_gen = passes[0].whole;       // generation 0: bracket its step launches for the stats
     // (a generation 0 forks only as a batch's; nothing that brackets or captures single launches forks)
-    const bool may_fork = (!whole_gen || batch == BATCH_FORK) && !ctx->opt_profile && !(ctx->opt_debug & 64);
+    const bool may_fork = (!whole_gen || batch == BATCH_FORK) && !ctx->opt_profile && !(ctx->opt_debug & FV_DBG_GRAPH);
     const GenShape shape = generation_shape(ctx, kernel, maxlen, np, may_fork, false);
     const int cap = shape.cap, nstreams = shape.nstreams;
     const bool two = nstreams > 1;
     if (two) { if (int rc = fork_streams(ctx, nstreams)) return rc; }
-    const bool col_last = !(ctx->opt_debug & 8);  // FV_OPT_DEBUG bit 3: run every last step as a full step
+    const bool col_last = !(ctx->opt_debug & FV_DBG_FULL_LAST_STEP);  // FV_OPT_DEBUG bit 3: run every last step as a full step
     // FV_OPT_DEBUG bit 6 (experiment): capture this generation's step launches into a hipGraph and replay it
-    const bool use_graph = (ctx->opt_debug & 64) && !ctx->opt_profile;
+    const bool use_graph = (ctx->opt_debug & FV_DBG_GRAPH) && !ctx->opt_profile;
     if (use_graph) FV_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
     if (whole_gen && !use_graph) FV_HIP(hipEventRecord(ctx->ev_s0, ctx->stream));
     // passes are sorted longest first: at lock-step s the passes with len >= s are a prefix; those with
@@ -759,7 +759,7 @@ int run_flat_full(fv_ctx *ctx, int kernel, int T)
         if (int rc = launch_init(ctx, ch, ctx->d_snap.p, ctx->d_rows.p, ctx->view.lb64, ctx->d_ob.p, init_rows_coded(ctx, base, ch.n))) return rc;
     }
     if (two) { if (int rc = fork_streams(ctx, nstreams)) return rc; }
-    const bool col_last = !(ctx->opt_debug & 8);
+    const bool col_last = !(ctx->opt_debug & FV_DBG_FULL_LAST_STEP);
     // single-column last steps of a set of passes, on one stream
     auto columns = [&](const std::vector<int> &which, hipStream_t st) -> int {
         ColumnQueue cols(ctx, st, ctx->d_snap.p);
@@ -1105,7 +1105,7 @@ int decode_full_impl(fv_ctx *ctx, const int *ob, int T, int n_split, int mode, i
     // the flat form of the right-hand generations: one device, one sequence, the reference's task tree, nothing that
     // brackets or captures single launches — and room for its workspace
     bool flat = ctx->opt_flat != 0 && mode == FV_MODE_REFERENCE && plan.generations() >= 2 && plan.generations() - 1 <= fvk::FLAT_MAX_GENS &&
-                !ctx->group && !ctx->comm && ctx->nranks == 1 && !ctx->opt_profile && !ctx->vanilla && !(ctx->opt_debug & 64);
+                !ctx->group && !ctx->comm && ctx->nranks == 1 && !ctx->opt_profile && !ctx->vanilla && !(ctx->opt_debug & FV_DBG_GRAPH);
     if (flat) {
         // the shape of one forked generation holding every right-hand pass of more than one step (the others are column jobs)
         int maxlen = 0, nlong = 0;
@@ -1182,7 +1182,7 @@ int decode_full_batch_impl(fv_ctx *ctx, const int *ob, const long long *offsets,
     // Generation 0 — nseq whole-sequence passes in lock-step — in the three-stream, four-task form of the right-hand
     // generations (DESIGN.md 5.2f has the measurement); FV_OPT_DEBUG bit 28: single-stream launches of up to
     // FV_OPT_MAX_BATCH tasks instead.
-    const int gen0 = (ctx->opt_debug & (1 << 28)) ? BATCH_SERIAL : BATCH_FORK;
+    const int gen0 = (ctx->opt_debug & FV_DBG_BATCH_GEN0_SERIAL) ? BATCH_SERIAL : BATCH_FORK;
     for (size_t g = 0; g < gens.size(); ++g) {
         ctx->stats.passes += (int)gens[g].size();
         if ((rc = run_generation_full(ctx, gens[g], kernel, nprof, gen0))) return rc;
@@ -1228,13 +1228,9 @@ int test_forward_impl(fv_ctx *ctx, const int *ob, int T, const fv_test_pass *tp,
     std::fill(ans, ans + T, 0);
     for (int q = 0; q < np; ++q) if (tp[q].L > 0) ans[tp[q].L - 1] = tp[q].init_state;
     FV_HIP(hipMemcpyAsync(ctx->d_ans.p, ans, (size_t)T * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    struct Restore {
-        fv_ctx *c; int debug;
-        ~Restore() { c->opt_debug = debug; c->test_record = false; }
-    } restore{ ctx, ctx->opt_debug };
-    ctx->opt_debug |= 8;              // every last step a full step: the whole last row, not the one column a decode reads
-    ctx->test_record = true;
-    ctx->test_variants = 0;
+    struct Restore { fv_ctx *c; int debug; ~Restore() { c->opt_debug = debug; } } restore{ ctx, ctx->opt_debug };
+    ctx->opt_debug |= FV_DBG_FULL_LAST_STEP;     // the whole last row, not the one column a decode reads
+    FvTestRecording recording(ctx);
     ctx->fork_active = false;
     size_t nprof = 0;
     if ((rc = run_generation_full(ctx, gen, kernel, nprof))) return rc;      // (sorts `gen` longest first)

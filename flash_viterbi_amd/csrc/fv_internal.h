@@ -53,6 +53,35 @@ struct DevBuf {
 
 namespace fvb { struct HNode { float v; int s; }; }         // heap node / select candidate: {value, state}
 
+// The bits of FV_OPT_DEBUG the host code tests (fv_ctx::opt_debug), named after what include/flashvit.h says each does.
+// (Bits 0, 4, 5, 11, 12 are FV_DEBUG_TIMING_ONLY: the kernels of the timing build read them from their arguments.)
+enum : int {
+    FV_DBG_NO_REVERSE = 1 << 1,             // full-state: no reverse sweep
+    FV_DBG_ALT_LOADS = 1 << 2,              // alternate load schedule
+    FV_DBG_FULL_LAST_STEP = 1 << 3,         // full last step instead of one column
+    FV_DBG_GRAPH = 1 << 6,                  // hipGraph replay of a generation
+    FV_DBG_OWN_CUTS = 1 << 7,               // FLASH-BS: the cut predictor uses the pass's own cuts only
+    FV_DBG_BEAM_F64 = 1 << 8,               // float64 step kernel always
+    FV_DBG_BEAM_Q16 = 1 << 9,               // 16-bit step kernel always
+    FV_DBG_NO_CAND_LISTS = 1 << 10,         // no candidate lists
+    FV_DBG_U16_W16 = 1 << 13,               // full-state: packed kernel in 16-wave workgroups
+    FV_DBG_U16_BATCHED = 1 << 14,           // packed kernel for every batched launch
+    FV_DBG_SELECT_WHOLE_GROUP = 1 << 15,    // FLASH-BS: whole-workgroup select for short lists too
+    FV_DBG_BEAM_ONE_STREAM = 1 << 16,       // pass groups on one stream whatever the size
+    FV_DBG_BEAM_GROUPS = 1 << 17,           // pass groups on four streams whatever the size
+    FV_DBG_FULL_ONE_STREAM = 1 << 18,       // full-state: right-hand generations on one stream
+    FV_DBG_ALL_LAYOUTS = 1 << 19,           // FLASH-BS: every heap layout rebuilt, every tie re-decided
+    FV_DBG_EAGER_REPLAY = 1 << 20,          // every duplicate step replays its heap at once
+    FV_DBG_SLABS = 1 << 21,                 // full-state: three slabs of source rows at any size
+    FV_DBG_SELECT_IN_MEMORY = 1 << 22,      // FLASH-BS: every selection in the memory-resident form
+    FV_DBG_DECIDE_IN_FULL = 1 << 23,        // runs of undecided steps always decided in full
+    FV_DBG_SELECT4_DIRTY = 1 << 24,         // four-wave select also on steps that may have to be resolved
+    FV_DBG_BEAM_WIDE = 1 << 25,             // 16-wave step-kernel workgroups whatever the launch size
+    FV_DBG_BEAM_NARROW = 1 << 26,           // 8-wave workgroups of the 16-bit step kernel whatever the launch size
+    FV_DBG_BATCH_GEN0_SERIAL = 1 << 28,     // fv_decode_full_batch: generation 0 in single-stream launches
+    FV_DBG_BEAM_BATCH_GEN0_OTHER = 1 << 29, // fv_decode_beam_batch: generation 0 in the launch form that is not the default
+};
+
 struct fv_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -173,8 +202,7 @@ struct fv_ctx {
     int opt_row_codes = 1;   // FV_OPT_ROW_CODES: 0 off, 1 auto, 2 on; 3 / 4 (measurements): single-task / batched launches only
     int vanilla = 0;         // set for the duration of fv_decode_vanilla
     int opt_csr_mem = 0;     // FV_OPT_DEBUG bit 31: trellis_step_csr / trellis_step_csr_f64 read their score rows from memory at any K
-    int opt_debug = 0;       // FV_OPT_DEBUG bits: 1 skip refine (timing only), 2 no reverse sweep, 4 alternate unroll, 8 full last step,
-                             // 16 launch only / 32 no score-row staging (sparse walk), 64 hipGraph replay, 256 / 512 beam step kernel: float64 / 16-bit
+    int opt_debug = 0;       // FV_OPT_DEBUG: the FV_DBG_* bits below; include/flashvit.h says what each does
     std::vector<hipEvent_t> prof_events;
     std::vector<int> h_ob;
     std::vector<hipGraphExec_t> graphs;     // experiment (FV_OPT_DEBUG bit 6): destroyed after the decode's sync
@@ -231,6 +259,16 @@ struct fv_ctx {
         f(d_tie_list); f(d_cut); f(d_cand); f(d_cand_count); f(d_dupwin); f(d_doubt); f(d_doubt_count); f(d_needfull);
         f(d_seqof); f(d_passL); f(d_tie_count); f(d_csr_acc); f(d_csr_tie);
     }
+};
+
+// A test hook's scope (include/flashvit_testing.h): the launch helpers record what they launch into the cleared
+// test_variants / test_selects until it ends.  on = false: an ordinary decode going through code a hook shares.
+struct FvTestRecording {
+    fv_ctx *c;
+    explicit FvTestRecording(fv_ctx *ctx, bool on = true) : c(ctx) { if (on) { c->test_record = true; c->test_variants = c->test_selects = 0; } }
+    ~FvTestRecording() { c->test_record = false; }
+    FvTestRecording(const FvTestRecording &) = delete;
+    FvTestRecording &operator=(const FvTestRecording &) = delete;
 };
 
 #define FV_HIP(call)                                                                          \

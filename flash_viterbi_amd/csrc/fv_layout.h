@@ -15,6 +15,7 @@ constexpr int BLOCK = NWAVES * 64;         // 1024 threads: one workgroup per CU
 constexpr int ROW_ALIGN = 32;              // nrows = roundup(K, 32): whole row blocks for every table type
 constexpr int MAX_BATCH = 8;               // independent tasks sharing one sweep of the table
 constexpr int LDS_LIMIT = 160 * 1024;      // bytes of LDS one workgroup may ask for (gfx950: all of a CU's 160 KB)
+constexpr int BEAM_LDS_LIMIT = 150 * 1024; // the smaller bound the beam path admits a beam width by (fv_beam.hip, beam_admit_k)
 
 // Tile-major layout with an R-row interleave: R = 4 for the f32 / f64 tables, 8 for the f16 table.
 template <int R>

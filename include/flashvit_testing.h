@@ -149,7 +149,7 @@ typedef struct {
     unsigned long long *variants, *selects;
 } fv_test_beam_tables;
 
-/* The caller's passes as ONE generation of the FLASH-BS driver (run_generation_beam, through the sorting, the dealing to
+/* The caller's passes as ONE generation of the FLASH-BS driver (beam_forward + beam_pass_ends, through the sorting, the dealing to
  * stream groups and the pass-list upload a decode's generations get), then the per-step buffers copied out.  No kernel is
  * launched that a decode would not launch; the copies are made after the generation has finished.  Admission, tables and
  * workspace are fv_decode_beam's (same refusals, same symbol check; ob == NULL reads the rows staged by fv_set_emissions);
