@@ -200,7 +200,7 @@ fvb::HeapAllArgs heap_all_args(const fv_ctx *ctx, int K, int beam, const int *ga
 {
     fvb::HeapAllArgs h;
     h.scores_all = ctx->d_scores.p; h.slot_val = ctx->d_slot_val.p; h.slot_state = ctx->d_slot_state.p;
-    h.err_counter = ctx->d_counters.p + 5; h.gate = gate; h.seq_of = seq_of;
+    h.err_counter = ctx->d_counters.p + fvk::CNT_HANDSHAKE_TIMEOUT; h.gate = gate; h.seq_of = seq_of;
     h.K = K; h.beam = beam; h.n = 0;
     return h;
 }
@@ -342,7 +342,7 @@ int beam_pass_ends(fv_ctx *ctx, const BeamGen &gen)
         f.LA64R = ctx->LA64R.p; f.LB32T = ctx->view.lb32; f.ob = ctx->d_ob.p;
         f.tie_count = ctx->d_tie_count.p; f.tie_list = ctx->d_tie_list.p; f.tie_cap = (unsigned int)ctx->d_tie_list.n;
         f.slot_val = ctx->d_slot_val.p; f.slot_state = ctx->d_slot_state.p; f.bp = ctx->d_bp.p;
-        f.K = K; f.ld = beam_ld(K); f.beam = beam; f.total = ctx->d_counters.p + 6; f.gate = needfull;
+        f.K = K; f.ld = beam_ld(K); f.beam = beam; f.total = ctx->d_counters.p + fvk::CNT_BEAM_TIES; f.gate = needfull;
         f.seq_of = gen.seq_of; f.csr = gen.rcx.csr;
         hipLaunchKernelGGL(ctx->csr ? fvb::tie_fixup<true> : fvb::tie_fixup<false>, dim3(512), dim3(256), 0, ctx->stream, f);
         FV_HIP(hipGetLastError());
@@ -761,7 +761,8 @@ int test_beam_select_impl(fv_ctx *ctx, int K, int beam, int s, const fv_test_sel
     FV_HIP(hipStreamSynchronize(ctx->stream));
     for (int q = 0; q < nsets; ++q)
         std::copy(cut.begin() + slot(q) * fvb::CUT_W, cut.begin() + (slot(q) + 1) * fvb::CUT_W, cut_out + (size_t)q * fvb::CUT_W);
-    const int which[8] = { 2, 5, 7, 9, 10, 11, 12, 13 };
+    const int which[8] = { fvk::CNT_BEAM_EXACT_SETS, fvk::CNT_HANDSHAKE_TIMEOUT, fvk::CNT_BEAM_CAND_SELECTS, fvk::CNT_BEAM_SPEC_STEPS,
+                           fvk::CNT_BEAM_REACH_EVENTS, fvk::CNT_BEAM_LIST_SHORT, fvk::CNT_BEAM_LIST_LONG, fvk::CNT_BEAM_LIST_ENTRIES };
     for (int i = 0; i < 8; ++i) counters_out[i] = cnt[which[i]];
     if (selects_out) *selects_out = ctx->test_selects;
     return FV_OK;

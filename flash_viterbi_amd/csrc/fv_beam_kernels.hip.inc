@@ -169,8 +169,8 @@ __device__ __forceinline__ bool finish_column(const BeamStepArgs &args, const Be
     if (any && spec && sval[a] == cut_theta) {
         const int at = atomicAdd(ps.doubt_count, 1);
         if (at < DOUBT_CAP) ps.doubt[at] = col;
-        atomicAdd(&args.counters[3], 1ull);
-        if (atomicExch(ps.dupwin, 1) == 0) atomicAdd(&args.counters[4], 1ull);
+        atomicAdd(&args.counters[fvk::CNT_BEAM_DUP_COLS], 1ull);
+        if (atomicExch(ps.dupwin, 1) == 0) atomicAdd(&args.counters[fvk::CNT_BEAM_DUP_STEPS], 1ull);
     }
     return any && r >= ps.cut[CUT_NEXT];
 }
@@ -786,8 +786,9 @@ __global__ __launch_bounds__(128) void heap_build_all(const HeapAllArgs args)
 // What the resolve code (an exact replay of an earlier step + the re-evaluation of the doubtful columns it decides)
 // works on; every per-step buffer is indexed by absolute time.
 struct ResolveCtx {
-    unsigned long long *counters;   // [2] exact replays run, [5] broken hand-shake, [10] selects whose doubtful columns reached the beam,
-                                    // [14] chains of undecided steps cut short by replay_safe
+    unsigned long long *counters;   // fvk::CNT_BEAM_EXACT_SETS exact replays run, CNT_HANDSHAKE_TIMEOUT broken hand-shake, CNT_BEAM_REACH_EVENTS
+                                    // selects whose doubtful columns reached the beam, CNT_BEAM_CHAIN_CUTS chains of undecided steps cut
+                                    // short by replay_safe
     int K, beam;
     int no_cut;                     // FV_OPT_DEBUG bit 23: always decide the whole trailing run of undecided steps (no replay_safe)
     const double *LA64R; int ld;    // float64 table, row-major, and its pitch
@@ -806,7 +807,8 @@ struct SelJob {
     int j, L;                  // absolute time of this step, first position of its pass
 };
 struct SelArgs {
-    unsigned long long *counters;   // [7] selects that ran on a candidate list, [9] duplicate steps carried speculatively
+    unsigned long long *counters;   // fvk::CNT_BEAM_CAND_SELECTS selects that ran on a candidate list, CNT_BEAM_SPEC_STEPS duplicate steps
+                                    // carried speculatively (and the three CNT_BEAM_LIST_* words)
     float margin;                   // lower bound of the next cut = extrapolated theta - margin * (max score - theta)
     int cand_cap;
     int K, beam;
@@ -1024,9 +1026,9 @@ __device__ __forceinline__ int select_body(const SelArgs &args, const SelJob &jo
         job.cut[CUT_MARGIN] = mg;
         job.cut[CUT_NEXT] = next;
         job.cut[CUT_LIST] = (float)C;
-        if (use_cand) { atomicAdd(&args.counters[7], 1ull); atomicAdd(&args.counters[13], (unsigned long long)C); }
-        else if (job.cand && args.s >= 2) atomicAdd(&args.counters[C < B ? 11 : 12], 1ull);      // a list that was too short / overflowed
-        if (spec) atomicAdd(&args.counters[9], 1ull);
+        if (use_cand) { atomicAdd(&args.counters[fvk::CNT_BEAM_CAND_SELECTS], 1ull); atomicAdd(&args.counters[fvk::CNT_BEAM_LIST_ENTRIES], (unsigned long long)C); }
+        else if (job.cand && args.s >= 2) atomicAdd(&args.counters[C < B ? fvk::CNT_BEAM_LIST_SHORT : fvk::CNT_BEAM_LIST_LONG], 1ull);      // a list that was too short / overflowed
+        if (spec) atomicAdd(&args.counters[fvk::CNT_BEAM_SPEC_STEPS], 1ull);
     }
     if (replay && !spec) return SEL_REPLAY;   // duplicate finite scores straddle the cut and may not be carried: exact replay (caller)
     if constexpr (!REG) {
@@ -1166,14 +1168,14 @@ __device__ __forceinline__ void replay_step(const ResolveCtx &c, int t, unsigned
     __syncthreads();                                 // LDS (heap, ring) is free
     if (threadIdx.x == 0) *reinterpret_cast<RingCtl *>(replay_heap(smem) + 2 * B + 2) = RingCtl{ 0u, 0u, 0u, 0u, 0.0f, { 0u, 0u, 0u } };
     __syncthreads();
-    if (w < 2) heap_replay_pair(c.b.scores_all + (size_t)t * c.K, c.K, B, smem, w, lane, &c.counters[5]);
+    if (w < 2) heap_replay_pair(c.b.scores_all + (size_t)t * c.K, c.K, B, smem, w, lane, &c.counters[fvk::CNT_HANDSHAKE_TIMEOUT]);
     if (w == 0) {
         const HNode *h = replay_heap(smem);
         for (int s = lane; s < B; s += 64) { const HNode n = h[s + 1]; c.b.hval[(size_t)t * BP + s] = n.v; c.b.hstate[(size_t)t * BP + s] = n.s; }
         if (lane == 0) {
             st_dev(c.b.cut + (size_t)t * CUT_W + CUT_N, (float)B);
             st_dev(c.b.cut + (size_t)t * CUT_W + CUT_STATE, 2.0f);
-            atomicAdd(&c.counters[2], 1ull);
+            atomicAdd(&c.counters[fvk::CNT_BEAM_EXACT_SETS], 1ull);
         }
     }
     wg_publish();
@@ -1367,7 +1369,7 @@ __device__ __forceinline__ void resolve_upto(const ResolveCtx &c, int L, int tar
     if (!c.no_cut) {
         for (int t = target - 1; t > t0; --t) {     // (every one of these steps is undecided; replay_safe starts with a barrier)
             if (replay_safe(c, t, bcast, NW)) {
-                if (threadIdx.x == 0) atomicAdd(&c.counters[14], 1ull);
+                if (threadIdx.x == 0) atomicAdd(&c.counters[fvk::CNT_BEAM_CHAIN_CUTS], 1ull);
                 t0 = t;
                 break;
             }
@@ -1411,7 +1413,7 @@ __device__ __forceinline__ void select_finish(const SelArgs &args, const SelJob 
     if (reach) {
         resolve_upto<CSR>(c, job.L, job.j, smem, &sh.sh_sel[0], NT / 64);
         const unsigned long long q2 = __builtin_amdgcn_s_memtime();
-        if (threadIdx.x == 0) atomicAdd(&c.counters[10], 1ull);
+        if (threadIdx.x == 0) atomicAdd(&c.counters[fvk::CNT_BEAM_REACH_EVENTS], 1ull);
         st = select_body<R, REG, NT>(args, job, sh, 0, false, !args.eager);
         const unsigned long long q3 = __builtin_amdgcn_s_memtime();
         if (st == SEL_REPLAY) replay_step(c, job.j, smem);
@@ -1427,7 +1429,7 @@ __device__ __forceinline__ void select_finish(const SelArgs &args, const SelJob 
 #endif
     if (dirty && (st == SEL_REPLAY || doubtful_reach(c, job, &sh.sh_sel[0], NT))) {
         resolve_upto<CSR>(c, job.L, job.j, smem, &sh.sh_sel[0], NT / 64);
-        if (threadIdx.x == 0) atomicAdd(&c.counters[10], 1ull);
+        if (threadIdx.x == 0) atomicAdd(&c.counters[fvk::CNT_BEAM_REACH_EVENTS], 1ull);
         st = select_body<R, REG, NT>(args, job, sh, 0, false, !args.eager);
     }
     if (st == SEL_REPLAY) replay_step(c, job.j, smem);

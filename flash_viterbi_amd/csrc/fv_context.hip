@@ -3,28 +3,6 @@
 #include "fv_internal.h"
 #include "flashvit_testing.h"
 
-namespace {
-
-// log() of a strided block of floats on several host threads (same libm call per entry as the reference).
-template <typename F>
-void parallel_rows(int rows, F &&fn)
-{
-    unsigned hw = std::thread::hardware_concurrency();
-    int nt = (int)std::min<unsigned>(hw ? hw : 4, 16);
-    if (rows < 256) nt = 1;
-    if (nt <= 1) { fn(0, rows); return; }
-    std::vector<std::thread> th;
-    int per = (rows + nt - 1) / nt;
-    for (int t = 0; t < nt; ++t) {
-        int a = t * per, b = std::min(rows, a + per);
-        if (a >= b) break;
-        th.emplace_back([=, &fn] { fn(a, b); });
-    }
-    for (auto &x : th) x.join();
-}
-
-}  // namespace
-
 namespace fvi {
 
 size_t device_bytes(const fv_ctx *c)
@@ -214,26 +192,26 @@ static int read_stats(fv_ctx *ctx, const unsigned long long *counters, clk::time
         FV_HIP(hipEventElapsedTime(&ms, ctx->prof_events[i], ctx->prof_events[i + 1]));
         st.step_kernel_ms += ms;
     }
-    st.refine_near = (long long)counters[0];
-    st.refine_rescan = (long long)counters[1];
-    st.beam_exact_sets = (long long)counters[2];
-    st.beam_dup_cols = (long long)counters[3];
-    st.beam_dup_steps = (long long)counters[4];
-    st.beam_ties = (long long)counters[6];
-    st.beam_cand_selects = (long long)counters[7];
-    st.refine_saturated = (long long)counters[8];
-    st.beam_spec_steps = (long long)counters[9];
-    st.beam_reach_events = (long long)counters[10];
-    st.beam_list_short = (long long)counters[11];
-    st.beam_list_long = (long long)counters[12];
-    st.beam_list_entries = (long long)counters[13];
-    st.beam_chain_cuts = (long long)counters[14];
+    st.refine_near = (long long)counters[fvk::CNT_REFINE_NEAR];
+    st.refine_rescan = (long long)counters[fvk::CNT_REFINE_RESCAN];
+    st.beam_exact_sets = (long long)counters[fvk::CNT_BEAM_EXACT_SETS];
+    st.beam_dup_cols = (long long)counters[fvk::CNT_BEAM_DUP_COLS];
+    st.beam_dup_steps = (long long)counters[fvk::CNT_BEAM_DUP_STEPS];
+    st.beam_ties = (long long)counters[fvk::CNT_BEAM_TIES];
+    st.beam_cand_selects = (long long)counters[fvk::CNT_BEAM_CAND_SELECTS];
+    st.refine_saturated = (long long)counters[fvk::CNT_REFINE_SATURATED];
+    st.beam_spec_steps = (long long)counters[fvk::CNT_BEAM_SPEC_STEPS];
+    st.beam_reach_events = (long long)counters[fvk::CNT_BEAM_REACH_EVENTS];
+    st.beam_list_short = (long long)counters[fvk::CNT_BEAM_LIST_SHORT];
+    st.beam_list_long = (long long)counters[fvk::CNT_BEAM_LIST_LONG];
+    st.beam_list_entries = (long long)counters[fvk::CNT_BEAM_LIST_ENTRIES];
+    st.beam_chain_cuts = (long long)counters[fvk::CNT_BEAM_CHAIN_CUTS];
     st.bt_restarts = (long long)counters[fvk::BT_COUNTER];
     if (counters[fvk::FLAT_COUNTER]) {               // the resolver of a flat decode met a generation it could not commit
         st.flat_first_miss = (int)(counters[fvk::FLAT_COUNTER] >> 32);
         st.flat_missed = (int)(counters[fvk::FLAT_COUNTER] & 0xffffffffull);
     }
-    if (counters[5]) { ctx->detail = "heap replay: producer/consumer hand-shake timed out"; return FV_ERR_DEVICE; }
+    if (counters[fvk::CNT_HANDSHAKE_TIMEOUT]) { ctx->detail = "heap replay: producer/consumer hand-shake timed out"; return FV_ERR_DEVICE; }
     st.device_bytes = (long long)fvi::device_bytes(ctx);
     st.ranks = ctx->nranks;
     return 0;
@@ -366,161 +344,39 @@ extern "C" void fv_destroy(fv_ctx *ctx)
     delete ctx;          // (the device buffers free themselves)
 }
 
-namespace fvi {
+namespace fvi {      // what a context holds — model, emission map, staged scores: one rule each
 
-// log B (transposed: one row per symbol) and log Pi, with the value checks fv_set_model and fv_set_model_sparse share
-static void log_emissions(const float *B, const float *Pi, int K, int M, HostTables &h, bool &ok_range, bool &any_big)
+// fn(member) for members 0 .. n-1 (or n-1 .. 1 and the handle last); stops at the first non-zero return and copies that
+// member's detail to the handle.  Name fn's parameter `ctx`: FV_HIP inside it then reports into the member.
+template <class F>
+static int for_each_member(fv_ctx *ctx, F &&fn, bool handle_last = false)
 {
-    h.b64.assign((size_t)M * K, 0.0); h.pi64.assign(K, 0.0);
-    h.b32.assign((size_t)M * K, 0.0f);
-    for (int i = 0; i < K; ++i) {
-        for (int o = 0; o < M; ++o) {
-            const float x = B[(size_t)i * M + o];
-            if (!(x >= 0.0f) || std::isinf(x)) ok_range = false;
-            if (x > 1.0f) any_big = true;
-            const double l = std::log((double)x);
-            h.b64[(size_t)o * K + i] = l; h.b32[(size_t)o * K + i] = (float)l;
-        }
-        const float x = Pi[i];
-        if (!(x >= 0.0f) || std::isinf(x)) ok_range = false;
-        if (x > 1.0f) any_big = true;
-        h.pi64[i] = std::log((double)x);
+    const int n = group_size(ctx);
+    for (int i = 0; i < n; ++i) {
+        fv_ctx *m = group_member(ctx, handle_last ? n - 1 - i : i);
+        if (int rc = fn(m)) { if (m != ctx) ctx->detail = m->detail; return rc; }
     }
+    return 0;
 }
 
-// Host side of fv_set_model: log() of every entry in double with the host libm (the calls the reference makes per
-// cell, FLASH:142,150,167,170) and the table encodings.  Built once per model, uploaded to every device of a context.
-int build_host_tables(const float *A, const float *B, const float *Pi, int K, int M, HostTables &h, std::string &detail)
+// "Nothing is staged any more" on one member: the rows, and with_map the class count of the emission map as well.
+static void drop_emissions(fv_ctx *m, bool with_map) { m->emis_rows = 0; m->emis_positive = false; if (with_map) m->emis_P = 0; }
+
+// ... on every member, and in the handle's statistics: the row count, and with_ms the staging time as well
+static void drop_group_emissions(fv_ctx *ctx, bool with_map, bool with_ms)
 {
-    h.K = K; h.M = M;
-    const int nrows = h.nrows = round_up(K, fvk::ROW_ALIGN);
-    const int ntiles = h.ntiles = (K + fvk::TILE_W - 1) / fvk::TILE_W;
-    // the full-state step kernels keep one score row in LDS: beyond that K only the beam path is available
-    // (it needs the float64 table alone, which also keeps the host footprint at 8 B per entry)
-    const bool full_ok = h.full_ok = fvk::step_lds_bytes<1>(nrows) <= (size_t)fvk::LDS_LIMIT;
-    h.u16_ok = fvk::u16_lds_bytes<1, 8>(nrows) <= (size_t)fvk::LDS_LIMIT && K <= 65536;
+    for_each_member(ctx, [&](fv_ctx *m) { drop_emissions(m, with_map); return 0; });
+    ctx->stats.emission_rows = 0;
+    if (with_ms) ctx->stats.set_emissions_ms = 0.0;
+}
 
-    const size_t tab = h.tab = (size_t)ntiles * nrows * fvk::TILE_W;
-    std::vector<double> &h64 = h.h64;
-    std::vector<float> &h32 = h.h32;
-    std::vector<unsigned short> &h16 = h.h16;
-    try {
-        h64.assign(tab, -HUGE_VAL);
-        if (full_ok) { h32.assign(tab, -HUGE_VALF); h16.assign(tab, 0xFC00u /* -inf */); }
-    } catch (...) { return FV_ERR_NOMEM; }
-    std::vector<double> dmax_row(K, 0.0);
-    bool ok_range = true;
-    std::vector<char> bad(K, 0), big(K, 0);
-    parallel_rows(K, [&](int a, int b) {
-        for (int k = a; k < b; ++k) {
-            const float *src = A + (size_t)k * K;
-            for (int i = 0; i < K; ++i) {
-                const float x = src[i];
-                if (!(x >= 0.0f) || std::isinf(x)) bad[k] = 1;
-                if (x > 1.0f) big[k] = 1;
-                const double l = std::log((double)x);
-                const size_t e = fvk::tab_index<4>(k, i, nrows);
-                h64[e] = l;
-                if (!full_ok) continue;
-                h32[e] = (float)l;
-                const _Float16 hl = (_Float16)l;          // round to nearest even; -inf stays -inf
-                unsigned short hb;
-                std::memcpy(&hb, &hl, 2);
-                h16[fvk::tab_index<8>(k, i, nrows)] = hb;
-                if (std::isfinite(l)) {
-                    // a finite log that overflows binary16 (< -65504) would become -inf: cannot happen for
-                    // float32 inputs (log >= -104), but keep the bound honest
-                    const double d = std::isfinite((double)hl) ? std::fabs((double)hl - l) : HUGE_VAL;
-                    if (d > dmax_row[k]) dmax_row[k] = d;
-                }
-            }
-        }
-    });
-    h.any_big = false;
-    log_emissions(B, Pi, K, M, h, ok_range, h.any_big);
-    for (int k = 0; k < K; ++k) { if (bad[k]) ok_range = false; if (big[k]) h.any_big = true; }
-    if (!ok_range) { detail = "model entries must be finite and >= 0"; return FV_ERR_ARG; }
-
-    double dmax = 0.0;
-    for (int k = 0; k < K; ++k) dmax = std::max(dmax, dmax_row[k]);
-    h.window16 = std::nextafter((float)(2.0 * dmax), HUGE_VALF);     // rounded up
-    // fixed-point table: step = (largest finite |log A|) / 65534, code = round(-L/step), 0xffff = -inf.
-    // The kernel evaluates fma(code, -step, s) with step as a float, so the error is measured against
-    // exactly that product (code * (double)(float)step is exact in double).
-    h.density = 1.0; h.windowq = 0.0f; h.qscale = -1.0f;
-    if (!full_ok) return FV_OK;
-    std::vector<unsigned short> &hq = h.hq;
-    try { hq.assign(tab, 0xFFFFu); } catch (...) { return FV_ERR_NOMEM; }
-    double lmax = 0.0;
-    for (size_t e = 0; e < tab; ++e) if (std::isfinite(h64[e])) lmax = std::max(lmax, -h64[e]);
-    const float stepf = lmax > 0.0 ? (float)(lmax / 65534.0) : 1.0f;
-    const double stepd = (double)stepf;
-    std::vector<double> dq_row(K, 0.0);
-    parallel_rows(K, [&](int a, int b) {
-        for (int k = a; k < b; ++k)
-            for (int i = 0; i < K; ++i) {
-                const double l = h64[fvk::tab_index<4>(k, i, nrows)];
-                if (!std::isfinite(l)) continue;
-                double q = std::nearbyint(-l / stepd);
-                if (q < 0) q = 0;
-                if (q > 65534.0) q = 65534.0;
-                hq[fvk::tab_index<8>(k, i, nrows)] = (unsigned short)q;
-                const double d = std::fabs(-q * stepd - l);
-                if (d > dq_row[k]) dq_row[k] = d;
-            }
-    });
-    double dqmax = 0.0;
-    for (int k = 0; k < K; ++k) dqmax = std::max(dqmax, dq_row[k]);
-    h.windowq = std::nextafter((float)(2.0 * dqmax), HUGE_VALF);
-    h.qscale = -stepf;
-    // sparse form of the same codes (CSC-Q16, see trellis_step_sparse): per tile, per column, the finite
-    // entries in ascending k as (k << 16 | code), 4 per lane load, columns padded to the tile's longest
-    if (K <= 65536) {
-        std::vector<int> &off = h.sp_off, &nwbv = h.sp_nwb;
-        off.assign(ntiles, 0); nwbv.assign(ntiles, 0);
-        std::vector<std::vector<uint32_t>> cols((size_t)ntiles * fvk::TILE_W);
-        parallel_rows(ntiles, [&](int a, int b) {
-            for (int tl = a; tl < b; ++tl)
-                for (int c = 0; c < fvk::TILE_W; ++c) {
-                    const int i = tl * fvk::TILE_W + c;
-                    if (i >= K) continue;
-                    std::vector<uint32_t> &v = cols[(size_t)tl * fvk::TILE_W + c];
-                    for (int k = 0; k < K; ++k) {
-                        const unsigned short code = hq[fvk::tab_index<8>(k, i, nrows)];
-                        if (code != 0xFFFFu) v.push_back(((uint32_t)k << 16) | code);
-                    }
-                }
-        });
-        size_t nnz = 0, total = 0;
-        for (int tl = 0; tl < ntiles; ++tl) {
-            size_t longest = 0;
-            for (int c = 0; c < fvk::TILE_W; ++c) {
-                const size_t n = cols[(size_t)tl * fvk::TILE_W + c].size();
-                nnz += n; longest = std::max(longest, n);
-            }
-            const int nch = (int)((longest + 3) / 4);
-            nwbv[tl] = (nch + 3) / 4;
-            off[tl] = (int)total;
-            total += (size_t)nwbv[tl] * 4 * fvk::TILE_W;
-        }
-        h.density = (double)nnz / ((double)K * K);
-        if (total < (size_t)1 << 30 && total > 0) {
-            std::vector<uint4> &sp = h.sp;
-            try { sp.resize(total); } catch (...) { return FV_ERR_NOMEM; }
-            const uint32_t pad = 0x0000FFFFu;           // k = 0, code = 0xffff (-inf)
-            parallel_rows(ntiles, [&](int a, int b) {
-                for (int tl = a; tl < b; ++tl)
-                    for (int j = 0; j < nwbv[tl] * 4; ++j)
-                        for (int c = 0; c < fvk::TILE_W; ++c) {
-                            const std::vector<uint32_t> &v = cols[(size_t)tl * fvk::TILE_W + c];
-                            uint32_t e[4];
-                            for (int q = 0; q < 4; ++q) e[q] = (size_t)(4 * j + q) < v.size() ? v[4 * j + q] : pad;
-                            sp[(size_t)off[tl] + (size_t)j * fvk::TILE_W + c] = make_uint4(e[0], e[1], e[2], e[3]);
-                        }
-            });
-        }
-    }
-    return FV_OK;
+// a host table to the device: the buffer grown to n elements, then one blocking copy
+template <typename T>
+static int upload(fv_ctx *ctx, DevBuf<T> &buf, const T *data, size_t n)
+{
+    FV_HIP(buf.ensure(n));
+    FV_HIP(hipMemcpy(buf.p, data, n * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
 }
 
 // What both model setters do first on a device: the context holds NO model from here until every upload has succeeded
@@ -531,8 +387,7 @@ static void drop_model(fv_ctx *ctx, bool keep_dense)
 {
     ctx->K = 0; ctx->M = 0; ctx->nrows = 0; ctx->full_ok = false; ctx->u16_ok = false; ctx->laq16_ready = false;
     ctx->rowq_ready = false; ctx->beam_q16_ready = false; ctx->csr = false;
-    ctx->emis_rows = 0; ctx->emis_positive = false;      // staged emission scores belong to the model they were staged under
-    ctx->emis_P = 0;                                     // ... and so does the emission map
+    drop_emissions(ctx, true);           // staged emission scores belong to the model they were staged under, and so does the map
     (void)hipStreamSynchronize(ctx->stream);
     ctx->LA64R.release(); ctx->LAQ16R.release();
     ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release();
@@ -547,12 +402,10 @@ static void drop_model(fv_ctx *ctx, bool keep_dense)
 static int finish_upload(fv_ctx *ctx, const HostTables &e)
 {
     ctx->window16 = e.window16; ctx->windowq = e.windowq; ctx->qscale = e.qscale; ctx->density = e.density;
-    FV_HIP(ctx->LB64T.ensure((size_t)e.M * e.K));
-    FV_HIP(ctx->LB32T.ensure((size_t)e.M * e.K));
-    FV_HIP(ctx->LPi64.ensure(e.K));
-    FV_HIP(hipMemcpy(ctx->LB64T.p, e.b64.data(), e.b64.size() * sizeof(double), hipMemcpyHostToDevice));
-    FV_HIP(hipMemcpy(ctx->LB32T.p, e.b32.data(), e.b32.size() * sizeof(float), hipMemcpyHostToDevice));
-    FV_HIP(hipMemcpy(ctx->LPi64.p, e.pi64.data(), e.pi64.size() * sizeof(double), hipMemcpyHostToDevice));
+    int rc = 0;
+    if ((rc = upload(ctx, ctx->LB64T, e.b64.data(), e.b64.size())) || (rc = upload(ctx, ctx->LB32T, e.b32.data(), e.b32.size())) ||
+        (rc = upload(ctx, ctx->LPi64, e.pi64.data(), e.pi64.size())))
+        return rc;
     ctx->K = e.K; ctx->M = e.M; ctx->nrows = e.nrows;
     ctx->logs_nonpositive = !e.any_big;
     ctx->stats = fv_stats{};
@@ -560,187 +413,57 @@ static int finish_upload(fv_ctx *ctx, const HostTables &e)
     return FV_OK;
 }
 
-// Device side of fv_set_model, once per device: the tables are overwritten in place.
-int upload_tables(fv_ctx *ctx, const HostTables &h)
+// Device side of fv_set_model, once per device: the tables are overwritten in place (grown in the order LAQ16, SP*, LA64, LA32, LA16).
+static int upload_tables(fv_ctx *ctx, const HostTables &h)
 {
     FV_HIP(hipSetDevice(ctx->device));
     drop_model(ctx, true);
-    const size_t tab = h.tab;
+    const size_t tab = h.tab, ntiles = (size_t)h.ntiles;
+    int rc = 0;
     if (h.full_ok) {
-        FV_HIP(ctx->LAQ16.ensure(tab));
-        FV_HIP(hipMemcpy(ctx->LAQ16.p, h.hq.data(), tab * sizeof(unsigned short), hipMemcpyHostToDevice));
-        if (!h.sp.empty()) {
-            FV_HIP(ctx->SPdata.ensure(h.sp.size()));
-            FV_HIP(ctx->SPoff.ensure(h.ntiles));
-            FV_HIP(ctx->SPnwb.ensure(h.ntiles));
-            FV_HIP(hipMemcpy(ctx->SPdata.p, h.sp.data(), h.sp.size() * sizeof(uint4), hipMemcpyHostToDevice));
-            FV_HIP(hipMemcpy(ctx->SPoff.p, h.sp_off.data(), h.ntiles * sizeof(int), hipMemcpyHostToDevice));
-            FV_HIP(hipMemcpy(ctx->SPnwb.p, h.sp_nwb.data(), h.ntiles * sizeof(int), hipMemcpyHostToDevice));
-        }
+        if ((rc = upload(ctx, ctx->LAQ16, h.hq.data(), tab))) return rc;
+        if (!h.sp.empty())
+            if ((rc = upload(ctx, ctx->SPdata, h.sp.data(), h.sp.size())) || (rc = upload(ctx, ctx->SPoff, h.sp_off.data(), ntiles)) ||
+                (rc = upload(ctx, ctx->SPnwb, h.sp_nwb.data(), ntiles)))
+                return rc;
     }
     FV_HIP(ctx->LA64.ensure(tab));
     if (h.full_ok) {
-        FV_HIP(ctx->LA32.ensure(tab));
-        FV_HIP(ctx->LA16.ensure(tab));
-        FV_HIP(hipMemcpy(ctx->LA16.p, h.h16.data(), tab * sizeof(unsigned short), hipMemcpyHostToDevice));
-        FV_HIP(hipMemcpy(ctx->LA32.p, h.h32.data(), tab * sizeof(float), hipMemcpyHostToDevice));
+        if ((rc = upload(ctx, ctx->LA32, h.h32.data(), tab)) || (rc = upload(ctx, ctx->LA16, h.h16.data(), tab))) return rc;
     } else {
         ctx->LA32.release(); ctx->LA16.release(); ctx->LAQ16.release();
     }
-    FV_HIP(hipMemcpy(ctx->LA64.p, h.h64.data(), tab * sizeof(double), hipMemcpyHostToDevice));
-    if (int rc = finish_upload(ctx, h)) return rc;
+    if ((rc = upload(ctx, ctx->LA64, h.h64.data(), tab)) || (rc = finish_upload(ctx, h))) return rc;
     ctx->laq16_ready = h.full_ok;          // beyond the float32 limit: built on first use (fv_full.hip)
     ctx->full_ok = h.full_ok; ctx->u16_ok = h.u16_ok;     // LA64R / LAQ16R: rebuilt on the next beam decode
     return FV_OK;
 }
 
-// what fv_set_model_sparse computes on the host: everything is O(nnz + K * M)
-struct HostCsr {
-    HostTables e;                        // K, M, nrows, ntiles, log B / log Pi, windowq, qscale, density, any_big
-    std::vector<uint4> ck;               // CSC-32 table (fv_kernels.hip.inc, trellis_step_csr)
-    std::vector<uint2> cq;
-    std::vector<double> c64;
-    std::vector<long long> off;
-    std::vector<int> nwb;
-    std::vector<double> rlog;            // log of every stored entry, in the caller's order
-};
-
-// Checks the CSR arrays, takes log((double)x) of every stored entry with the host libm (per entry the call fv_set_model
-// makes) and derives the Q16 step and window from the finite ones exactly as build_host_tables does from the dense
-// table's: the absent entries are its -inf cells, which take part in neither.
-int build_host_csr(const long long *row_ptr, const int *col, const float *val, const float *B, const float *Pi, int K, int M,
-                   HostCsr &h, std::string &detail)
-{
-    HostTables &e = h.e;
-    e.K = K; e.M = M;
-    e.nrows = round_up(K, fvk::ROW_ALIGN);
-    const int ntiles = e.ntiles = (K + fvk::TILE_W - 1) / fvk::TILE_W;
-    if (row_ptr[0] != 0) { detail = "fv_set_model_sparse: row_ptr[0] must be 0 (row 0)"; return FV_ERR_ARG; }
-    for (int k = 0; k < K; ++k)
-        if (row_ptr[k + 1] < row_ptr[k]) { detail = "fv_set_model_sparse: row_ptr decreases at row " + std::to_string(k); return FV_ERR_ARG; }
-    const long long nnz = row_ptr[K];
-    if (nnz > 0 && (!col || !val)) return FV_ERR_ARG;
-    // (a row holds at most K entries once its columns are strictly ascending, so nnz <= K * K without a check of its own)
-    std::vector<int> bad_row(K, 0);
-    std::vector<char> big(K, 0);
-    std::vector<double> lmax_row(K, 0.0);
-    try { h.rlog.resize((size_t)nnz); } catch (...) { return FV_ERR_NOMEM; }
-    parallel_rows(K, [&](int a, int b) {
-        for (int k = a; k < b; ++k) {
-            int prev = -1;
-            for (long long p = row_ptr[k]; p < row_ptr[k + 1]; ++p) {
-                const int i = col[p];
-                const float x = val[p];
-                if (i < 0 || i >= K) bad_row[k] |= 1;
-                else if (i <= prev) bad_row[k] |= 2;
-                prev = i;
-                if (!(x >= 0.0f) || std::isinf(x)) bad_row[k] |= 4;
-                if (x > 1.0f) big[k] = 1;
-                const double l = std::log((double)x);
-                h.rlog[(size_t)p] = l;
-                if (std::isfinite(l)) lmax_row[k] = std::max(lmax_row[k], -l);
-            }
-        }
-    });
-    for (int k = 0; k < K; ++k) {
-        if (bad_row[k] & 1) { detail = "fv_set_model_sparse: row " + std::to_string(k) + " holds a column outside [0, K)"; return FV_ERR_ARG; }
-        if (bad_row[k] & 2) { detail = "fv_set_model_sparse: the columns of row " + std::to_string(k) + " are not strictly ascending"; return FV_ERR_ARG; }
-    }
-    bool ok_range = true;
-    e.any_big = false;
-    log_emissions(B, Pi, K, M, e, ok_range, e.any_big);
-    for (int k = 0; k < K; ++k) {
-        if (bad_row[k] & 4) { detail = "model entries must be finite and >= 0 (row " + std::to_string(k) + ")"; return FV_ERR_ARG; }
-        if (big[k]) e.any_big = true;
-    }
-    if (!ok_range) { detail = "model entries must be finite and >= 0"; return FV_ERR_ARG; }
-
-    double lmax = 0.0;
-    for (int k = 0; k < K; ++k) lmax = std::max(lmax, lmax_row[k]);
-    const float stepf = lmax > 0.0 ? (float)(lmax / 65534.0) : 1.0f;
-    const double stepd = (double)stepf;
-    auto code_of = [&](double l) {
-        double q = std::nearbyint(-l / stepd);
-        if (q < 0) q = 0;
-        if (q > 65534.0) q = 65534.0;
-        return q;
-    };
-    // per destination column: the number of finite entries, then the tiles' extents (columns padded to the tile's
-    // longest, rounded up to a wave-block of 4 chunks x 4 entries)
-    std::vector<int> cnt((size_t)ntiles * fvk::TILE_W, 0);
-    long long nfin = 0;
-    double dqmax = 0.0;
-    for (long long p = 0; p < nnz; ++p) {
-        const double l = h.rlog[(size_t)p];
-        if (!std::isfinite(l)) continue;
-        ++cnt[(size_t)col[p]];
-        ++nfin;
-        dqmax = std::max(dqmax, std::fabs(-code_of(l) * stepd - l));
-    }
-    e.windowq = std::nextafter((float)(2.0 * dqmax), HUGE_VALF);
-    e.qscale = -stepf;
-    e.window16 = 0.0f;                   // (no binary16 table)
-    e.density = (double)nfin / ((double)K * K);
-    h.off.assign(ntiles, 0); h.nwb.assign(ntiles, 0);
-    long long total = 0;
-    for (int tl = 0; tl < ntiles; ++tl) {
-        int longest = 0;
-        for (int c = 0; c < fvk::TILE_W; ++c) longest = std::max(longest, cnt[(size_t)tl * fvk::TILE_W + c]);
-        h.nwb[tl] = (longest + 15) / 16;
-        h.off[tl] = total;
-        total += (long long)h.nwb[tl] * 4 * fvk::TILE_W;
-    }
-    try {
-        h.ck.assign((size_t)total, make_uint4(0u, 0u, 0u, 0u));
-        h.cq.assign((size_t)total, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
-        h.c64.assign((size_t)total * 4, -HUGE_VAL);
-    } catch (...) { return FV_ERR_NOMEM; }
-    // rows in ascending k: every column fills in ascending source state
-    std::fill(cnt.begin(), cnt.end(), 0);
-    unsigned int *kw = reinterpret_cast<unsigned int *>(h.ck.data());
-    unsigned short *qw = reinterpret_cast<unsigned short *>(h.cq.data());
-    for (int k = 0; k < K; ++k)
-        for (long long p = row_ptr[k]; p < row_ptr[k + 1]; ++p) {
-            const double l = h.rlog[(size_t)p];
-            if (!std::isfinite(l)) continue;
-            const int i = col[p], n = cnt[(size_t)i]++;
-            const size_t pos = 4 * ((size_t)h.off[i / fvk::TILE_W] + (size_t)(n >> 2) * fvk::TILE_W + (i % fvk::TILE_W)) + (n & 3);
-            kw[pos] = (unsigned int)k;
-            qw[pos] = (unsigned short)code_of(l);
-            h.c64[pos] = l;
-        }
-    return FV_OK;
-}
-
 // Device side of fv_set_model_sparse, once per device; as upload_tables, the context holds no model until every upload
 // has succeeded.  The dense tables of an earlier fv_set_model are released.
-int upload_csr(fv_ctx *ctx, const HostCsr &h, const long long *row_ptr, const int *col)
+static int upload_csr(fv_ctx *ctx, const HostCsr &h, const long long *row_ptr, const int *col)
 {
     const HostTables &e = h.e;
     FV_HIP(hipSetDevice(ctx->device));
     drop_model(ctx, false);
-    const size_t nnz = h.rlog.size(), nv = h.ck.size();
+    const size_t nnz = h.rlog.size(), nv = h.ck.size(), ntiles = (size_t)e.ntiles;
+    int rc = 0;
+    // (an empty model still has tables: one element each)
     FV_HIP(ctx->CSk.ensure(std::max<size_t>(nv, 1)));
     FV_HIP(ctx->CSq.ensure(std::max<size_t>(nv, 1)));
     FV_HIP(ctx->CS64.ensure(std::max<size_t>(nv * 4, 1)));
-    FV_HIP(ctx->CSoff.ensure(e.ntiles));
-    FV_HIP(ctx->CSnwb.ensure(e.ntiles));
-    FV_HIP(ctx->CRptr.ensure((size_t)e.K + 1));
+    if (nv)
+        if ((rc = upload(ctx, ctx->CSk, h.ck.data(), nv)) || (rc = upload(ctx, ctx->CSq, h.cq.data(), nv)) ||
+            (rc = upload(ctx, ctx->CS64, h.c64.data(), nv * 4)))
+            return rc;
+    if ((rc = upload(ctx, ctx->CSoff, h.off.data(), ntiles)) || (rc = upload(ctx, ctx->CSnwb, h.nwb.data(), ntiles)) ||
+        (rc = upload(ctx, ctx->CRptr, row_ptr, (size_t)e.K + 1)))
+        return rc;
     FV_HIP(ctx->CRcol.ensure(std::max<size_t>(nnz, 1)));
     FV_HIP(ctx->CRlog.ensure(std::max<size_t>(nnz, 1)));
-    if (nv) {
-        FV_HIP(hipMemcpy(ctx->CSk.p, h.ck.data(), nv * sizeof(uint4), hipMemcpyHostToDevice));
-        FV_HIP(hipMemcpy(ctx->CSq.p, h.cq.data(), nv * sizeof(uint2), hipMemcpyHostToDevice));
-        FV_HIP(hipMemcpy(ctx->CS64.p, h.c64.data(), nv * 4 * sizeof(double), hipMemcpyHostToDevice));
-    }
-    FV_HIP(hipMemcpy(ctx->CSoff.p, h.off.data(), e.ntiles * sizeof(long long), hipMemcpyHostToDevice));
-    FV_HIP(hipMemcpy(ctx->CSnwb.p, h.nwb.data(), e.ntiles * sizeof(int), hipMemcpyHostToDevice));
-    FV_HIP(hipMemcpy(ctx->CRptr.p, row_ptr, ((size_t)e.K + 1) * sizeof(long long), hipMemcpyHostToDevice));
-    if (nnz) {
-        FV_HIP(hipMemcpy(ctx->CRcol.p, col, nnz * sizeof(int), hipMemcpyHostToDevice));
-        FV_HIP(hipMemcpy(ctx->CRlog.p, h.rlog.data(), nnz * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (int rc = finish_upload(ctx, e)) return rc;
+    if (nnz)
+        if ((rc = upload(ctx, ctx->CRcol, col, nnz)) || (rc = upload(ctx, ctx->CRlog, h.rlog.data(), nnz))) return rc;
+    if ((rc = finish_upload(ctx, e))) return rc;
     ctx->csr = true; ctx->csr_nnz = (long long)nnz;
     ctx->stats.density = ctx->density;
     return FV_OK;
@@ -748,6 +471,7 @@ int upload_csr(fv_ctx *ctx, const HostCsr &h, const long long *row_ptr, const in
 
 }  // namespace fvi
 
+// Both model setters: build on the host (fv_model.cpp), then for every member drop and upload.
 extern "C" int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const int *col, const float *val, const float *B,
                                    const float *Pi, int K, int M)
 {
@@ -758,11 +482,7 @@ extern "C" int fv_set_model_sparse(fv_ctx *ctx, const long long *row_ptr, const 
     int rc = FV_OK;
     try { rc = fvi::build_host_csr(row_ptr, col, val, B, Pi, K, M, h, ctx->detail); } catch (const std::bad_alloc &) { rc = FV_ERR_NOMEM; }
     if (rc) return rc;
-    const int n = fvi::group_size(ctx);
-    for (int r = 0; r < n; ++r) {
-        fv_ctx *m = fvi::group_member(ctx, r);
-        if ((rc = fvi::upload_csr(m, h, row_ptr, col))) { if (m != ctx) ctx->detail = m->detail; return rc; }
-    }
+    if ((rc = fvi::for_each_member(ctx, [&](fv_ctx *ctx) { return fvi::upload_csr(ctx, h, row_ptr, col); }))) return rc;
     ctx->stats.set_model_ms = ms_since(t0);
     return FV_OK;
 }
@@ -776,25 +496,40 @@ extern "C" int fv_set_model(fv_ctx *ctx, const float *A, const float *B, const f
     int rc = fvi::build_host_tables(A, B, Pi, K, M, h, ctx->detail);
     if (rc) return rc;
     // a multi-device context uploads the same host tables to every device
-    const int n = fvi::group_size(ctx);
-    for (int r = 0; r < n; ++r) {
-        fv_ctx *m = fvi::group_member(ctx, r);
-        if ((rc = fvi::upload_tables(m, h))) { if (m != ctx) ctx->detail = m->detail; return rc; }
-    }
+    if ((rc = fvi::for_each_member(ctx, [&](fv_ctx *ctx) { return fvi::upload_tables(ctx, h); }))) return rc;
     ctx->stats.set_model_ms = ms_since(t0);
     return FV_OK;
 }
 
 namespace fvi {
 
+PointerPlace pointer_place(const void *p)
+{
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return { false, -1 }; }
+    return { at.type == hipMemoryTypeDevice, at.device };
+}
+
+int emis_refusal(fv_ctx *ctx, const char *who, unsigned long long where, long long t_base)
+{
+    const unsigned long long K = (unsigned long long)ctx->K;
+    std::string cls;
+    if (ctx->emis_P) {                                      // which score of the caller's row that was
+        int p = -1;
+        FV_HIP(hipMemcpy(&p, ctx->EMap.p + where % K, sizeof p, hipMemcpyDeviceToHost));
+        cls = ", class = " + std::to_string(p);
+    }
+    ctx->detail = std::string(who) + ": the score at (t = " + std::to_string(t_base + (long long)(where / K)) + ", state = " +
+                  std::to_string(where % K) + cls + ") is NaN, +inf or beyond the float32 range; scores are finite or -inf";
+    return FV_ERR_ARG;
+}
+
 // fv_set_emissions on one device.  A block the kernel cannot read where it lies (host memory; a multi-device context,
 // whose members each take a copy) goes into a raw device buffer first, released before the call returns.
-static int stage_emissions_on(fv_ctx *ctx, const void *scores, int dtype, int T, long long ld, bool in_place)
+static int stage_emissions_on(fv_ctx *ctx, const EmisBlock &b, bool in_place)
 {
     FV_HIP(hipSetDevice(ctx->device));
-    const size_t K = (size_t)ctx->K, esz = emis_elem_size[dtype], cells = (size_t)T * K;
-    const size_t width = ctx->emis_P ? (size_t)ctx->emis_P : K;                            // scores of a row: P through a map
-    const size_t raw_bytes = in_place ? 0 : ((size_t)(T - 1) * (size_t)ld + width) * esz;  // (the last row ends at its last score)
+    const size_t cells = (size_t)b.n * (size_t)ctx->K, raw_bytes = in_place ? 0 : emis_raw_bytes(ctx, b);
     {   // sized in 64 bits and compared with the free device memory before anything is allocated
         unsigned long long grow = raw_bytes, released = 0;
         if (cells > ctx->E32.n) { grow += 4ull * cells; released += ctx->E32.bytes(); }
@@ -812,31 +547,19 @@ static int stage_emissions_on(fv_ctx *ctx, const void *scores, int dtype, int T,
     FV_HIP(ctx->E64.ensure(cells));
     FV_HIP(ctx->d_emflags.ensure(2));
     DevBuf<unsigned char> raw;
-    const void *src = scores;
-    if (!in_place) {
-        FV_HIP(raw.ensure(raw_bytes));
-        FV_HIP(hipMemcpyAsync(raw.p, scores, raw_bytes, hipMemcpyDefault, ctx->stream));
-        src = raw.p;
-    }
+    if (!in_place) FV_HIP(raw.ensure(raw_bytes));
     unsigned long long got[2] = { 0ull, ~0ull };
-    FV_HIP(hipMemsetAsync(ctx->d_emflags.p, 0, sizeof(unsigned long long), ctx->stream));               // no flag
-    FV_HIP(hipMemsetAsync(ctx->d_emflags.p + 1, 0xFF, sizeof(unsigned long long), ctx->stream));        // no refused index
-    if (int rc = launch_stage_emissions(ctx, src, dtype, ld, T, ctx->EMap.p, ctx->emis_P, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p)) return rc;
+    auto reset = [&]() -> int {
+        FV_HIP(hipMemsetAsync(ctx->d_emflags.p, 0, sizeof(unsigned long long), ctx->stream));               // no flag
+        FV_HIP(hipMemsetAsync(ctx->d_emflags.p + 1, 0xFF, sizeof(unsigned long long), ctx->stream));        // no refused index
+        return 0;
+    };
+    if (int rc = stage_block(ctx, b, raw.p, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p, reset)) return rc;
     FV_HIP(hipMemcpyAsync(got, ctx->d_emflags.p, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
     FV_HIP(hipStreamSynchronize(ctx->stream));              // the one sync of the call: copies and kernel are done, `raw` can go
-    if (got[0] & FV_EMIS_BAD) {
-        std::string cls;
-        if (ctx->emis_P) {                                  // which score of the caller's row that was
-            int p = -1;
-            FV_HIP(hipMemcpy(&p, ctx->EMap.p + got[1] % K, sizeof p, hipMemcpyDeviceToHost));
-            cls = ", class = " + std::to_string(p);
-        }
-        ctx->detail = "fv_set_emissions: the score at (t = " + std::to_string(got[1] / K) + ", state = " + std::to_string(got[1] % K) + cls +
-                      ") is NaN, +inf or beyond the float32 range; scores are finite or -inf";
-        return FV_ERR_ARG;
-    }
+    if (got[0] & FV_EMIS_BAD) return emis_refusal(ctx, "fv_set_emissions", got[1], 0);
     ctx->emis_positive = (got[0] & FV_EMIS_POSITIVE) != 0;
-    ctx->emis_rows = T;
+    ctx->emis_rows = b.n;
     return FV_OK;
 }
 
@@ -846,39 +569,28 @@ extern "C" int fv_set_emissions(fv_ctx *ctx, const void *scores, int dtype, int 
 {
     if (!ctx) return FV_ERR_ARG;
     FV_NO_STREAM(ctx);
-    const int n = fvi::group_size(ctx);
-    for (int r = 0; r < n; ++r) {                // whatever happens next, the rows staged before are gone
-        fv_ctx *m = fvi::group_member(ctx, r);
-        m->emis_rows = 0; m->emis_positive = false;
-    }
-    ctx->stats.emission_rows = 0;
-    ctx->stats.set_emissions_ms = 0.0;           // (a refused call staged nothing: no time to report)
+    fvi::drop_group_emissions(ctx, false, true);      // whatever happens next, the rows staged before are gone
     if (ctx->K == 0) { ctx->detail = "fv_set_emissions: no model (the row length K is the model's)"; return FV_ERR_STATE; }
-    if (!scores || T < 1 || ld < (ctx->emis_P ? ctx->emis_P : ctx->K) || ld > (1ll << 59) / T || !fvi::emis_dtype_ok(dtype)) {
+    const fvi::EmisBlock b{ scores, dtype, T, ld };
+    if (!fvi::emis_block_ok(ctx, b)) {
         ctx->detail = "fv_set_emissions: scores != NULL, T >= 1, ld >= K (ld >= P while an emission map is set) and dtype "
                       "FV_EMIS_LOG_F32, _F64, _F16 or _BF16";
         return FV_ERR_ARG;
     }
     auto t0 = clk::now();
-    // where the block lies: a pointer the runtime does not know (plain malloc) makes the query fail — that is host memory
-    hipPointerAttribute_t at{};
-    bool on_device = false;
-    if (hipPointerGetAttributes(&at, scores) == hipSuccess) on_device = at.type == hipMemoryTypeDevice;
-    else (void)hipGetLastError();
-    for (int r = 0; r < n; ++r) {
-        fv_ctx *m = fvi::group_member(ctx, r);
-        const bool in_place = on_device && n == 1 && at.device == m->device;
-        const int rc = fvi::drained(m, fvi::stage_emissions_on(m, scores, dtype, T, ld, in_place));
-        if (rc) {
-            if (m != ctx) ctx->detail = m->detail;
-            for (int q = 0; q < n; ++q) fvi::group_member(ctx, q)->emis_rows = 0;
-            ctx->stats.device_bytes = (long long)fvi::device_bytes(ctx);      // the tables may have grown before the refusal
-            return rc;
-        }
+    const fvi::PointerPlace at = fvi::pointer_place(scores);
+    const bool single = fvi::group_size(ctx) == 1;
+    const int rc = fvi::for_each_member(ctx, [&](fv_ctx *ctx) {
+        const bool in_place = at.on_device && single && at.device == ctx->device;
+        return fvi::drained(ctx, fvi::stage_emissions_on(ctx, b, in_place));
+    });
+    ctx->stats.device_bytes = (long long)fvi::device_bytes(ctx);          // (after a refusal too: the tables may have grown before it)
+    if (rc) {
+        fvi::for_each_member(ctx, [](fv_ctx *m) { m->emis_rows = 0; return 0; });
+        return rc;
     }
     ctx->stats.set_emissions_ms = ms_since(t0);
     ctx->stats.emission_rows = T;
-    ctx->stats.device_bytes = (long long)fvi::device_bytes(ctx);
     return FV_OK;
 }
 
@@ -892,9 +604,7 @@ extern "C" int fv_set_emission_map(fv_ctx *ctx, const int *pdf_of_state, int P)
     if (!pdf_of_state && P != 0) { ctx->detail = "fv_set_emission_map: pdf_of_state == NULL clears the map and takes P == 0"; return FV_ERR_ARG; }
     if (pdf_of_state) {
         if (P < 1) { ctx->detail = "fv_set_emission_map: P >= 1 score classes with a map"; return FV_ERR_ARG; }
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, pdf_of_state) != hipSuccess) (void)hipGetLastError();      // (plain host memory)
-        else if (at.type == hipMemoryTypeDevice) {
+        if (fvi::pointer_place(pdf_of_state).on_device) {
             ctx->detail = "fv_set_emission_map: pdf_of_state is a device pointer; the map is read on the host";
             return FV_ERR_ARG;
         }
@@ -905,31 +615,15 @@ extern "C" int fv_set_emission_map(fv_ctx *ctx, const int *pdf_of_state, int P)
                 return FV_ERR_ARG;
             }
     }
-    const int n = fvi::group_size(ctx);
-    auto unset = [&] {
-        for (int r = 0; r < n; ++r) {
-            fv_ctx *m = fvi::group_member(ctx, r);
-            m->emis_rows = 0; m->emis_positive = false; m->emis_P = 0;
-        }
-        ctx->stats.emission_rows = 0;
-        ctx->stats.set_emissions_ms = 0.0;
-    };
-    unset();
-    int rc = FV_OK;
-    for (int r = 0; r < n && rc == FV_OK; ++r) {
-        fv_ctx *m = fvi::group_member(ctx, r);
-        rc = [&]() -> int {
-            fv_ctx *ctx = m;                     // (FV_HIP reports into the member)
-            FV_HIP(hipSetDevice(ctx->device));
-            if (!pdf_of_state) { ctx->EMap.release(); return FV_OK; }
-            FV_HIP(ctx->EMap.ensure((size_t)ctx->K));
-            FV_HIP(hipMemcpy(ctx->EMap.p, pdf_of_state, (size_t)ctx->K * sizeof(int), hipMemcpyHostToDevice));
-            ctx->emis_P = P;
-            return FV_OK;
-        }();
-        if (rc && m != ctx) ctx->detail = m->detail;
-    }
-    if (rc) unset();                             // an upload failed: no map anywhere, nothing staged
+    fvi::drop_group_emissions(ctx, true, true);
+    const int rc = fvi::for_each_member(ctx, [&](fv_ctx *ctx) -> int {
+        FV_HIP(hipSetDevice(ctx->device));
+        if (!pdf_of_state) { ctx->EMap.release(); return FV_OK; }
+        if (int up = fvi::upload(ctx, ctx->EMap, pdf_of_state, (size_t)ctx->K)) return up;
+        ctx->emis_P = P;
+        return FV_OK;
+    });
+    if (rc) fvi::drop_group_emissions(ctx, true, true);      // an upload failed: no map anywhere, nothing staged
     ctx->stats.device_bytes = (long long)fvi::device_bytes(ctx);
     return rc;
 }
@@ -938,14 +632,8 @@ extern "C" int fv_clear_emissions(fv_ctx *ctx)
 {
     if (!ctx) return FV_ERR_ARG;
     FV_NO_STREAM(ctx);
-    const int n = fvi::group_size(ctx);
-    for (int r = 0; r < n; ++r) {
-        fv_ctx *m = fvi::group_member(ctx, r);
-        (void)hipSetDevice(m->device);
-        m->emis_rows = 0; m->emis_positive = false;
-        m->E32.release(); m->E64.release();
-    }
-    ctx->stats.emission_rows = 0;
+    fvi::drop_group_emissions(ctx, false, false);
+    fvi::for_each_member(ctx, [](fv_ctx *m) { (void)hipSetDevice(m->device); m->E32.release(); m->E64.release(); return 0; });
     ctx->stats.device_bytes = (long long)fvi::device_bytes(ctx);
     return FV_OK;
 }
@@ -977,16 +665,13 @@ extern "C" int fv_test_device_free(fv_ctx *ctx, void *p)
 // include/flashvit_testing.h: the staging kernel alone between two device events, reps launches back to back
 extern "C" int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, int dtype, int T, long long ld, int reps, float *ms_out)
 {
-    if (!ctx || !ms_out || !dev_scores || T < 1 || reps < 1 || ctx->K == 0 || ld < (ctx->emis_P ? ctx->emis_P : ctx->K) ||
-        ld > (1ll << 59) / T || !fvi::emis_dtype_ok(dtype) || ctx->group)
-        return FV_ERR_ARG;
+    const fvi::EmisBlock b{ dev_scores, dtype, T, ld };
+    if (!ctx || !ms_out || reps < 1 || ctx->K == 0 || !fvi::emis_block_ok(ctx, b) || ctx->group) return FV_ERR_ARG;
     FV_NO_STREAM(ctx);
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, dev_scores) != hipSuccess) { (void)hipGetLastError(); return FV_ERR_ARG; }
-    if (at.type != hipMemoryTypeDevice || at.device != ctx->device) return FV_ERR_ARG;
+    const fvi::PointerPlace at = fvi::pointer_place(dev_scores);
+    if (!at.on_device || at.device != ctx->device) return FV_ERR_ARG;
     FV_HIP(hipSetDevice(ctx->device));
-    ctx->emis_rows = 0; ctx->emis_positive = false;         // the tables are overwritten: nothing stays staged
-    ctx->stats.emission_rows = 0;
+    fvi::drop_group_emissions(ctx, false, false);           // the tables are overwritten: nothing stays staged
     const size_t cells = (size_t)T * (size_t)ctx->K;
     FV_HIP(ctx->E32.ensure(cells));
     FV_HIP(ctx->E64.ensure(cells));
@@ -997,10 +682,11 @@ extern "C" int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, i
     struct Ev { hipEvent_t &a, &b; ~Ev() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev{ e0, e1 };
     FV_HIP(hipEventCreate(&e0));
     FV_HIP(hipEventCreate(&e1));
-    if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T, ctx->EMap.p, ctx->emis_P, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p)) return fvi::drained(ctx, rc);      // warm
+    auto keep = [] { return 0; };           // (the words were reset above and are not judged)
+    if (int rc = fvi::stage_block(ctx, b, nullptr, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p, keep)) return fvi::drained(ctx, rc);      // warm
     FV_HIP(hipEventRecord(e0, ctx->stream));
     for (int r = 0; r < reps; ++r)
-        if (int rc = fvi::launch_stage_emissions(ctx, dev_scores, dtype, ld, T, ctx->EMap.p, ctx->emis_P, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p)) return fvi::drained(ctx, rc);
+        if (int rc = fvi::stage_block(ctx, b, nullptr, ctx->E32.p, ctx->E64.p, ctx->d_emflags.p, keep)) return fvi::drained(ctx, rc);
     FV_HIP(hipEventRecord(e1, ctx->stream));
     FV_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0.0f;
@@ -1018,16 +704,9 @@ extern "C" int fv_test_flat_poison(fv_ctx *ctx, int t)
     return FV_OK;
 }
 
-extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
+// one member's option
+static int set_option_on(fv_ctx *ctx, int key, long long value)
 {
-    if (!ctx) return FV_ERR_ARG;
-    FV_NO_STREAM(ctx);
-    if (ctx->group && ctx->group_rank == 0) {          // a multi-device context: the same option on every member
-        for (int r = fvi::group_size(ctx) - 1; r >= 1; --r) {
-            const int rc = fv_set_option(fvi::group_member(ctx, r), key, value);
-            if (rc) return rc;
-        }
-    }
     switch (key) {
     case FV_OPT_KERNEL:
         // (FV_KERNEL_SPARSE_CSR is reported, never chosen)
@@ -1062,6 +741,15 @@ extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
         ctx->opt_debug = (int)(value & 0x3fffffff); return FV_OK;
     default: return FV_ERR_ARG;
     }
+}
+
+extern "C" int fv_set_option(fv_ctx *ctx, int key, long long value)
+{
+    if (!ctx) return FV_ERR_ARG;
+    FV_NO_STREAM(ctx);
+    if (ctx->group && ctx->group_rank != 0) return set_option_on(ctx, key, value);
+    // the handle of a multi-device context: the same option on every member, itself last
+    return fvi::for_each_member(ctx, [&](fv_ctx *ctx) -> int { FV_NO_STREAM(ctx); return set_option_on(ctx, key, value); }, true);
 }
 
 extern "C" long long fv_checkpoint_memory_bytes(int K, int T, int step)

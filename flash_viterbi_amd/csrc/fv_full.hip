@@ -887,13 +887,12 @@ static void launch_stage_as(fv_ctx *ctx, const void *src, long long ld, int T, c
                            static_cast<const TIN *>(src), ld, T, ctx->K, map, E32, E64, flags);
 }
 
-// map != NULL (P > 0): the tied form, rows of P scores gathered through the K entries of map
-int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T, const int *map, int P,
-                           float *E32, double *E64, unsigned long long *flags)
+// while an emission map is set: the tied form, rows of P scores gathered through the K entries of the map
+int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T, float *E32, double *E64, unsigned long long *flags)
 {
     const int K = ctx->K;
     const int gx = std::min((K + fvk::EMIS_BLOCK - 1) / fvk::EMIS_BLOCK, 2048), gy = std::max(1, std::min(T, 2048 / gx));
-    if (P <= 0) map = nullptr;
+    const int *map = ctx->emis_P > 0 ? ctx->EMap.p : nullptr;
     switch (dtype) {
     case FV_EMIS_LOG_F64: launch_stage_as<double>(ctx, src, ld, T, map, dim3(gx, gy), E32, E64, flags); break;
     case FV_EMIS_LOG_F32: launch_stage_as<float>(ctx, src, ld, T, map, dim3(gx, gy), E32, E64, flags); break;
@@ -992,7 +991,7 @@ int admit_full(fv_ctx *ctx, const int *ob, int T, int &kernel)
             return FV_ERR_UNSUPPORTED;
         }
         if (!f64 && !ctx->view.logs_nonpositive) {
-            ctx->detail = fvi::CSR_FILTER_RANGE_DETAIL;
+            ctx->detail = fvi::filter_range_detail(ctx);
             return FV_ERR_UNSUPPORTED;
         }
         for (int j = 0; ob && j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
@@ -1017,7 +1016,7 @@ int admit_full(fv_ctx *ctx, const int *ob, int T, int &kernel)
     }
     for (int j = 0; ob && j < T; ++j) if (ob[j] < 0 || ob[j] >= ctx->view.nsym) return FV_ERR_ARG;
     if (ctx->opt_kernel >= FV_KERNEL_F32_REFINE && !ctx->view.logs_nonpositive) {
-        ctx->detail = fvi::FILTER_RANGE_DETAIL;
+        ctx->detail = fvi::filter_range_detail(ctx);
         return FV_ERR_UNSUPPORTED;
     }
     FV_HIP(hipSetDevice(ctx->device));

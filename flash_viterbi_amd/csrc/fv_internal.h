@@ -1,6 +1,7 @@
 // fv_internal.h — what the translation units of libflashvit.so share: the context behind the opaque fv_ctx of
 // include/flashvit.h, device buffers, the error macro and the few functions that cross a seam.
-//   fv_context.hip  fv_create / fv_destroy / fv_set_model / options / statistics, workspace, batch admission, decode epilogue
+//   fv_context.hip  fv_create / fv_destroy / options / statistics, workspace, batch admission, decode epilogue, model upload, emission staging
+//   fv_model.cpp    the host-only model builders of fv_set_model / fv_set_model_sparse (value checks, logs, table encodings)
 //   fv_full.hip     full-state kernels and their decode drivers (FLASH, vanilla, checkpoint)
 //   fv_beam.hip     FLASH-BS kernels and their decode driver
 //   fv_comm.hip     multi-GPU: partition, RCCL all-gather, merge, the single-process multi-device context
@@ -289,7 +290,7 @@ struct FvTestRecording {
         }                                                                                                     \
     } while (0)
 
-constexpr int FV_NCOUNTERS = 17;   // device statistics words (fv_kernels.hip.inc / fv_beam_kernels.hip.inc say which is which)
+constexpr int FV_NCOUNTERS = fvk::NCOUNTERS;   // device statistics words (fv_layout.h names them)
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline int fv_ldq(int K) { return round_up(K, 128); }         // pitch of the row-major 16-bit table
@@ -309,8 +310,19 @@ struct HostTables {
     float window16 = 0.0f, windowq = 0.0f, qscale = -1.0f;
     double density = 1.0;
 };
+// what fv_set_model_sparse computes on the host: everything is O(nnz + K * M)
+struct HostCsr {
+    HostTables e;                        // K, M, nrows, ntiles, log B / log Pi, windowq, qscale, density, any_big
+    std::vector<uint4> ck;               // CSC-32 table (fv_kernels.hip.inc, trellis_step_csr)
+    std::vector<uint2> cq;
+    std::vector<double> c64, rlog;       // rlog: the log of every stored entry, in the caller's order
+    std::vector<long long> off;
+    std::vector<int> nwb;
+};
+// fv_model.cpp: the two builders, host code only.  A refusal (FV_ERR_ARG) leaves its sentence in `detail`.
 int build_host_tables(const float *A, const float *B, const float *Pi, int K, int M, HostTables &h, std::string &detail);
-int upload_tables(fv_ctx *ctx, const HostTables &h);
+int build_host_csr(const long long *row_ptr, const int *col, const float *val, const float *B, const float *Pi, int K, int M,
+                   HostCsr &h, std::string &detail);
 
 size_t device_bytes(const fv_ctx *c);
 // A workspace request: buffers and the elements each is wanted to hold.  A batch decode names itself (`what`) and its
@@ -354,16 +366,39 @@ int drained(fv_ctx *ctx, int rc);
 // model's log B.  ob == NULL: the T rows fv_set_emissions staged (FV_ERR_ARG if there are fewer), and ob is pointed at
 // 0 .. T-1, which the rest of the decode handles as any observation sequence.
 int emission_view(fv_ctx *ctx, const int *&ob, long long T);
-// fvk::stage_emissions lives with the full-state kernels (fv_full.hip); fv_set_emissions launches it through here
+// fvk::stage_emissions lives with the full-state kernels (fv_full.hip); stage_block launches it through here
 enum { FV_EMIS_BAD = 1, FV_EMIS_POSITIVE = 2 };
-// (map: the device copy of the emission map and P its class count for the tied form; NULL / 0 without a map)
-// E32 / E64: the two tables the rows go to, flags: the two words the value rules report into (fv_set_emissions: the
-// context's; a stream: its own chunk tables)
-int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T, const int *map, int P,
-                           float *E32, double *E64, unsigned long long *flags);
-// fv_set_emissions' argument rules (dtype, element sizes), shared with fv_stream_push_emissions
+// (through the context's emission map while one is set: the tied form)  E32 / E64: the two tables the rows go to, flags: the
+// two words the value rules report into (fv_set_emissions: the context's; a stream: its own chunk tables)
+int launch_stage_emissions(fv_ctx *ctx, const void *src, int dtype, long long ld, int T, float *E32, double *E64, unsigned long long *flags);
+// Staging a block of emission scores: the one path of fv_set_emissions, a stream's score-row push and
+// fv_test_stage_emissions_ms.  n rows of K scores (P while an emission map is set) at row pitch ld, in elements of dtype.
+struct EmisBlock { const void *scores; int dtype; int n; long long ld; };
 constexpr size_t emis_elem_size[4] = { 4, 8, 2, 2 };      // by FV_EMIS_LOG_F32, _F64, _F16, _BF16
-inline bool emis_dtype_ok(int dtype) { return dtype >= FV_EMIS_LOG_F32 && dtype <= FV_EMIS_LOG_BF16; }
+inline size_t emis_width(const fv_ctx *ctx) { return ctx->emis_P ? (size_t)ctx->emis_P : (size_t)ctx->K; }    // scores of a row
+// the argument rule (each caller words its own refusal)
+inline bool emis_block_ok(const fv_ctx *ctx, const EmisBlock &b)
+{
+    return b.scores && b.n >= 1 && b.ld >= (long long)emis_width(ctx) && b.ld <= (1ll << 59) / b.n && b.dtype >= FV_EMIS_LOG_F32 &&
+           b.dtype <= FV_EMIS_LOG_BF16;
+}
+// bytes of the raw copy of a block the kernel cannot read where it lies (the last row ends at its last score)
+inline size_t emis_raw_bytes(const fv_ctx *ctx, const EmisBlock &b) { return ((size_t)(b.n - 1) * (size_t)b.ld + emis_width(ctx)) * emis_elem_size[b.dtype]; }
+// where a caller's block lies; a pointer the runtime does not know (plain malloc) makes the query fail: host memory
+struct PointerPlace { bool on_device; int device; };
+PointerPlace pointer_place(const void *p);
+// raw != NULL: the block is copied there first (emis_raw_bytes of the caller's, kept until the stream has drained); then
+// reset_flags(), the caller's way of resetting the two words it owns; then the staging launch into E32 / E64, the value rules
+// reporting into flags[2].  All on ctx->stream, no sync: reading the words back is the caller's.
+template <class Reset>
+int stage_block(fv_ctx *ctx, const EmisBlock &b, unsigned char *raw, float *E32, double *E64, unsigned long long *flags, Reset &&reset_flags)
+{
+    if (raw) FV_HIP(hipMemcpyAsync(raw, b.scores, emis_raw_bytes(ctx, b), hipMemcpyDefault, ctx->stream));
+    if (int rc = reset_flags()) return rc;
+    return launch_stage_emissions(ctx, raw ? raw : b.scores, b.dtype, b.ld, b.n, E32, E64, flags);
+}
+// refuses the score at staged index `where` (row * K + state, rows counted from time t_base) in who's name: FV_ERR_ARG
+int emis_refusal(fv_ctx *ctx, const char *who, unsigned long long where, long long t_base);
 // decode prologue: observation sequence to the device (through the pinned block), counters and answers cleared
 int begin_decode(fv_ctx *ctx, const int *ob, int T);
 // big-LDS attributes of the kernels each translation unit owns
@@ -388,6 +423,7 @@ constexpr const char *FILTER_RANGE_DETAIL = "the filter+refine kernels need ever
 constexpr const char *CSR_FILTER_RANGE_DETAIL =
     "fv_set_model_sparse: the walk over the stored entries is a filter kernel and needs every model entry in [0,1] "
     "(and every staged emission score <= 0); FV_KERNEL_CSR_F64 decodes such input";
+inline const char *filter_range_detail(const fv_ctx *ctx) { return ctx->csr ? CSR_FILTER_RANGE_DETAIL : FILTER_RANGE_DETAIL; }
 // frees an open stream's buffers (fv_destroy, close, abort)
 void stream_drop(fv_ctx *ctx);
 // fv_comm.hip

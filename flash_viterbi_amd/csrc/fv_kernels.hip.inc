@@ -505,7 +505,7 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step(const StepArgs<NB> args
             if (kind[t] == 1) {
                 r = exact_cell(tmp[t], t1_at<NB>(T1s, a1[t], t), Lc[t]);
                 kb = a1[t];
-                if (m1[t] != M1v[t]) atomicAdd(&args.counters[0], 1ull);
+                if (m1[t] != M1v[t]) atomicAdd(&args.counters[CNT_REFINE_NEAR], 1ull);
             } else if (kind[t] == 3) {
                 r = m1[t]; kb = a1[t];                    // timing-only build: no refine
             }
@@ -553,7 +553,7 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step(const StepArgs<NB> args
                     if (better(ov, ok, bx, bk)) { bx = ov; bk = ok; }
                 }
                 if (lane == L) { rr[t] = bx; rk[t] = bk; }
-                if (lane == 0) atomicAdd(&args.counters[1], 1ull);
+                if (lane == 0) atomicAdd(&args.counters[CNT_REFINE_RESCAN], 1ull);
             }
         }
 #pragma unroll
@@ -999,7 +999,7 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
                 thrs[t] = thr;
                 if (thr >= 65535u) {                              // saturated sums could matter: exact walk of every row
                     kind[t] = 2;
-                    if (w == 0 && rg == 0) atomicAdd(&args.counters[8], 1ull);      // statistics: columns that took this branch
+                    if (w == 0 && rg == 0) atomicAdd(&args.counters[CNT_REFINE_SATURATED], 1ull);      // statistics: columns that took this branch
                 }
                 else if (m2[t] <= thr) kind[t] = 2;
                 else if (m1[t] <= thr && a1[t] >= 0) kind[t] = 1;
@@ -1041,7 +1041,7 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
             if (kind[t] == 1) {
                 r = exact_cell(tmp[t], tv[t], Lc[t]);
                 kb = a1[t];
-                if (m1[t] != Zc[t]) atomicAdd(&args.counters[0], 1ull);
+                if (m1[t] != Zc[t]) atomicAdd(&args.counters[CNT_REFINE_NEAR], 1ull);
             }
             rr[t] = r; rk[t] = kb;
         }
@@ -1089,7 +1089,7 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
                     if (better(ov, ok, bx, bk)) { bx = ov; bk = ok; }
                 }
                 if (lane == L) { rr[t] = bx; rk[t] = bk; }
-                if (lane == 0) atomicAdd(&args.counters[1], 1ull);
+                if (lane == 0) atomicAdd(&args.counters[CNT_REFINE_RESCAN], 1ull);
             }
         }
     }
@@ -1315,7 +1315,7 @@ __global__ __launch_bounds__(SP_BLOCK) void trellis_step_sparse(const SparseArgs
         if (kind[t] == 1) {
             r = exact_cell(tmp[t], t1_at<NB>(T1s, a1[t], t), Lc[t]);
             kb = a1[t];
-            if (m1[t] != M1v[t]) atomicAdd(&args.counters[0], 1ull);
+            if (m1[t] != M1v[t]) atomicAdd(&args.counters[CNT_REFINE_NEAR], 1ull);
         } else if (kind[t] == 3) {
             r = m1[t]; kb = a1[t];
         } else if (kind[t] == 2) {
@@ -1341,7 +1341,7 @@ __global__ __launch_bounds__(SP_BLOCK) void trellis_step_sparse(const SparseArgs
                 }
                 }
             }
-            atomicAdd(&args.counters[1], 1ull);
+            atomicAdd(&args.counters[CNT_REFINE_RESCAN], 1ull);
         }
         rr[t] = r; rk[t] = kb;
     }
@@ -1546,13 +1546,13 @@ __global__ __launch_bounds__(SP_BLOCK) void trellis_step_csr(const CsrArgs<NB> a
                         }
                     }
                 }
-                atomicAdd(&args.counters[1], 1ull);
+                atomicAdd(&args.counters[CNT_REFINE_RESCAN], 1ull);
             } else if (m1[t] >= thr && e1[t] >= 0) {
                 const size_t pos = 4 * (v0 + vec(e1[t] >> 2)) + (e1[t] & 3);
                 const int k = (int)kw[pos];
                 r = exact_cell(tmp[t], score1(k, t), args.c64[pos]);
                 kbest = k;
-                if (m1[t] != M1) atomicAdd(&args.counters[0], 1ull);
+                if (m1[t] != M1) atomicAdd(&args.counters[CNT_REFINE_NEAR], 1ull);
             }
         }
         rr[t] = r; rk[t] = kbest;

@@ -32,8 +32,17 @@ struct PassChunk { int n; PassDesc p[PASS_CHUNK]; };
 struct FlatDesc { int L, R, generation, chain; long long arg_row; };
 constexpr int FLAT_MAX_GENS = 40;          // (a generation halves the pass length: T < 2^31 has at most 32)
 struct FlatGens { int ngen; int begin[FLAT_MAX_GENS + 1]; };   // passes [begin[g], begin[g + 1]) are generation g + 1
-constexpr int FLAT_COUNTER = 15;           // device statistics word of the resolver: first-miss generation << 32 | missed passes
-constexpr int BT_COUNTER = 16;             // device statistics word of the back-tracks: passes through the retry branch of the chunk walk (fv_stats.bt_restarts)
+// The device statistics words (ctx->d_counters), named after the fv_stats field each one feeds (read_stats, fv_context.hip).
+enum : int {
+    CNT_REFINE_NEAR = 0, CNT_REFINE_RESCAN, CNT_BEAM_EXACT_SETS, CNT_BEAM_DUP_COLS, CNT_BEAM_DUP_STEPS,
+    CNT_HANDSHAKE_TIMEOUT,                 // = 5: a heap replay's producer / consumer hand-shake timed out (FV_ERR_DEVICE, no field)
+    CNT_BEAM_TIES, CNT_BEAM_CAND_SELECTS, CNT_REFINE_SATURATED, CNT_BEAM_SPEC_STEPS, CNT_BEAM_REACH_EVENTS, CNT_BEAM_LIST_SHORT,
+    CNT_BEAM_LIST_LONG, CNT_BEAM_LIST_ENTRIES, CNT_BEAM_CHAIN_CUTS,
+    FLAT_COUNTER,                          // = 15, the resolver: first-miss generation << 32 | missed passes
+    BT_COUNTER,                            // = 16, the back-tracks: passes through the retry branch of the chunk walk (fv_stats.bt_restarts)
+    NCOUNTERS
+};
+static_assert(CNT_HANDSHAKE_TIMEOUT == 5 && FLAT_COUNTER == 15 && BT_COUNTER == 16 && NCOUNTERS == 17, "the words keep their places");
 
 // LDS of one trellis_step / trellis_step_u16 workgroup (score rows + reduction scratch)
 template <int NB>

@@ -336,8 +336,8 @@ extern "C" int fv_stream_push_emissions(fv_ctx *ctx, const void *scores, int dty
     if (!ctx) return FV_ERR_ARG;
     if (int rc = push_admission(ctx, who, scores, n, path_out, committed_out, fv_stream::SCORES)) return rc;
     fv_stream *s = ctx->strm;
-    const size_t K = (size_t)ctx->K, width = ctx->emis_P ? (size_t)ctx->emis_P : K;
-    if (ld < (long long)width || ld > (1ll << 59) / n || !fvi::emis_dtype_ok(dtype)) {
+    const fvi::EmisBlock b{ scores, dtype, n, ld };
+    if (!fvi::emis_block_ok(ctx, b)) {
         ctx->detail = std::string(who) + ": ld >= K (ld >= P while an emission map is set) and dtype FV_EMIS_LOG_F32, _F64, _F16 or _BF16";
         return FV_ERR_ARG;
     }
@@ -345,42 +345,27 @@ extern "C" int fv_stream_push_emissions(fv_ctx *ctx, const void *scores, int dty
     FV_HIP(hipSetDevice(ctx->device));
     if (int rc = make_room(ctx, n)) return refused(ctx, rc);
     // the chunk tables and, for a block the kernel cannot read where it lies, its raw copy: as fv_set_emissions
-    hipPointerAttribute_t at{};
-    bool in_place = false;
-    if (hipPointerGetAttributes(&at, scores) == hipSuccess) in_place = at.type == hipMemoryTypeDevice && at.device == ctx->device;
-    else (void)hipGetLastError();
-    const size_t cells = (size_t)n * K, raw_bytes = in_place ? 0 : ((size_t)(n - 1) * (size_t)ld + width) * fvi::emis_elem_size[dtype];
+    const fvi::PointerPlace at = fvi::pointer_place(scores);
+    const bool in_place = at.on_device && at.device == ctx->device;
+    const size_t cells = (size_t)n * (size_t)ctx->K, raw_bytes = in_place ? 0 : fvi::emis_raw_bytes(ctx, b);
     if (s->e32.ensure(cells) != hipSuccess || s->e64.ensure(cells) != hipSuccess || s->raw.ensure(raw_bytes) != hipSuccess) {
         (void)hipGetLastError();
         ctx->detail = std::string(who) + ": " + std::to_string(12ull * cells + raw_bytes) + " bytes needed for the staged chunk";
         return refused(ctx, FV_ERR_NOMEM);
     }
-    const void *src = scores;
-    if (!in_place) {
-        FV_HIP(hipMemcpyAsync(s->raw.p, scores, raw_bytes, hipMemcpyDefault, ctx->stream));
-        src = s->raw.p;
-    }
     // the value rules decide whether the push is taken at all: the chunk is staged and its flags are read before any step
-    s->h_ctl->emflags[0] = 0ull; s->h_ctl->emflags[1] = ~0ull;
-    FV_HIP(hipMemcpyAsync(s->ctl.p->emflags, s->h_ctl->emflags, sizeof s->h_ctl->emflags, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = fvi::launch_stage_emissions(ctx, src, dtype, ld, n, ctx->EMap.p, ctx->emis_P, s->e32.p, s->e64.p, s->ctl.p->emflags))
-        return refused(ctx, rc);
+    auto reset = [&]() -> int {
+        s->h_ctl->emflags[0] = 0ull; s->h_ctl->emflags[1] = ~0ull;
+        FV_HIP(hipMemcpyAsync(s->ctl.p->emflags, s->h_ctl->emflags, sizeof s->h_ctl->emflags, hipMemcpyHostToDevice, ctx->stream));
+        return 0;
+    };
+    if (int rc = fvi::stage_block(ctx, b, in_place ? nullptr : s->raw.p, s->e32.p, s->e64.p, s->ctl.p->emflags, reset)) return refused(ctx, rc);
     FV_HIP(hipMemcpyAsync(s->h_ctl->emflags, s->ctl.p->emflags, sizeof s->h_ctl->emflags, hipMemcpyDeviceToHost, ctx->stream));
     FV_HIP(hipStreamSynchronize(ctx->stream));
     const unsigned long long flags = s->h_ctl->emflags[0], where = s->h_ctl->emflags[1];
-    if (flags & fvi::FV_EMIS_BAD) {
-        std::string cls;
-        if (ctx->emis_P) {
-            int p = -1;
-            FV_HIP(hipMemcpy(&p, ctx->EMap.p + where % K, sizeof p, hipMemcpyDeviceToHost));
-            cls = ", class = " + std::to_string(p);
-        }
-        ctx->detail = std::string(who) + ": the score at (t = " + std::to_string(s->times + (long long)(where / K)) + ", state = " +
-                      std::to_string(where % K) + cls + ") is NaN, +inf or beyond the float32 range; scores are finite or -inf";
-        return FV_ERR_ARG;
-    }
+    if (flags & fvi::FV_EMIS_BAD) return fvi::emis_refusal(ctx, who, where, s->times);
     if ((flags & fvi::FV_EMIS_POSITIVE) && s->kernel != FV_KERNEL_F64_STREAM && s->kernel != FV_KERNEL_CSR_F64) {
-        ctx->detail = ctx->csr ? fvi::CSR_FILTER_RANGE_DETAIL : fvi::FILTER_RANGE_DETAIL;
+        ctx->detail = fvi::filter_range_detail(ctx);
         return FV_ERR_UNSUPPORTED;
     }
     s->kind = fv_stream::SCORES;

@@ -96,7 +96,7 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_stream_abort", "fv_stream_last_stats"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select", "fv_test_device_alloc", "fv_test_device_free",
-                "fv_test_stage_emissions_ms", "fv_test_flat_poison", "fv_test_beam_forward"]
+                "fv_test_stage_emissions_ms", "fv_test_flat_poison", "fv_test_beam_forward", "fv_test_model_digest"]
 TIE_TAG = 1 << 30
 # FV_TS_*: select-kernel instantiations reported by test_beam_select
 TS_BITS = {"topb_select<4,listed>": 1 << 0, "topb_select<4,derived>": 1 << 1, "topb_select<16,listed>": 1 << 2,
@@ -197,6 +197,7 @@ def load_library():
     L.fv_merge_paths.argtypes = [ci, ci, ci, vp, vp]
     L.fv_plan_flat.argtypes = [ci, ci, ci, ci, ctypes.POINTER(FlatInfo), ci]
     L.fv_test_flat_poison.argtypes = [vp, ci]
+    L.fv_test_model_digest.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, ctypes.c_char_p, ci]
     L.fv_test_forward.argtypes = [vp, vp, ci, ctypes.POINTER(ForwardPass), ci, vp, vp, ctypes.POINTER(ctypes.c_ulonglong)]
     cf = ctypes.c_float
     L.fv_test_beam_step.argtypes = [vp, ci, ctypes.POINTER(BeamSet), ci, vp, ci, cf, cf, ci, vp, vp, vp, ctypes.POINTER(ci),
@@ -350,6 +351,32 @@ def dense_to_csr(A):
     indptr = np.zeros(A.shape[0] + 1, dtype=np.int64)
     np.cumsum(np.bincount(rows, minlength=A.shape[0]), out=indptr[1:])
     return indptr, cols.astype(np.int32), A[rows, cols]
+
+
+MODEL_DIGESTS_DENSE = ("h64", "h32", "h16", "hq", "sp", "sp_off", "sp_nwb", "b64", "b32", "pi64")
+MODEL_DIGESTS_CSR = ("ck", "cq", "c64", "off", "nwb", "rlog", "b64", "b32", "pi64")
+MODEL_PARAMS = ("window16", "windowq", "qscale", "density", "any_big")
+
+
+def test_model_digest(A, B, Pi):
+    """fv_test_model_digest (no GPU): the host builder of set_model (A: a dense K x K matrix) or of set_model_sparse (A: the
+    tuple (indptr, indices, data)) alone.  Returns (rc, detail, digests, params): the builder's return code and refusal
+    sentence, the FNV-1a digest of every host table by the names of MODEL_DIGESTS_DENSE / _CSR, and MODEL_PARAMS as floats."""
+    B = np.ascontiguousarray(B, dtype=np.float32)
+    Pi = np.ascontiguousarray(Pi, dtype=np.float32)
+    K, M = B.shape
+    if isinstance(A, tuple):
+        indptr, indices, data = (np.ascontiguousarray(a, dtype=t) for a, t in zip(A, (np.int64, np.int32, np.float32)))
+        args, names = (None, _p(indptr), _p(indices), _p(data)), MODEL_DIGESTS_CSR
+    else:
+        A = np.ascontiguousarray(A, dtype=np.float32)
+        assert A.shape == (K, K)
+        args, names = (_p(A), None, None, None), MODEL_DIGESTS_DENSE
+    digests = np.zeros(len(names), dtype=np.uint64)
+    params = np.zeros(len(MODEL_PARAMS), dtype=np.float64)
+    detail = ctypes.create_string_buffer(512)
+    rc = load_library().fv_test_model_digest(*args, _p(B), _p(Pi), K, M, _p(digests), _p(params), detail, len(detail))
+    return rc, detail.value.decode(), dict(zip(names, (int(d) for d in digests))), dict(zip(MODEL_PARAMS, params.tolist()))
 
 
 class FlashViterbi:

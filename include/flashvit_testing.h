@@ -58,6 +58,20 @@ int fv_test_device_free(fv_ctx *ctx, void *p);
  * tools/bench_emissions.py and tools/bench_emissions_tied.py. */
 int fv_test_stage_emissions_ms(fv_ctx *ctx, const void *dev_scores, int dtype, int T, long long ld, int reps, float *ms_out);
 
+/* The host builders of fv_set_model (A != NULL) or fv_set_model_sparse (A == NULL: row_ptr, col, val) alone: no context, no
+ * GPU.  Returns the builder's return code and, of every host table it made, the FNV-1a 64-bit digest of its bytes:
+ *   dense  digests[10]  h64 h32 h16 hq sp sp_off sp_nwb b64 b32 pi64   (the tile-major tables of log A in float64, float32,
+ *                       binary16 and Q16 codes, the CSC-Q16 table with its tile offsets and wave-block counts, log B, log Pi)
+ *   CSR    digests[9]   ck cq c64 off nwb rlog b64 b32 pi64             (source states, codes and logs by destination column,
+ *                       the tiles' offsets and wave-block counts, the logs in the caller's order)
+ *   params[5]           window16, windowq, qscale, density, any_big (0 / 1)
+ *   detail              (may be NULL) the refusal's sentence, at most detail_cap - 1 characters; empty without one.
+ * A table the builder did not make (a refusal, K beyond a kernel's limit) digests as the empty string.  FV_ERR_ARG without
+ * a sentence: a NULL array, K < 1 or M < 1. */
+int fv_test_model_digest(const float *A, const long long *row_ptr, const int *col, const float *val, const float *B,
+                         const float *Pi, int K, int M, unsigned long long *digests, double *params, char *detail,
+                         int detail_cap);
+
 /* One slot set of a beam step: n entries {val[e], state[e]} (states in [0, K)), beam <= n <= beam + 32. */
 typedef struct { const float *val; const int *state; int n; } fv_test_beam_set;
 /* One entry of a candidate list: a score and its destination state. */

@@ -181,3 +181,18 @@ def write_text(spec, out_dir):
 def sha(a):
     import hashlib
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16]
+
+
+def plain_model(K, M, density, seed, scale=1.0, zero_a=False):
+    """Unnormalised float32 (A, B, Pi) with entries in [0, scale), a fraction `density` of A kept, from numpy's PCG64 alone (no arithmetic a numpy build could round differently)."""
+    rng = np.random.default_rng(seed)
+    A = rng.random((K, K), dtype=np.float32)
+    keep = rng.random((K, K), dtype=np.float32) < np.float32(density)
+    A = np.where(keep, A, np.float32(0)).astype(np.float32)
+    B = rng.random((K, M), dtype=np.float32)
+    Pi = rng.random(K, dtype=np.float32)
+    if scale != 1.0:
+        A = (A * np.float32(scale)).astype(np.float32)      # (exact: a power of two)
+    if zero_a:
+        A[:] = 0
+    return A, B, Pi
