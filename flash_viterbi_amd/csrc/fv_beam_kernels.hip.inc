@@ -255,28 +255,13 @@ static inline size_t beam_step_lds(int beam, int nwv = BEAM_WAVES) { return (siz
 // ---------------------------------------------------------------- beam step on the 16-bit table
 
 // Row-major fixed-point copy of log A for beam_step_q16, built on the device from LA64R:
-//   q16_range: lmax = largest finite |log A| (as the bit pattern of a non-negative double: monotone);
-//   q16_rows : step = (float)(lmax / 65534), code = nearbyint(-L / step) (0xffff = -inf), and the largest
-//              |code * step - (-L)| actually made, from which the filter window is taken — the same
-//              construction fv_set_model uses for the dense kernels' table.
-__global__ void q16_range(const double *rm, size_t n, unsigned long long *lmax_bits)
-{
-    double m = 0.0;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-        const double l = rm[e];
-        if (l > -__builtin_huge_val() && -l > m) m = -l;
-    }
-#pragma unroll
-    for (int k = 1; k < 64; k <<= 1) { const double o = __shfl_xor(m, k); m = o > m ? o : m; }
-    if ((threadIdx.x & 63) == 0 && m > 0.0) atomicMax(lmax_bits, (unsigned long long)__double_as_longlong(m));
-}
-
+//   fvk::q16_range: lmax = largest finite |log A|;
+//   q16_rows      : the codes and the largest distance actually made, from which q16_params takes the filter window
+//                   (fvk::q16_step / q16_quantise: the same construction fv_set_model uses for the dense kernels' table).
 __global__ void q16_rows(const double *rm, unsigned short *q, int K, int ld, int ldq, const unsigned long long *lmax_bits,
                          unsigned long long *dmax_bits)
 {
-    const double lmax = __longlong_as_double((long long)*lmax_bits);
-    const float stepf = lmax > 0.0 ? (float)(lmax / 65534.0) : 1.0f;
-    const double stepd = (double)stepf;
+    const double stepd = (double)fvk::q16_step(lmax_bits);
     const size_t n = (size_t)K * ldq;
     double dm = 0.0;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
@@ -284,27 +269,17 @@ __global__ void q16_rows(const double *rm, unsigned short *q, int K, int ld, int
         unsigned short code = 0xFFFFu;
         if (i < K) {
             const double l = rm[(size_t)k * ld + i];
-            if (l > -__builtin_huge_val()) {
-                double c = nearbyint(-l / stepd);
-                c = c < 0.0 ? 0.0 : (c > 65534.0 ? 65534.0 : c);
-                code = (unsigned short)c;
-                const double d = fabs(-c * stepd - l);
-                dm = d > dm ? d : dm;
-            }
+            if (l > -__builtin_huge_val()) code = fvk::q16_quantise(l, stepd, dm);
         }
         q[e] = code;
     }
-#pragma unroll
-    for (int k = 1; k < 64; k <<= 1) { const double o = __shfl_xor(dm, k); dm = o > dm ? o : dm; }
-    if ((threadIdx.x & 63) == 0 && dm > 0.0) atomicMax(dmax_bits, (unsigned long long)__double_as_longlong(dm));
+    fvk::q16_publish_max(dmax_bits, dm);
 }
 
 __global__ void q16_params(const unsigned long long *lmax_bits, const unsigned long long *dmax_bits, float *qpar)
 {
-    const double lmax = __longlong_as_double((long long)*lmax_bits);
-    const float stepf = lmax > 0.0 ? (float)(lmax / 65534.0) : 1.0f;
     const double dmax = __longlong_as_double((long long)*dmax_bits);
-    qpar[0] = -stepf;
+    qpar[0] = -fvk::q16_step(lmax_bits);
     qpar[1] = __uint_as_float(__float_as_uint((float)(2.0 * dmax)) + 1u);      // rounded up
 }
 
@@ -1207,6 +1182,7 @@ __device__ __forceinline__ void patch_doubtful(const ResolveCtx &c, int t, int N
                 const float y = fvk::exact_cell(tmp, sv[sl], csr_log(c.csr, ss[sl], col));
                 if (y > best) { best = y; arg = sl; }
             }
+            // (fvk::wave_argbest, written out as at the dense site below: the selects and beam_resolve keep their instructions)
 #pragma unroll
             for (int m = 1; m < 64; m <<= 1) {
                 const float ov = __shfl_xor(best, m);
@@ -1271,6 +1247,7 @@ __device__ __forceinline__ void patch_doubtful(const ResolveCtx &c, int t, int N
                 }
             }
         }
+        // fvk::wave_argbest written out: the call raises topb_select_cand<8 | 16, .., false> from 56 / 64 to 68 / 76 bytes of scratch
 #pragma unroll
         for (int m = 1; m < 64; m <<= 1) {
             const float ov = __shfl_xor(best, m);
@@ -1649,12 +1626,7 @@ __global__ __launch_bounds__(256) void tie_fixup(const FixArgs args)
                 }
             }
         }
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const float ov = __shfl_xor(best, m);
-            const int ok = __shfl_xor(arg, m);
-            if (fvk::better(ov, ok, best, arg)) { best = ov; arg = ok; }
-        }
+        fvk::wave_argbest(best, arg);
         if (lane == 0 && best > -FLT_MAX) args.bp[(size_t)j * args.K + i] = ss[arg];
     }
     if (per_seq && lane == 0 && mine) atomicAdd(args.total, (unsigned long long)mine);
@@ -1663,7 +1635,7 @@ __global__ __launch_bounds__(256) void tie_fixup(const FixArgs args)
 struct BeamEndArgs {
     int K, beam, n;
     int lazy;          // 1: first attempt, on provisional back-pointers: a tied cell on the path raises the flag of the pass's
-                       //    sequence (flag[p.seq]) and ends the walk
+                       //    sequence (flag[p.seq])
                        // 0: after tie_fixup; runs only if that flag is up
     int *flag;         // one per sequence of the call
     unsigned long long *restarts;      // counter fvk::BT_COUNTER: retries of the chunk walk
@@ -1699,12 +1671,7 @@ __global__ __launch_bounds__(64) void beam_end_backtrack(const BeamEndArgs args,
             const float v = hval[i];
             if (fvk::better(v, i, score, arg)) { score = v; arg = i; }
         }
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const float ov = __shfl_xor(score, m);
-            const int ok = __shfl_xor(arg, m);
-            if (fvk::better(ov, ok, score, arg)) { score = ov; arg = ok; }
-        }
+        fvk::wave_argbest(score, arg);
         stt = hstate[arg];
         if (lane == 0) { ans[p.R] = stt; score_out[p.seq] = score; }
     } else {
@@ -1718,51 +1685,14 @@ __global__ __launch_bounds__(64) void beam_end_backtrack(const BeamEndArgs args,
         stt = __any(found) ? want : -1;
     }
     // state at time j -> state at time j - 1; a tagged (tied) cell yields its provisional state and sets `tag`
-    auto hop = [&](int st, int j, bool &tag) {
+    const bool met_tag = fvk::chunk_walk(p.L, p.R, stt, ans + p.L, args.restarts, [&](int st, int j, bool &tag) {
         if (st < 0) return -1;
         int nx = bp[(size_t)j * args.K + st];
         if (nx >= 0 && (nx & TIE_TAG)) { tag = true; nx &= ~TIE_TAG; }
         return nx;
-    };
-    const int len = p.R - p.L;
-    if (len < fvk::BT_MIN_PARALLEL) {
-        if (lane != 0) return;
-        for (int j = p.R; j > p.L; --j) {
-            bool tag = false;
-            stt = hop(stt, j, tag);
-            if (tag && args.lazy) { atomicExch(flag, 1); return; }      // (not lazy: tie_fixup has rewritten every listed cell)
-            ans[j - 1] = stt;
-        }
-        return;
-    }
-    // long chains: 64 lanes, one chunk of the time axis each, verified chunk by chunk (fvk::backtrack has the argument); a
-    // tagged cell counts only if it lies on a verified chunk
-    const int cs = (len + 63) / 64;
-    auto top = [&](int c) { return max(p.R - c * cs, p.L); };
-    int base = 0, exact = stt;
-    bool met_tag = false;
-    while (base < 64 && top(base) > p.L) {
-        int x = -2, y = -2;
-        bool tag = false;
-        if (lane >= base && top(lane) > p.L) {
-            const int t_hi = top(lane), t_lo = top(lane + 1);
-            int t = min(top(base), t_hi + fvk::BT_WARMUP), st = exact;
-            bool warm_tag = false;
-            for (; t > t_hi; --t) st = hop(st, t, warm_tag);          // (tags met above the chunk belong to the chunk above)
-            x = st;
-            for (; t > t_lo; --t) { st = hop(st, t, tag); ans[t - 1] = st; }
-            y = st;
-        }
-        const int y_above = __shfl_up(y, 1);
-        const bool ok = lane <= base || top(lane) <= p.L || min(top(base), top(lane) + fvk::BT_WARMUP) == top(base) || x == y_above;
-        const unsigned long long bad = ~__ballot(ok);
-        const int f = bad ? __ffsll((long long)bad) - 1 : 64;          // chunks base .. f - 1 are final
-        met_tag |= __any(tag && lane >= base && lane < f);
-        if (!bad) break;
-        if (lane == 0) atomicAdd(args.restarts, 1ull);
-        exact = __shfl(y, f - 1);
-        base = f;
-    }
+    });
+    // (not lazy: tie_fixup has rewritten every listed cell.)  A lazy walk is finished even when it met a tag: what it
+    // wrote below the tagged cell is provisional, and the gated second walk rewrites the whole range.
     if (met_tag && args.lazy && lane == 0) atomicExch(flag, 1);
 }
 

@@ -1027,7 +1027,7 @@ int admit_full(fv_ctx *ctx, const int *ob, int T, int &kernel)
         FV_HIP(ctx->LAQ16.ensure(tab));
         FV_HIP(ctx->d_qaux.ensure(3));
         FV_HIP(hipMemsetAsync(ctx->d_qaux.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL(fvk::q16_tile_range, dim3(2048), dim3(256), 0, ctx->stream, ctx->LA64.p, tab, ctx->d_qaux.p);
+        hipLaunchKernelGGL(fvk::q16_range, dim3(2048), dim3(256), 0, ctx->stream, ctx->LA64.p, tab, ctx->d_qaux.p);
         hipLaunchKernelGGL(fvk::q16_tile_codes, dim3(4096), dim3(256), 0, ctx->stream, ctx->LA64.p, ctx->LAQ16.p, ctx->K, ctx->nrows,
                            ntiles, ctx->d_qaux.p, ctx->d_qaux.p + 1);
         FV_HIP(hipGetLastError());

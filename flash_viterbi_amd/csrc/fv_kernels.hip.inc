@@ -1,5 +1,5 @@
 // fv_kernels.hip.inc — gfx950 kernels of the full-state FLASH Viterbi path.
-// Included by fv_api.hip only.  wave = 64 lanes everywhere in this file.
+// Included by fv_full.hip only (fv_device_common.h holds what the FLASH-BS kernels share).  wave = 64 lanes everywhere in this file.
 //
 // Data layout in HBM (built once by fv_set_model):
 //   LA32 float  (float)log((double)A[k][i])   k = source state (row), i = destination (column)
@@ -86,16 +86,6 @@ struct StepArgs {
     CodeSlot c[NB];
 };
 
-
-__device__ __forceinline__ void wave_best(float &v, int &k)
-{
-#pragma unroll
-    for (int m = 16; m <= 32; m <<= 1) {
-        float ov = __shfl_xor(v, m);
-        int ok = __shfl_xor(k, m);
-        if (better(ov, ok, v, k)) { v = ov; k = ok; }
-    }
-}
 
 // Threshold of the filter kernels.  The streamed value of a cell is y = fl(T1[k] + Lq) (one rounding),
 // the exact one ktmp = fl(fl(tmp + T1[k]) + L) (two roundings); every log is <= 0, so |T1[k] + Lq| and
@@ -233,6 +223,47 @@ __device__ __forceinline__ void unpack_q(const uint4 &v, float (&a)[8])
 __device__ __forceinline__ float tab_load(const float *p) { return *p; }
 __device__ __forceinline__ float tab_load(const half_t *p) { return h2f(p->bits); }
 __device__ __forceinline__ float tab_load(const q16_t *p) { return q2f(p->bits); }
+
+// The kind-2 rescan of trellis_step / trellis_step_u16.  Lane L of this wave holds two candidates of its own inside the
+// window: the whole wave re-walks that lane's rows together, one row per lane, with the reference expression on the
+// float64 entry of EVERY row (a superset of the candidates): one gather latency, no filter pass in front of it.  Lane L's
+// rows are those of the wave's nj row blocks (w, w + NWV, ...: R rows of row group L / 16 in each); rows >= kend are
+// left out.  Two rows per lane and trip, and all loads of a trip — score(k), the incoming score of row k, and the
+// table entries — are requested before the first is used (the rescan is the tail of its launch: a serial loop paid
+// one memory latency per 64 rows).  L64tile: the tile's float64 table (T4 layout) from the first row the kernel numbers 0;
+// tmp: this lane's own log B.  Every lane returns the best (value, row) of lane L's rows.
+template <int R, int NWV, typename Score>
+__device__ __forceinline__ void rescan_lane_rows(const double *L64tile, int L, int nj, int kend, float tmp, Score score, float &bx, int &bk)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int cL = L & (TILE_W - 1), rgL = L >> 4;
+    const float tmpL = __shfl(tmp, L);
+    const int nlane_rows = nj * R;
+    bx = FV_NEG_INF;
+    bk = INT_MAX;
+    for (int e0 = 0; e0 < nlane_rows; e0 += 128) {
+        int kk[2];
+        float tt[2];
+        double LL[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int e = e0 + 64 * u + lane;
+            const int k = (w + NWV * (e / R)) * (4 * R) + rgL * R + (e % R);
+            kk[u] = (e < nlane_rows && k < kend) ? k : -1;
+            const int ks = kk[u] >= 0 ? k : 0;
+            tt[u] = score(ks);
+            LL[u] = L64tile[(size_t)(ks >> 2) * (TILE_W * 4) + cL * 4 + (ks & 3)];
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (kk[u] >= 0) {
+                const float x = exact_cell(tmpL, tt[u], LL[u]);
+                if (better(x, kk[u], bx, bk)) { bx = x; bk = kk[u]; }
+            }
+        }
+    }
+    wave_argbest(bx, bk);
+}
 
 // One trellis step for up to NB independent tasks that share one sweep of the table.
 //
@@ -511,10 +542,8 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step(const StepArgs<NB> args
             }
             rr[t] = r; rk[t] = kb;
         }
-        // Lanes with two candidates of their own inside the window (kind 2): the whole wave re-walks that
-        // lane's rows together, one row per lane, with the reference expression on the float64 entry of
-        // EVERY row (a superset of the candidates): one gather latency, no filter pass in front of it.
-        // Wave-uniform loop over the (rare) lanes that need it.
+        // Lanes with two candidates of their own inside the window (kind 2): rescan_lane_rows over the slab's rows (scores
+        // from the LDS row, every slab row real or a -inf pad).  Wave-uniform loop over the (rare) lanes that need it.
         const double *L64tile = args.LA64 + (size_t)tile * nrows * TILE_W + (size_t)(row_lo >> 2) * (TILE_W * 4);
 #pragma unroll
         for (int t = 0; t < NB; ++t) {
@@ -522,36 +551,9 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step(const StepArgs<NB> args
             while (need) {
                 const int L = __ffsll((long long)need) - 1;
                 need &= need - 1;
-                const int cL = L & (TILE_W - 1), rgL = L >> 4;
-                const float tmpL = __shfl(tmp[t], L);
-                float bx = FV_NEG_INF;
-                int bk = INT_MAX;
-                const int nlane_rows = nj * R;
-                for (int e0 = 0; e0 < nlane_rows; e0 += 128) {         // two rows per lane and trip, both gathers in flight
-                    int kk[2];
-                    double LL[2];
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        const int e = e0 + 64 * u + lane;
-                        const int k = (w + NWV * (e / R)) * RBR + rgL * R + (e % R);
-                        kk[u] = e < nlane_rows ? k : -1;
-                        const int ks = kk[u] >= 0 ? k : 0;
-                        LL[u] = L64tile[(size_t)(ks >> 2) * (TILE_W * 4) + cL * 4 + (ks & 3)];
-                    }
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        if (kk[u] >= 0) {
-                            const float x = exact_cell(tmpL, t1_at<NB>(T1s, kk[u], t), LL[u]);
-                            if (better(x, kk[u], bx, bk)) { bx = x; bk = kk[u]; }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int m = 1; m < 64; m <<= 1) {
-                    const float ov = __shfl_xor(bx, m);
-                    const int ok = __shfl_xor(bk, m);
-                    if (better(ov, ok, bx, bk)) { bx = ov; bk = ok; }
-                }
+                float bx;
+                int bk;
+                rescan_lane_rows<R, NWV>(L64tile, L, nj, srows, tmp[t], [&](int k) { return t1_at<NB>(T1s, k, t); }, bx, bk);
                 if (lane == L) { rr[t] = bx; rk[t] = bk; }
                 if (lane == 0) atomicAdd(&args.counters[CNT_REFINE_RESCAN], 1ull);
             }
@@ -560,11 +562,12 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step(const StepArgs<NB> args
         for (int t = 0; t < NB; ++t) rk[t] = rk[t] != INT_MAX ? rk[t] + row_lo : INT_MAX;       // slab-local row -> row
     }
 
+    // column_fold written out: the call raises trellis_step<double, 8, 2, true, 16> from 100 to 104 bytes of scratch
 #pragma unroll
     for (int t = 0; t < NB; ++t) {
         float r = rr[t];
         int kb = rk[t];
-        wave_best(r, kb);
+        rowgroup_argbest(r, kb);
         if (lane < TILE_W) { redR[(t * TILE_W + c) * NWV + w] = r; redK[(t * TILE_W + c) * NWV + w] = kb; }
     }
     __syncthreads();
@@ -576,9 +579,9 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step(const StepArgs<NB> args
         if (better(fv.y, fk.y, r, kb)) { r = fv.y; kb = fk.y; }
         if (better(fv.z, fk.z, r, kb)) { r = fv.z; kb = fk.z; }
         if (better(fv.w, fk.w, r, kb)) { r = fv.w; kb = fk.w; }
-        wave_best(r, kb);
+        rowgroup_argbest(r, kb);
         if (lane < TILE_W && col < K) {
-            if (args.merge) {              // the slabs below this one: their row is lower, so it stays unless beaten strictly
+            if (args.merge) {             // the slabs below this one: their row is lower, so it stays unless beaten strictly
                 const float pv = args.t[w].t1_out[col];
                 const int pk = args.t[w].bp_out[col];
                 if (pk >= 0 && !(r > pv)) { r = pv; kb = pk; }
@@ -1045,7 +1048,7 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
             }
             rr[t] = r; rk[t] = kb;
         }
-        // kind 2: the whole wave re-walks that lane's rows, one row per lane, with the reference expression
+        // kind 2: rescan_lane_rows over the real rows (k < K), scores from the float row in global memory
         const double *L64tile = args.LA64 + (size_t)tile * nrows * TILE_W;
 #pragma unroll
         for (int t = 0; t < NB; ++t) {
@@ -1053,64 +1056,19 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
             while (need) {
                 const int L = __ffsll((long long)need) - 1;
                 need &= need - 1;
-                const int cL = L & (TILE_W - 1), rgL = L >> 4;
-                const float tmpL = __shfl(tmp[t], L);
                 const float *t1g = args.t[t].t1_in;
-                float bx = FV_NEG_INF;
-                int bk = INT_MAX;
-                const int nlane_rows = nj * R;
-                // two rows per lane and trip: all four loads are requested before the first is used (the rescan is the
-                // tail of its launch: a serial loop paid one memory latency per 64 rows)
-                for (int e0 = 0; e0 < nlane_rows; e0 += 128) {
-                    int kk[2];
-                    float tt[2];
-                    double LL[2];
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        const int e = e0 + 64 * u + lane;
-                        const int k = (w + NWV * (e / R)) * RBR + rgL * R + (e % R);
-                        kk[u] = (e < nlane_rows && k < K) ? k : -1;
-                        const int ks = kk[u] >= 0 ? k : 0;
-                        tt[u] = t1g[ks];
-                        LL[u] = L64tile[(size_t)(ks >> 2) * (TILE_W * 4) + cL * 4 + (ks & 3)];
-                    }
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        if (kk[u] >= 0) {
-                            const float x = exact_cell(tmpL, tt[u], LL[u]);
-                            if (better(x, kk[u], bx, bk)) { bx = x; bk = kk[u]; }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int m = 1; m < 64; m <<= 1) {
-                    const float ov = __shfl_xor(bx, m);
-                    const int ok = __shfl_xor(bk, m);
-                    if (better(ov, ok, bx, bk)) { bx = ov; bk = ok; }
-                }
+                float bx;
+                int bk;
+                rescan_lane_rows<R, NWV>(L64tile, L, nj, K, tmp[t], [&](int k) { return t1g[k]; }, bx, bk);
                 if (lane == L) { rr[t] = bx; rk[t] = bk; }
                 if (lane == 0) atomicAdd(&args.counters[CNT_REFINE_RESCAN], 1ull);
             }
         }
     }
 
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
-        float r = rr[t];
-        int kb = rk[t];
-        wave_best(r, kb);
-        if (lane < TILE_W) { redR[(t * TILE_W + c) * NWV + w] = r; redK[(t * TILE_W + c) * NWV + w] = kb; }
-    }
-    __syncthreads();
-    if (w < NB && w < args.nb) {
-        const float4 fv = *reinterpret_cast<const float4 *>(redR + (w * TILE_W + c) * NWV + (rg * 4) % NWV);
-        const int4 fk = *reinterpret_cast<const int4 *>(redK + (w * TILE_W + c) * NWV + (rg * 4) % NWV);
-        float r = fv.x;
-        int kb = fk.x;
-        if (better(fv.y, fk.y, r, kb)) { r = fv.y; kb = fk.y; }
-        if (better(fv.z, fk.z, r, kb)) { r = fv.z; kb = fk.z; }
-        if (better(fv.w, fk.w, r, kb)) { r = fv.w; kb = fk.w; }
-        wave_best(r, kb);
+    float r;
+    int kb;
+    if (column_fold<NB, NWV>(rr, rk, redR, redK, args.nb, r, kb, lane, w, c, rg)) {
         const bool any = r > -FLT_MAX;
         if (lane < TILE_W && col < K) {
             // reference: score starts at -FLT_MAX with arg = -1 and only a strictly greater ktmp replaces it
@@ -1119,7 +1077,7 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
         }
         if (CODES && (args.codes & 2)) {
             // FV_OPT_ROW_CODES: the tile's maximum over its real columns and every column's code relative to it, beside the floats
-            // (every lane holds its column's result after wave_best; pad columns count as unreachable)
+            // (every lane holds its column's result after column_fold; pad columns count as unreachable)
             const float val = (col < K && any) ? r : -FLT_MAX;
             float tmx = val;
 #pragma unroll
@@ -1133,27 +1091,12 @@ __global__ __launch_bounds__(NWV * 64) void trellis_step_u16(const StepArgs<NB> 
 }
 
 // 16-bit table for models beyond the f32 kernels' LDS limit, built on the device from the float64 table (the host
-// builds it for smaller models, together with the f32 / f16 / sparse forms): the same construction — step =
-// (float)(largest finite |log A| / 65534), code = rne(-L / step), 0xffff = -inf, window from the largest
-// |code * step + L| actually made.  lmax_bits / dmax_bits: doubles as ordered bit patterns (non-negative), atomicMax.
-__global__ void q16_tile_range(const double *t4, size_t n, unsigned long long *lmax_bits)
-{
-    double m = 0.0;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-        const double l = t4[e];
-        if (l > -__builtin_huge_val() && -l > m) m = -l;
-    }
-#pragma unroll
-    for (int k = 1; k < 64; k <<= 1) { const double o = __shfl_xor(m, k); m = o > m ? o : m; }
-    if ((threadIdx.x & 63) == 0 && m > 0.0) atomicMax(lmax_bits, (unsigned long long)__double_as_longlong(m));
-}
-
+// builds it for smaller models, together with the f32 / f16 / sparse forms): q16_range over the table, then the codes
+// by the rule of fv_device_common.h (q16_step / q16_quantise).
 __global__ void q16_tile_codes(const double *t4, unsigned short *q8, int K, int nrows, int ntiles,
                                const unsigned long long *lmax_bits, unsigned long long *dmax_bits)
 {
-    const double lmax = __longlong_as_double((long long)*lmax_bits);
-    const float stepf = lmax > 0.0 ? (float)(lmax / 65534.0) : 1.0f;
-    const double stepd = (double)stepf;
+    const double stepd = (double)q16_step(lmax_bits);
     const size_t n = (size_t)ntiles * nrows * TILE_W;           // one thread per (tile, row, column) of the padded table
     double dm = 0.0;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
@@ -1162,18 +1105,10 @@ __global__ void q16_tile_codes(const double *t4, unsigned short *q8, int K, int 
         const int k = rem / TILE_W, col = tile * TILE_W + rem % TILE_W;
         unsigned short code = 0xFFFFu;
         const double l = t4[tab_index<4>(k, col, nrows)];
-        if (k < K && col < K && l > -__builtin_huge_val()) {
-            double c = nearbyint(-l / stepd);
-            c = c < 0.0 ? 0.0 : (c > 65534.0 ? 65534.0 : c);
-            code = (unsigned short)c;
-            const double d = fabs(-c * stepd - l);
-            dm = d > dm ? d : dm;
-        }
+        if (k < K && col < K && l > -__builtin_huge_val()) code = q16_quantise(l, stepd, dm);
         q8[tab_index<8>(k, col, nrows)] = code;
     }
-#pragma unroll
-    for (int k = 1; k < 64; k <<= 1) { const double o = __shfl_xor(dm, k); dm = o > dm ? o : dm; }
-    if ((threadIdx.x & 63) == 0 && dm > 0.0) atomicMax(dmax_bits, (unsigned long long)__double_as_longlong(dm));
+    q16_publish_max(dmax_bits, dm);
 }
 
 // ---------------------------------------------------------------- sparse transition table
@@ -1345,27 +1280,9 @@ __global__ __launch_bounds__(SP_BLOCK) void trellis_step_sparse(const SparseArgs
         }
         rr[t] = r; rk[t] = kb;
     }
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
-        float r = rr[t];
-        int kb = rk[t];
-        wave_best(r, kb);
-        if (lane < TILE_W) { redR[(t * TILE_W + c) * SP_WAVES + w] = r; redK[(t * TILE_W + c) * SP_WAVES + w] = kb; }
-    }
-    __syncthreads();
-    if (w < NB && w < args.nb) {
-        // 8 wave results per column: lanes (c, rg<2) read 4 each
-        float r = FV_NEG_INF;
-        int kb = INT_MAX;
-        if (rg < 2) {
-            const float4 fv = *reinterpret_cast<const float4 *>(redR + (w * TILE_W + c) * SP_WAVES + rg * 4);
-            const int4 fk = *reinterpret_cast<const int4 *>(redK + (w * TILE_W + c) * SP_WAVES + rg * 4);
-            r = fv.x; kb = fk.x;
-            if (better(fv.y, fk.y, r, kb)) { r = fv.y; kb = fk.y; }
-            if (better(fv.z, fk.z, r, kb)) { r = fv.z; kb = fk.z; }
-            if (better(fv.w, fk.w, r, kb)) { r = fv.w; kb = fk.w; }
-        }
-        wave_best(r, kb);
+    float r;
+    int kb;
+    if (column_fold<NB, SP_WAVES>(rr, rk, redR, redK, args.nb, r, kb, lane, w, c, rg)) {
         if (lane < TILE_W && col < K) {
             const bool any = r > -FLT_MAX;
             args.t[w].t1_out[col] = any ? r : -FLT_MAX;
@@ -1557,27 +1474,9 @@ __global__ __launch_bounds__(SP_BLOCK) void trellis_step_csr(const CsrArgs<NB> a
         }
         rr[t] = r; rk[t] = kbest;
     }
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
-        float r = rr[t];
-        int kbest = rk[t];
-        wave_best(r, kbest);
-        if (lane < TILE_W) { redR[(t * TILE_W + c) * SP_WAVES + w] = r; redK[(t * TILE_W + c) * SP_WAVES + w] = kbest; }
-    }
-    __syncthreads();
-    if (w < NB && w < args.nb) {
-        // 8 wave results per column: lanes (c, rg<2) read 4 each
-        float r = FV_NEG_INF;
-        int kbest = INT_MAX;
-        if (rg < 2) {
-            const float4 fv = *reinterpret_cast<const float4 *>(redR + (w * TILE_W + c) * SP_WAVES + rg * 4);
-            const int4 fk = *reinterpret_cast<const int4 *>(redK + (w * TILE_W + c) * SP_WAVES + rg * 4);
-            r = fv.x; kbest = fk.x;
-            if (better(fv.y, fk.y, r, kbest)) { r = fv.y; kbest = fk.y; }
-            if (better(fv.z, fk.z, r, kbest)) { r = fv.z; kbest = fk.z; }
-            if (better(fv.w, fk.w, r, kbest)) { r = fv.w; kbest = fk.w; }
-        }
-        wave_best(r, kbest);
+    float r;
+    int kbest;
+    if (column_fold<NB, SP_WAVES>(rr, rk, redR, redK, args.nb, r, kbest, lane, w, c, rg)) {
         if (lane < TILE_W && col < K) {
             const bool any = r > -FLT_MAX;
             args.t[w].t1_out[col] = any ? r : -FLT_MAX;
@@ -1694,27 +1593,9 @@ __global__ __launch_bounds__(SP_BLOCK) void trellis_step_csr_f64(const CsrF64Arg
         }
     }
 
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
-        float r = m1[t];
-        int kbest = k1[t];
-        wave_best(r, kbest);
-        if (lane < TILE_W) { redR[(t * TILE_W + c) * SP_WAVES + w] = r; redK[(t * TILE_W + c) * SP_WAVES + w] = kbest; }
-    }
-    __syncthreads();
-    if (w < NB && w < args.nb) {
-        // 8 wave results per column: lanes (c, rg<2) read 4 each
-        float r = FV_NEG_INF;
-        int kbest = INT_MAX;
-        if (rg < 2) {
-            const float4 fv = *reinterpret_cast<const float4 *>(redR + (w * TILE_W + c) * SP_WAVES + rg * 4);
-            const int4 fk = *reinterpret_cast<const int4 *>(redK + (w * TILE_W + c) * SP_WAVES + rg * 4);
-            r = fv.x; kbest = fk.x;
-            if (better(fv.y, fk.y, r, kbest)) { r = fv.y; kbest = fk.y; }
-            if (better(fv.z, fk.z, r, kbest)) { r = fv.z; kbest = fk.z; }
-            if (better(fv.w, fk.w, r, kbest)) { r = fv.w; kbest = fk.w; }
-        }
-        wave_best(r, kbest);
+    float r;
+    int kbest;
+    if (column_fold<NB, SP_WAVES>(m1, k1, redR, redK, args.nb, r, kbest, lane, w, c, rg)) {
         if (lane < TILE_W && col < K) {
             // a column no finite entry reaches: the reference's initial (-FLT_MAX, -1), as last_column_csr leaves it
             const bool any = r > -FLT_MAX;
@@ -1764,70 +1645,42 @@ __global__ void init_rows(const PassChunk ch, const double *LA64, int nrows, con
 }
 
 // End state of the whole-sequence pass, reference FLASH:186-196: ascending scan with strict '>'
-// from i = 0, i.e. the lowest index among the maxima.
-__global__ __launch_bounds__(1024) void final_argmax(const float *row, int K, int *ans_last, float *score_out)
+// from i = 0, i.e. the lowest index among the maxima.  One workgroup of 1024 threads per row: per thread an ascending scan
+// with strict '>', then the (value, lowest index) order of `better` across lanes and waves (block_argbest).
+__device__ __forceinline__ void end_pick(const float *row, int K, int *ans_out, float *score_out)
 {
     __shared__ float sv[16];
     __shared__ int sk[16];
     float v = FV_NEG_INF;
     int k = INT_MAX;
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
+    for (int i = threadIdx.x; i < K; i += 1024) {
         const float x = row[i];
         if (x > v) { v = x; k = i; }
     }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        float ov = __shfl_xor(v, m);
-        int ok = __shfl_xor(k, m);
-        if (better(ov, ok, v, k)) { v = ov; k = ok; }
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sv[w] = v; sk[w] = k; }
-    __syncthreads();
+    block_argbest<16>(v, k, sv, sk);
     if (threadIdx.x == 0) {
-        for (int q = 1; q < (int)(blockDim.x >> 6); ++q)
-            if (better(sv[q], sk[q], v, k)) { v = sv[q]; k = sk[q]; }
-        *ans_last = k;
+        *ans_out = k;
         *score_out = v;
     }
 }
 
+__global__ __launch_bounds__(1024) void final_argmax(const float *row, int K, int *ans_last, float *score_out)
+{
+    end_pick(row, K, ans_last, score_out);
+}
+
 // The same end pick for every whole-sequence pass of a batch decode's generation 0 in ONE launch (a launch costs
 // 1.5-3 us; a batch has one whole pass per sequence): workgroup b takes job b — its pass's last score row — and writes
-// ans[R] and score[seq].  Per lane an ascending scan with strict '>', then the (value, lowest index) order of
-// `better` across lanes and waves: the lowest index among the maxima, as FLASH:186-196.
+// ans[R] and score[seq].
 struct ArgmaxJob { int row; int R; int seq; };          // row: index of the K-float row in units of `nrows` floats
 constexpr int ARGMAX_CHUNK = 256;
 struct ArgmaxArgs { const float *rows; int *ans; float *score; int K, nrows, n; ArgmaxJob j[ARGMAX_CHUNK]; };
 
 __global__ __launch_bounds__(1024) void final_argmax_batch(const ArgmaxArgs args)
 {
-    __shared__ float sv[16];
-    __shared__ int sk[16];
     if ((int)blockIdx.x >= args.n) return;             // workgroup-uniform
     const ArgmaxJob job = args.j[blockIdx.x];
-    const float *row = args.rows + (size_t)job.row * args.nrows;
-    float v = FV_NEG_INF;
-    int k = INT_MAX;
-    for (int i = threadIdx.x; i < args.K; i += blockDim.x) {
-        const float x = row[i];
-        if (x > v) { v = x; k = i; }
-    }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        float ov = __shfl_xor(v, m);
-        int ok = __shfl_xor(k, m);
-        if (better(ov, ok, v, k)) { v = ov; k = ok; }
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sv[w] = v; sk[w] = k; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < (int)(blockDim.x >> 6); ++q)
-            if (better(sv[q], sk[q], v, k)) { v = sv[q]; k = sk[q]; }
-        args.ans[job.R] = k;
-        args.score[job.seq] = v;
-    }
+    end_pick(args.rows + (size_t)job.row * args.nrows, args.K, args.ans + job.R, args.score + job.seq);
 }
 
 // Last step of a pass whose end state is already fixed (every pass except the whole-sequence one):
@@ -1837,10 +1690,18 @@ struct ColJob { const float *t1_in; const float *tmp_row; int *bp_row; int R; };
 constexpr int COL_CHUNK = 48;
 struct ColArgs { const double *LA64; const int *ans; int K, nrows, n; ColJob p[COL_CHUNK]; };
 
-__global__ __launch_bounds__(256) void last_column(const ColArgs args)
+// What last_column and last_column_csr do with their threads' (best, arg) — each the strict-'>' best of the thread's own
+// ascending rows: the workgroup's (256 threads) lowest row among the maxima, or -1 where no row is reachable.
+__device__ __forceinline__ void last_column_tail(float best, int arg, int *bp_cell)
 {
     __shared__ float sv[4];
     __shared__ int sk[4];
+    block_argbest<4>(best, arg, sv, sk);
+    if (threadIdx.x == 0) *bp_cell = best > -FLT_MAX ? arg : -1;
+}
+
+__global__ __launch_bounds__(256) void last_column(const ColArgs args)
+{
     const ColJob job = args.p[blockIdx.x];
     const int i = args.ans[job.R];
     if (i < 0 || i >= args.K) return;                  // workgroup-uniform
@@ -1866,20 +1727,7 @@ __global__ __launch_bounds__(256) void last_column(const ColArgs args)
             }
         }
     }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const float ov = __shfl_xor(best, m);
-        const int ok = __shfl_xor(arg, m);
-        if (better(ov, ok, best, arg)) { best = ov; arg = ok; }
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sv[w] = best; sk[w] = arg; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < 4; ++q)
-            if (better(sv[q], sk[q], best, arg)) { best = sv[q]; arg = sk[q]; }
-        job.bp_row[i] = best > -FLT_MAX ? arg : -1;
-    }
+    last_column_tail(best, arg, job.bp_row + i);
 }
 
 // init_rows for a CSR-set model: row Ans[L-1] of log A is the caller's CSR row scattered into a -inf row — column i
@@ -1915,8 +1763,6 @@ struct CsrColArgs {
 
 __global__ __launch_bounds__(256) void last_column_csr(const CsrColArgs args)
 {
-    __shared__ float sv[4];
-    __shared__ int sk[4];
     const ColJob job = args.p[blockIdx.x];
     const int i = args.ans[job.R];
     if (i < 0 || i >= args.K) return;                  // workgroup-uniform
@@ -1947,70 +1793,15 @@ __global__ __launch_bounds__(256) void last_column_csr(const CsrColArgs args)
             }
         }
     }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const float ov = __shfl_xor(best, m);
-        const int ok = __shfl_xor(arg, m);
-        if (better(ov, ok, best, arg)) { best = ov; arg = ok; }
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sv[w] = best; sk[w] = arg; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < 4; ++q)
-            if (better(sv[q], sk[q], best, arg)) { best = sv[q]; arg = sk[q]; }
-        job.bp_row[i] = best > -FLT_MAX ? arg : -1;
-    }
+    last_column_tail(best, arg, job.bp_row + i);
 }
 
-// Back-track of each pass from its (already fixed) end state: c[j-1] = bp[j][c[j]].  Equivalent to
-// the forward propagation of T2 in the reference (FLASH:242, :176-179) followed by the read-off
-// (:261, :198-201).  Writes c[L..R-1]; later generations overwrite the positions they own.
-//
-// A chain of T dependent loads is latency-bound (64 us at T = 256, 1 ms at T = 4096 for one lane).  Survivor paths
-// merge within a few steps (every state's best predecessor is one of the few best-scoring states), so long chains are
-// walked by 64 lanes at once: lane c walks chunk c of the time axis, starting BT_WARMUP steps above it from a guessed
-// state; by the time it enters its chunk it has (almost always) merged with the true chain.  Nothing is assumed: a
-// chunk's result stands only if the state it entered with equals the state the chunk above it — itself verified —
-// left with (the map is deterministic: equal at one time means equal from there on); the first chunk that fails
-// restarts from the verified state, and the others are walked again behind it.
-//
-// One pass [L, R] walked by one wave: bp is the arg row of time L + 1 (the row of time j at bp + (j - L - 1) * K), `end` the
-// state at time R, out[j - L] receives c[j] for j = L .. R-1.  `restarts` (counter BT_COUNTER) counts the retries: one atomic of
-// lane 0 per failed verification, nothing on the way of a walk whose chunks all stand.
+// Back-track of each pass from its (already fixed) end state: c[j-1] = bp[j][c[j]], by the chunk walk of
+// fv_device_common.h.  Writes c[L..R-1]; later generations overwrite the positions they own.
+// bp is the arg row of time L + 1 (the row of time j at bp + (j - L - 1) * K); no cell of a full-state arg row is tagged.
 __device__ __forceinline__ void backtrack_walk(int L, int R, const int *bp, int K, int end, int *out, unsigned long long *restarts)
 {
-    const int lane = threadIdx.x, len = R - L;
-    auto hop = [&](int st, int j) { return st >= 0 ? bp[(size_t)(j - L - 1) * K + st] : -1; };       // state at time j -> state at time j - 1
-    if (len < BT_MIN_PARALLEL) {
-        if (lane != 0) return;
-        int st = end;
-        for (int j = R; j > L; --j) { st = hop(st, j); out[j - 1 - L] = st; }
-        return;
-    }
-    const int cs = (len + 63) / 64;                      // times per chunk; chunk c: from time top(c) down to top(c + 1)
-    auto top = [&](int c) { return max(R - c * cs, L); };
-    int base = 0, exact = end;                           // chunks below `base` are final; `exact` = state at time top(base)
-    while (base < 64 && top(base) > L) {                 // (wave-uniform)
-        int x = -2, y = -2;                              // state this lane entered its chunk with / left it with
-        if (lane >= base && top(lane) > L) {
-            const int t_hi = top(lane), t_lo = top(lane + 1);
-            int t = min(top(base), t_hi + BT_WARMUP), st = exact;     // at top(base) `exact` is the true state; above the chunk it is a guess
-            for (; t > t_hi; --t) st = hop(st, t);
-            x = st;
-            for (; t > t_lo; --t) { st = hop(st, t); out[t - 1 - L] = st; }
-            y = st;
-        }
-        const int y_above = __shfl_up(y, 1);
-        // lanes whose walk started at top(base) started from the true state: consistent by construction
-        const bool ok = lane <= base || top(lane) <= L || min(top(base), top(lane) + BT_WARMUP) == top(base) || x == y_above;
-        const unsigned long long bad = ~__ballot(ok);
-        if (!bad) break;
-        if (lane == 0) atomicAdd(restarts, 1ull);
-        const int f = __ffsll((long long)bad) - 1;       // first chunk that entered with the wrong state: everything above it is final
-        exact = __shfl(y, f - 1);
-        base = f;
-    }
+    chunk_walk(L, R, end, out, restarts, [&](int st, int j, bool &) { return st >= 0 ? bp[(size_t)(j - L - 1) * K + st] : -1; });
 }
 
 __global__ __launch_bounds__(64) void backtrack(const PassChunk ch, const int *bp, int K, int *ans, unsigned long long *restarts)

@@ -34,6 +34,7 @@ inline float window_of(double dmax) { return std::nextafter((float)(2.0 * dmax),
 // 0 .. 65534 (0xffff stands for -inf).  The kernels evaluate fma(code, -step, s) with step as a float, so the error is
 // measured against exactly that product (code * (double)(float)step is exact in double).  Both builders take codes,
 // windowq and qscale from here: a dense-set and a CSR-set model of the same matrix agree bit for bit.
+// (The device side of the same rule: q16_step / q16_quantise, fv_device_common.h.)
 struct Q16Rule {
     float stepf;
     double stepd;
