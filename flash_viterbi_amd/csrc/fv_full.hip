@@ -923,6 +923,20 @@ int stream_step(fv_ctx *ctx, int kernel, const float *t1_in, float *t1_out, cons
     return launch_step_kernel(ctx, StepLaunch{ kernel, ctx->stream, false, reverse }, &sl, 1);
 }
 
+int stream_step_batch(fv_ctx *ctx, int kernel, const StreamTask *tasks, int nb, int reverse)
+{
+    fvk::TaskSlot slots[fvk::MAX_BATCH];
+    if (nb < 1 || nb > fvk::MAX_BATCH) return FV_ERR_ARG;
+    for (int q = 0; q < nb; ++q) {
+        slots[q].t1_in = tasks[q].t1_in; slots[q].t1_out = tasks[q].t1_out; slots[q].bp_out = tasks[q].bp_out;
+        slots[q].tmp_row = tasks[q].tmp_row; slots[q].tmp64_row = tasks[q].tmp64_row;
+    }
+    return launch_step_kernel(ctx, StepLaunch{ kernel, ctx->stream, false, reverse }, slots, nb);
+}
+
+// (one stream: nothing is forked)
+int stream_batch_cap(const fv_ctx *ctx, int kernel) { return std::min(generation_shape(ctx, kernel, 0, 0, false, false).cap, fvk::MAX_BATCH); }
+
 int stream_end_pick(fv_ctx *ctx, const float *row, int *end, float *score) { return end_pick(ctx, row, end, score); }
 
 int stream_backtrack(fv_ctx *ctx, const int *bp, int R, int *path, unsigned long long *restarts)

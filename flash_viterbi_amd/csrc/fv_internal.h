@@ -5,7 +5,8 @@
 //   fv_full.hip     full-state kernels and their decode drivers (FLASH, vanilla, checkpoint)
 //   fv_beam.hip     FLASH-BS kernels and their decode driver
 //   fv_comm.hip     multi-GPU: partition, RCCL all-gather, merge, the single-process multi-device context
-//   fv_stream.hip   fv_stream_*: the online decode — the ancestor kernels, the stream's own buffers and its entry points
+//   fv_stream.hip   fv_stream_* / fv_streams_*: the online decode — the ancestor kernels, the buffers of a stream and of a set
+//                   of streams, and their entry points
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -227,6 +228,10 @@ struct fv_ctx {
     struct fv_stream *strm = nullptr;
     fv_stream_stats strm_stats{};
     bool strm_any = false;
+    // fv_streams_*: the open set of streams (the same rules: its buffers are its own), the statistics of the open or the last set
+    struct fv_streams *set = nullptr;
+    fv_streams_stats set_stats{};
+    bool set_any = false;
 
     fv_stats stats{};
     // statistics of a decode about to start: everything cleared but what the model and the staged emissions own
@@ -281,11 +286,16 @@ struct FvTestRecording {
         }                                                                                     \
     } while (0)
 
-// every entry point that runs on the context's buffers or changes what a stream was opened on refuses while one is open
+// every entry point that runs on the context's buffers or changes what a stream was opened on refuses while one is open,
+// or a set of them
 #define FV_NO_STREAM(c)                                                                                        \
     do {                                                                                                      \
         if ((c)->strm) {                                                                                      \
             (c)->detail = "a stream is open on this context: fv_stream_close or fv_stream_abort first";       \
+            return FV_ERR_STATE;                                                                              \
+        }                                                                                                     \
+        if ((c)->set) {                                                                                       \
+            (c)->detail = "a set of streams is open on this context: fv_streams_end first";                   \
             return FV_ERR_STATE;                                                                              \
         }                                                                                                     \
     } while (0)
@@ -414,6 +424,12 @@ int stream_init_row(fv_ctx *ctx, const double *lb64, const int *sym, float *row)
 // one single-task step launch, the form the whole-sequence pass of a one-shot decode takes
 int stream_step(fv_ctx *ctx, int kernel, const float *t1_in, float *t1_out, const float *tmp_row, const double *tmp64_row,
                 int *bp_out, int reverse);
+// A set's lock-step (fv_streams_*): one step launch of nb <= stream_batch_cap tasks, each on rows and emission rows of its
+// own slot — the form a batch decode's step launches take (fv_decode_full_batch), bit for bit the single-task launches.
+// stream_batch_cap: tasks per launch the generation policy allows this kernel under the FV_OPT_MAX_BATCH in force.
+struct StreamTask { const float *t1_in; float *t1_out; const float *tmp_row; const double *tmp64_row; int *bp_out; };
+int stream_step_batch(fv_ctx *ctx, int kernel, const StreamTask *tasks, int nb, int reverse);
+int stream_batch_cap(const fv_ctx *ctx, int kernel);
 // the end pick on `row` into *end / *score, and the back-track of local times 0 .. R from path[R] through the arg rows
 // (row j of `bp`: local time j; row 0 is never read) into path[0 .. R-1]
 int stream_end_pick(fv_ctx *ctx, const float *row, int *end, float *score);
@@ -424,7 +440,7 @@ constexpr const char *CSR_FILTER_RANGE_DETAIL =
     "fv_set_model_sparse: the walk over the stored entries is a filter kernel and needs every model entry in [0,1] "
     "(and every staged emission score <= 0); FV_KERNEL_CSR_F64 decodes such input";
 inline const char *filter_range_detail(const fv_ctx *ctx) { return ctx->csr ? CSR_FILTER_RANGE_DETAIL : FILTER_RANGE_DETAIL; }
-// frees an open stream's buffers (fv_destroy, close, abort)
+// frees an open stream's buffers, and an open set's (fv_destroy, close, abort, fv_streams_end)
 void stream_drop(fv_ctx *ctx);
 // fv_comm.hip
 // Multi-device context: one host thread per member runs the same decode on its own device (whole-sequence pass + the

@@ -76,6 +76,16 @@ class StreamStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class StreamsStats(ctypes.Structure):
+    """fv_streams_stats: the open set of streams, or the last one ended, summed over its life."""
+    _fields_ = [("calls", ctypes.c_longlong), ("step_launches", ctypes.c_longlong), ("task_steps", ctypes.c_longlong),
+                ("check_launches", ctypes.c_longlong), ("check_slots", ctypes.c_longlong), ("syncs", ctypes.c_longlong),
+                ("nslots", ctypes.c_int), ("batch_cap", ctypes.c_int), ("kernel", ctypes.c_int), ("push_ms_total", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FlatInfo(ctypes.Structure):
     """fv_flat_info: one right-hand pass of the flat schedule."""
     _fields_ = [("L", ctypes.c_int), ("R", ctypes.c_int), ("generation", ctypes.c_int), ("batch", ctypes.c_int),
@@ -93,7 +103,9 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_create_multi", "fv_device_count", "fv_decode_full_batch", "fv_plan_passes_batch", "fv_decode_beam_batch",
            "fv_set_model_sparse", "fv_set_emissions", "fv_clear_emissions", "fv_plan_flat", "fv_set_emission_map",
            "fv_stream_open", "fv_stream_push", "fv_stream_push_emissions", "fv_stream_pending", "fv_stream_close",
-           "fv_stream_abort", "fv_stream_last_stats"]
+           "fv_stream_abort", "fv_stream_last_stats",
+           "fv_streams_open", "fv_streams_push", "fv_streams_push_emissions", "fv_streams_pending", "fv_streams_close",
+           "fv_streams_abort", "fv_streams_end", "fv_streams_slot_stats", "fv_streams_last_stats"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select", "fv_test_device_alloc", "fv_test_device_free",
                 "fv_test_stage_emissions_ms", "fv_test_flat_poison", "fv_test_beam_forward", "fv_test_model_digest"]
@@ -171,6 +183,16 @@ def load_library():
     L.fv_stream_close.argtypes = [vp, vp, ctypes.POINTER(cll), ctypes.POINTER(ctypes.c_float)]
     L.fv_stream_abort.argtypes = [vp]
     L.fv_stream_last_stats.argtypes = [vp, ctypes.POINTER(StreamStats)]
+    L.fv_streams_open.argtypes = [vp, ci, cll, ci]
+    L.fv_streams_push.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    L.fv_streams_push_emissions.argtypes = [vp, vp, ci, vp, ci, vp, cll, vp, vp, vp, vp]
+    L.fv_streams_pending.argtypes = [vp, ci]
+    L.fv_streams_pending.restype = cll
+    L.fv_streams_close.argtypes = [vp, ci, vp, ctypes.POINTER(cll), ctypes.POINTER(ctypes.c_float)]
+    L.fv_streams_abort.argtypes = [vp, ci]
+    L.fv_streams_end.argtypes = [vp]
+    L.fv_streams_slot_stats.argtypes = [vp, ci, ctypes.POINTER(StreamStats)]
+    L.fv_streams_last_stats.argtypes = [vp, ctypes.POINTER(StreamsStats)]
     L.fv_test_device_alloc.argtypes = [vp, ctypes.c_size_t, vp, ctypes.POINTER(vp)]
     L.fv_test_device_free.argtypes = [vp, vp]
     L.fv_test_stage_emissions_ms.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
@@ -515,6 +537,80 @@ class FlashViterbi:
     def stream_stats(self):
         s = StreamStats()
         self._check(self._L.fv_stream_last_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    # ---- fv_streams_*: a set of online streams ("slots") on one context, the slots of one push call stepped together.
+    # A set and the single stream exclude each other.
+
+    def streams_open(self, nslots, lag_rows_hint=0, check_every=0):
+        """fv_streams_open: nslots slots (1..64), lag_rows_hint and check_every as stream_open, for every slot."""
+        self._check(self._L.fv_streams_open(self._h, int(nslots), int(lag_rows_hint), int(check_every)))
+
+    def streams_push(self, ids, obs=None, scores=None, ld=None):
+        """fv_streams_push (obs: one int sequence per named slot) or fv_streams_push_emissions (scores: one 2-D array of
+        score rows per named slot, packed into one block; or (block, lengths), block in the forms set_emissions takes with
+        slot ids[q]'s rows laid end to end in it).  Returns (pieces, statuses): per named slot the piece of the path this
+        call committed (int32, possibly empty) and FV_OK or ERR_NO_PRED — a dead slot is reported, not raised, as
+        decode_full_batch reports it.  A refused call raises FlashVitError and consumes nothing in any slot."""
+        if (obs is None) == (scores is None):
+            raise ValueError("streams_push: either obs or scores")
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        if obs is not None:
+            ob, ptr, offsets = _batch_arg(obs, None)
+        elif isinstance(scores, tuple) and len(scores) == 2:
+            block, lengths = scores
+            _, _, offsets = _batch_arg(None, lengths)
+            keep, ptr, code, n, pitch = _emission_arg(block, ld, "streams_push")
+        else:
+            blocks = [np.asarray(b) for b in scores]
+            _, _, offsets = _batch_arg(None, [b.shape[0] for b in blocks])
+            keep, ptr, code, n, pitch = _emission_arg(np.concatenate(blocks) if blocks else np.zeros((0, 0), np.float32), ld, "streams_push")
+        if offsets.size != ids.size + 1:
+            raise ValueError("streams_push: one sequence per named slot")
+        sizes, pending, room = offsets.tolist(), self._L.fv_streams_pending, [0]
+        for q, i in enumerate(ids.tolist()):
+            room.append(room[-1] + max(pending(self._h, i), 0) + max(sizes[q + 1] - sizes[q], 1))
+        room = np.array(room, dtype=np.int64)
+        path = np.empty(max(int(room[-1]), 1), dtype=np.int32)
+        done = np.zeros(max(ids.size, 1), dtype=np.int64)
+        status = np.zeros(max(ids.size, 1), dtype=np.int32)
+        if obs is not None:
+            rc = self._L.fv_streams_push(self._h, _p(ids), ids.size, ptr, _p(offsets), _p(path), _p(room), _p(done), _p(status))
+        else:
+            rc = self._L.fv_streams_push_emissions(self._h, _p(ids), ids.size, ptr, code, _p(offsets), pitch, _p(path), _p(room),
+                                                   _p(done), _p(status))
+        if rc != ERR_NO_PRED:
+            self._check(rc)
+        return ([path[room[q]:room[q] + done[q]].copy() for q in range(ids.size)], [int(x) for x in status[:ids.size]])
+
+    def streams_pending(self, id):
+        """fv_streams_pending: times slot id consumed and has not yet committed (< 0: no set, or no such slot)."""
+        return int(self._L.fv_streams_pending(self._h, int(id)))
+
+    def streams_close(self, id):
+        """fv_streams_close: (the last piece, the score, rc) of slot id's sequence, as stream_close; the slot is empty again."""
+        piece = np.empty(max(int(self._L.fv_streams_pending(self._h, int(id))), 1), dtype=np.int32)
+        n = ctypes.c_longlong(0)
+        score = ctypes.c_float(0)
+        rc = self._L.fv_streams_close(self._h, int(id), _p(piece), ctypes.byref(n), ctypes.byref(score))
+        if rc != ERR_NO_PRED:
+            self._check(rc)
+        return piece[:n.value].copy(), np.float32(score.value), rc
+
+    def streams_abort(self, id):
+        self._check(self._L.fv_streams_abort(self._h, int(id)))
+
+    def streams_end(self):
+        self._check(self._L.fv_streams_end(self._h))
+
+    def streams_slot_stats(self, id):
+        s = StreamStats()
+        self._check(self._L.fv_streams_slot_stats(self._h, int(id), ctypes.byref(s)))
+        return s.as_dict()
+
+    def streams_stats(self):
+        s = StreamsStats()
+        self._check(self._L.fv_streams_last_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
 
     def decode_full(self, ob, n_split=1, mode=MODE_REFERENCE, T=None):

@@ -435,6 +435,63 @@ typedef struct {
 } fv_stream_stats;
 int fv_stream_last_stats(const fv_ctx *ctx, fv_stream_stats *out);
 
+/* Many online streams on one context.
+ * A set of nslots online streams ("slots", ids 0 .. nslots-1) on one context: fv_stream_*'s contract per slot, the steps of
+ * the slots named in one push call sharing their step launches and checks.
+ *   The contract.  Per slot — whatever the other slots do, however the calls group the slots, whatever batch_cap is — the
+ * pieces, the committed count after every call the slot took part in, the final score and the return codes are bit for bit
+ * those of the same pushes through fv_stream_* on a context of its own, so their concatenation is
+ * fv_decode_full(..., 1, FV_MODE_SINGLE_PASS)'s result; the slot's fv_stream_stats counters times, committed, pushes, checks,
+ * commits, lag_max and bt_restarts equal that stream's.  The check rule is per slot and unchanged: a check every check_every
+ * steps of that slot counted from its last check, and after the last step of each of its pushes.
+ *   fv_streams_open: nslots in 1 .. 64; lag_rows_hint and check_every exactly as fv_stream_open, applied to every slot;
+ * admission and kernel choice as there, fixed for the set's life.  batch_cap, the tasks one step launch takes, is the
+ * smaller of FV_OPT_MAX_BATCH at the open and what fv_decode_full_batch would take for the model (with FV_OPT_MAX_BATCH = 1
+ * every step is a single-task launch).  A set and the single stream exclude each other: each open answers FV_ERR_STATE
+ * while the other is open, and while a set is open everything that answers FV_ERR_STATE under an open stream does so too.
+ * FV_ERR_UNSUPPORTED: multi-device, partitioned and communicator contexts.
+ *   fv_streams_push: ids[0 .. nids) are distinct slots; slot ids[q] consumes ob[offsets[q] .. offsets[q+1]) — the offsets
+ * contract of the batch decodes (offsets[0] = 0), every length >= 1; a slot with nothing to push is left out of the call.
+ * The first push into an empty slot starts a new sequence there (time 0 from Pi) and fixes its kind, symbols or score
+ * rows.  path_offsets has nids + 1 entries: slot ids[q]'s piece is written at path_out + path_offsets[q], committed_out[q]
+ * is its length, and the room path_offsets[q+1] - path_offsets[q] must be at least fv_streams_pending(ctx, ids[q]) + n_q.
+ * status_out[q] (status_out may be NULL) is what fv_stream_push would return for that slot, FV_OK or FV_ERR_NO_PRED; the
+ * call returns the most negative status.  A dead slot does not disturb the others; it then accepts only fv_streams_close
+ * (FV_ERR_NO_PRED, nothing delivered) and fv_streams_abort, and naming it in a push refuses the call with FV_ERR_STATE.
+ *   A refused call consumes nothing in any slot, runs no step and leaves every slot as it was: FV_ERR_ARG for bad
+ * pointers, nids < 1, an id outside the set or named twice, a length below 1, a symbol outside [0, M), the other kind of
+ * input for a slot that has one, too little room; FV_ERR_NOMEM for a refused growth of arg rows.  fv_last_error_detail
+ * names the slot and, where it applies, the time counted from that slot's sequence start.
+ *   fv_streams_push_emissions: scores is one block, slot ids[q]'s rows are its rows offsets[q] .. offsets[q+1]), one dtype
+ * and one ld; host or device pointer, emission map and value rules exactly as fv_stream_push_emissions.  The block is
+ * staged in one launch and its flags are read once, before any step: a NaN, a +inf or an out-of-range score anywhere
+ * refuses the whole call (FV_ERR_ARG; the detail names slot, time and state of the lowest offending staged index), a
+ * score above 0 under a filter kernel refuses it with FV_ERR_UNSUPPORTED.
+ *   fv_streams_pending: times slot id consumed and has not yet committed; < 0 without a set or for an id outside it.
+ *   fv_streams_close: fv_stream_close's work on slot id — end pick, back-track of everything pending, the score — and
+ * the slot is empty and ready for a new sequence, its buffers kept: sequences come and go while other slots are in
+ * mid-sequence.  An empty slot delivers nothing and returns FV_OK.  fv_streams_abort drops slot id's sequence.
+ * fv_streams_end frees the whole set, whatever its slots hold; so does fv_destroy.
+ *   fv_streams_slot_stats: fv_stream_stats of slot id's sequence, or of the last one that left the slot.  push_ms_total
+ * of a slot is the wall time of the calls it took part in, undivided: the slots of one call all count the whole call. */
+int fv_streams_open(fv_ctx *ctx, int nslots, long long lag_rows_hint, int check_every);
+int fv_streams_push(fv_ctx *ctx, const int *ids, int nids, const int *ob, const long long *offsets,
+                    int *path_out, const long long *path_offsets, long long *committed_out, int *status_out);
+int fv_streams_push_emissions(fv_ctx *ctx, const int *ids, int nids, const void *scores, int dtype,
+                              const long long *offsets, long long ld,
+                              int *path_out, const long long *path_offsets, long long *committed_out, int *status_out);
+long long fv_streams_pending(const fv_ctx *ctx, int id);
+int fv_streams_close(fv_ctx *ctx, int id, int *path_out, long long *n_out, float *score_out);
+int fv_streams_abort(fv_ctx *ctx, int id);      /* drops slot id's sequence; the slot is empty again */
+int fv_streams_end(fv_ctx *ctx);                /* frees the whole set, whatever its slots hold */
+int fv_streams_slot_stats(const fv_ctx *ctx, int id, fv_stream_stats *out);
+/* The open set, or the last one ended (FV_ERR_STATE: there never was one), summed over its life.  The launch counters
+ * are bare launches: step_launches of task_steps tasks in all; check_launches, two per pair, serving check_slots
+ * slot-checks; syncs: the times the host waited for the device (at most two per symbol push call, three per score push
+ * call, one more per regrow, one per close). */
+typedef struct { long long calls, step_launches, task_steps, check_launches, check_slots, syncs; int nslots, batch_cap, kernel; double push_ms_total; } fv_streams_stats;
+int fv_streams_last_stats(const fv_ctx *ctx, fv_streams_stats *out);
+
 int fv_last_stats(const fv_ctx *ctx, fv_stats *out);
 const char *fv_strerror(int rc);
 const char *fv_last_error_detail(const fv_ctx *ctx);
