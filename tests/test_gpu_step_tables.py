@@ -60,18 +60,6 @@ def header_variants():
 
 # ---------------------------------------------------------------- models and pass sets
 
-def unreachable_model(K, M, T, seed):
-    """A generate_data model with states no path reaches: every 7th column of A is zero (those states have no
-    predecessor: -FLT_MAX / -1 in every step row) and a third of Pi is zero (-inf entries of a Pi-initialised row)."""
-    A, Bm, Pi = modelgen.model64(dict(kind="data_script", K=K, M=M, seed=seed, prob=0.112))
-    A = A.copy()
-    A[:, ::7] = 0.0
-    Pi = Pi.copy()
-    Pi[np.random.RandomState(seed).rand(K) < 0.33] = 0.0
-    ob = np.random.RandomState(seed + 1).randint(0, M, T).astype(np.int32)
-    return hostio.quantize_text16(A), hostio.quantize_text16(Bm), hostio.quantize_text16(Pi), ob
-
-
 def one_state_model(M, T, seed):
     rs = np.random.RandomState(seed)
     Bm = rs.uniform(0.1, 1.0, (1, M))
@@ -86,7 +74,8 @@ def build_model(kind, K, T, seed, prob=0.112, M=8):
     if kind in ("wideA", "wideB"):
         return modelgen.wide_model(kind, K, M, T, seed)
     if kind == "unreachable":
-        return unreachable_model(K, M, T, seed)
+        # every 7th column of A zero, a third of Pi zero (the golden unreachable_K300_T40 is this model)
+        return modelgen.unreachable_model(K, M, T, seed)
     if kind == "data_script" and K < 64:
         # (the generator leaves a row without out-edges unnormalised, NaN, which small K draws often; the vectorised
         # builder of the same distributions gives such a row one edge)
