@@ -232,6 +232,11 @@ struct fv_ctx {
     struct fv_streams *set = nullptr;
     fv_streams_stats set_stats{};
     bool set_any = false;
+    // fv_set_max_lag: the bound streams and sets opened from now on force commits at (0: none; kept across fv_set_model*),
+    // and fv_last_lag_stats' record of the last stream closed or aborted and of the slots of the last set ended
+    long long max_lag = 0;
+    fv_lag_stats strm_lag{};
+    std::vector<fv_lag_stats> set_lag;
 
     fv_stats stats{};
     // statistics of a decode about to start: everything cleared but what the model and the staged emissions own

@@ -12,6 +12,11 @@
 // lock-step: their steps share step launches of up to batch_cap tasks (fvi::stream_step_batch), the checks that come
 // due in one lock-step share one pair of launches (stream_ancestors_set / stream_verdict_set, a slot per blockIdx.y),
 // and the host meets the device twice per call whatever the number of slots.
+//
+// fv_set_max_lag bounds the commit lag of the streams and sets opened after it: their check is three
+// launches (stream_ancestors_lag / stream_decide / stream_apply), and a check that finds more than one ancestor max_lag
+// or more steps past the anchor FORCES the commit of the best state's ancestor and prunes the other states.  Without it
+// every stream runs the two launches above with the arguments they always had.
 #include "fv_internal.h"
 
 #include <climits>
@@ -32,9 +37,30 @@ struct StreamCtl {
     int acc[2][4];
     int sym0;                         // the symbol of time 0 (init row); a stream of score rows: its row in the staged chunk
     float score;                      // the end pick's score (close)
+    // a lag-bounded stream (fv_set_max_lag; the words below stay as stream_reset left them in every other stream).
+    // best[p]: the arg-max key of the score row at check number q (p = q & 1), double-buffered like acc; decision, vstar:
+    // what stream_decide made of acc[p], best[p] and the anchor, read by the apply launch; then the forced commits' counters
+    unsigned long long best[2];
+    int decision, vstar;
+    long long forced, first_forced, last_forced;
+    unsigned long long pruned;
 };
 
 constexpr int ANC_BLOCK = 256;
+
+// stream_decide's verdicts
+enum { DECIDE_NONE = 0, DECIDE_ONE = 1, DECIDE_DEAD = 2, DECIDE_FORCED = 3 };
+
+// The arg-max key of score x at state s: the order-preserving image of the float's bits in the high half, 0x7fffffff - s
+// in the low half, so that the maximum over a row carries the LOWEST index among equal scores (the end-pick rule of
+// fv_stream_close).  Every key is above 0, the fold's neutral element: -inf maps to 0x007fffff in the high half.  (x + 0.0f:
+// a negative zero compares equal to a positive one and must not lose to it on its bits.)
+__device__ __forceinline__ unsigned long long best_key(float x, int s)
+{
+    const unsigned int u = __float_as_uint(x + 0.0f);
+    const unsigned int image = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)image << 32) | (unsigned int)(0x7fffffff - s);
+}
 
 __global__ __launch_bounds__(ANC_BLOCK) void stream_reset(StreamCtl *ctl, int *anc, int K)
 {
@@ -44,6 +70,8 @@ __global__ __launch_bounds__(ANC_BLOCK) void stream_reset(StreamCtl *ctl, int *a
         ctl->anchor = 0; ctl->rec_time = -1; ctl->rec_state = -1; ctl->dead = 0; ctl->commits = 0; ctl->bt_restarts = 0ull;
         for (int p = 0; p < 2; ++p) { ctl->acc[p][0] = INT_MAX; ctl->acc[p][1] = -1; ctl->acc[p][2] = 0; ctl->acc[p][3] = 0; }
         ctl->sym0 = 0; ctl->score = 0.0f;
+        ctl->best[0] = ctl->best[1] = 0ull; ctl->decision = DECIDE_NONE; ctl->vstar = -1;
+        ctl->forced = 0; ctl->first_forced = ctl->last_forced = -1; ctl->pruned = 0ull;
     }
 }
 
@@ -52,16 +80,24 @@ __global__ __launch_bounds__(ANC_BLOCK) void stream_reset(StreamCtl *ctl, int *a
 // and one into the old ancestor row; -1 (no predecessor) ends a chain.  Lanes along s: the first gather is coalesced,
 // the others land wherever the survivor paths lead (after a few steps on a handful of states: the same cache lines).
 // Then the fold over all K: wave shuffle, LDS across the four waves, one atomic triple per workgroup that saw a live state.
-__device__ __forceinline__ void ancestors_body(const int *bp_new, int r, int K, const int *anc_in, int *anc_out, int *acc)
+// LAG (a lag-bounded stream): the same launch folds the score row of time t into best, the arg-max key of the check's parity
+// (best_key: the lowest index among the maxima) — wave shuffle, LDS, one 64-bit vector atomicMax per workgroup.  Rows past
+// K take no part.
+template <bool LAG>
+__device__ __forceinline__ void ancestors_body(const int *bp_new, int r, int K, const int *anc_in, int *anc_out, int *acc,
+                                               const float *row, unsigned long long *best)
 {
     __shared__ int s_mn[ANC_BLOCK / 64], s_mx[ANC_BLOCK / 64], s_cnt[ANC_BLOCK / 64];
+    __shared__ unsigned long long s_key[LAG ? ANC_BLOCK / 64 : 1];
     const int s = blockIdx.x * ANC_BLOCK + threadIdx.x;
     int v = -1;
+    unsigned long long key = 0ull;
     if (s < K) {
         int x = s;
         for (int j = 0; j < r && x >= 0; ++j) x = bp_new[x - (long long)j * K];
         v = x >= 0 ? anc_in[x] : -1;
         anc_out[s] = v;
+        if constexpr (LAG) key = best_key(row[s], s);
     }
     int mn = v >= 0 ? v : INT_MAX, mx = v, cnt = v >= 0 ? 1 : 0;
 #pragma unroll
@@ -69,19 +105,33 @@ __device__ __forceinline__ void ancestors_body(const int *bp_new, int r, int K, 
         mn = min(mn, __shfl_xor(mn, m));
         mx = max(mx, __shfl_xor(mx, m));
         cnt += __shfl_xor(cnt, m);
+        if constexpr (LAG) key = max(key, (unsigned long long)__shfl_xor((long long)key, m));
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { s_mn[w] = mn; s_mx[w] = mx; s_cnt[w] = cnt; }
+    if (lane == 0) {
+        s_mn[w] = mn; s_mx[w] = mx; s_cnt[w] = cnt;
+        if constexpr (LAG) s_key[w] = key;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int q = 1; q < ANC_BLOCK / 64; ++q) { mn = min(mn, s_mn[q]); mx = max(mx, s_mx[q]); cnt += s_cnt[q]; }
+        for (int q = 1; q < ANC_BLOCK / 64; ++q) {
+            mn = min(mn, s_mn[q]); mx = max(mx, s_mx[q]); cnt += s_cnt[q];
+            if constexpr (LAG) key = max(key, s_key[q]);
+        }
         if (cnt) { atomicMin(&acc[0], mn); atomicMax(&acc[1], mx); atomicAdd(&acc[2], cnt); }
+        if constexpr (LAG) atomicMax(best, key);
     }
 }
 
 __global__ __launch_bounds__(ANC_BLOCK) void stream_ancestors(const int *bp_new, int r, int K, const int *anc_in, int *anc_out, int *acc)
 {
-    ancestors_body(bp_new, r, K, anc_in, anc_out, acc);
+    ancestors_body<false>(bp_new, r, K, anc_in, anc_out, acc, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(ANC_BLOCK) void stream_ancestors_lag(const int *bp_new, int r, int K, const int *anc_in, int *anc_out, int *acc,
+                                                                  const float *row, unsigned long long *best)
+{
+    ancestors_body<true>(bp_new, r, K, anc_in, anc_out, acc, row, best);
 }
 
 // One check, second launch (the fold is final: the launch before this one has ended).  One ancestor v: thread 0 notes
@@ -131,7 +181,7 @@ __global__ __launch_bounds__(ANC_BLOCK) void stream_ancestors_set(const CheckArg
 {
     if ((int)blockIdx.y >= a.n) return;
     const CheckSlot &c = a.s[blockIdx.y];
-    ancestors_body(c.bp_new, c.r, a.K, c.anc_in, c.anc_out, c.ctl->acc[c.parity]);
+    ancestors_body<false>(c.bp_new, c.r, a.K, c.anc_in, c.anc_out, c.ctl->acc[c.parity], nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(ANC_BLOCK) void stream_verdict_set(const CheckArgs a)
@@ -139,6 +189,116 @@ __global__ __launch_bounds__(ANC_BLOCK) void stream_verdict_set(const CheckArgs 
     if ((int)blockIdx.y >= a.n) return;
     const CheckSlot &c = a.s[blockIdx.y];
     verdict_body(c.ctl, c.parity, c.t, c.base, c.bp_t, a.K, c.anc_out, c.path);
+}
+
+// ---- the check of a lag-bounded stream (fv_set_max_lag): three launches.  stream_ancestors_lag above;
+// stream_decide, one thread, turns the fold into the decision word; stream_apply is the verdict launch driven by that word.
+// The decision has a launch of its own because the apply launch moves the anchor and overwrites anc_out in place: it
+// cannot read either of them to decide, and no launch reads a word that the same launch writes.
+//
+// decide: none alive: dead.  One ancestor: the commit of every stream.  More than one and t - anchor >= max_lag: FORCED —
+// s* = the lowest index among the maxima of the score row of time t (best), v* = anc_out[s*].  More than one ancestor
+// means a state with a predecessor chain back to the anchor, so the maximum is such a state's and v* >= 0; a row that says
+// otherwise (scores the step kernels cannot produce) forces nothing.
+__device__ __forceinline__ void decide_body(StreamCtl *ctl, int parity, long long t, long long max_lag, const int *anc_out, int K)
+{
+    const int mn = ctl->acc[parity][0], mx = ctl->acc[parity][1], cnt = ctl->acc[parity][2];
+    int decision = DECIDE_NONE, v = -1;
+    if (cnt == 0) decision = DECIDE_DEAD;
+    else if (mn == mx) { decision = DECIDE_ONE; v = mn; }
+    else if (t - ctl->anchor >= max_lag) {
+        const unsigned int best = 0x7fffffffu - (unsigned int)(ctl->best[parity] & 0xffffffffull);
+        if (best < (unsigned int)K) v = anc_out[best];       // (every fold of K >= 1 states holds a key of one of them)
+        if (v >= 0) decision = DECIDE_FORCED;
+    }
+    ctl->decision = decision; ctl->vstar = v;
+}
+
+__global__ void stream_decide(StreamCtl *ctl, int parity, long long t, long long max_lag, const int *anc_out, int K)
+{
+    if (threadIdx.x == 0) decide_body(ctl, parity, t, max_lag, anc_out, K);
+}
+
+// apply.  ONE: verdict_body's commit and re-anchoring.  FORCED: every state whose ancestor is not v* is pruned — its entry
+// of the score row of time t becomes -inf, which no later cell can take as its source (its arg entry of time t stays and
+// is never read again) — the survivors are re-anchored (anc[s] = s; they have a predecessor: their ancestor is v* >= 0),
+// the pruned states with an ancestor are counted (one vector atomic per workgroup that pruned one), and thread 0 records
+// (anchor, v*) exactly like any commit, with the forced counters and times.  Each thread reads and writes its own anc_out
+// entry only; thread 0 alone reads and moves the anchor; pruned is read by no launch.
+// The row belongs to the stream (StreamSeq::rows), outside the context's d_rows: FV_OPT_ROW_CODES never attaches codes to
+// it (coded_row_index), and it must stay that way — codes a step wrote beside a row that is pruned afterwards would be wrong.
+__device__ __forceinline__ void apply_body(StreamCtl *ctl, int parity, long long t, long long base, const int *bp_t, int K,
+                                           int *anc_out, int *path, float *row)
+{
+    __shared__ int s_cnt[ANC_BLOCK / 64];
+    const int decision = ctl->decision, v = ctl->vstar;
+    const int s = blockIdx.x * ANC_BLOCK + threadIdx.x;
+    if (decision == DECIDE_ONE) {
+        if (s < K) anc_out[s] = bp_t[s] >= 0 ? s : -1;
+    } else if (decision == DECIDE_FORCED) {              // (uniform over the launch: every thread meets the barrier)
+        int cnt = 0;
+        if (s < K) {
+            const int a = anc_out[s];
+            if (a != v) { row[s] = -INFINITY; cnt = a >= 0 ? 1 : 0; }
+            anc_out[s] = a == v ? s : -1;
+        }
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) cnt += __shfl_xor(cnt, m);
+        if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int q = 1; q < ANC_BLOCK / 64; ++q) cnt += s_cnt[q];
+            if (cnt) atomicAdd(&ctl->pruned, (unsigned long long)cnt);
+        }
+    }
+    if (s == 0) {
+        int *next = ctl->acc[parity ^ 1];
+        next[0] = INT_MAX; next[1] = -1; next[2] = 0;
+        ctl->best[parity ^ 1] = 0ull;
+        if (decision == DECIDE_DEAD) ctl->dead = 1;
+        else if (decision != DECIDE_NONE) {
+            const long long a = ctl->anchor;
+            path[a - base] = v;
+            ctl->rec_time = a; ctl->rec_state = v; ctl->anchor = t; ctl->commits += 1;
+            if (decision == DECIDE_FORCED) {
+                ctl->forced += 1;
+                if (ctl->first_forced < 0) ctl->first_forced = t;
+                ctl->last_forced = t;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(ANC_BLOCK) void stream_apply(StreamCtl *ctl, int parity, long long t, long long base, const int *bp_t,
+                                                          int K, int *anc_out, int *path, float *row)
+{
+    apply_body(ctl, parity, t, base, bp_t, K, anc_out, path, row);
+}
+
+// The set forms, a slot per blockIdx.y as above.  What a lag-bounded slot's check needs besides its CheckSlot lies beside
+// it, not in it: the arguments of the two launches of an unbounded set stay as they are.
+struct LagSlot { float *row; long long max_lag; };
+struct LagArgs { CheckArgs a; LagSlot l[CHECK_SLOTS]; };
+
+__global__ __launch_bounds__(ANC_BLOCK) void stream_ancestors_lag_set(const LagArgs g)
+{
+    if ((int)blockIdx.y >= g.a.n) return;
+    const CheckSlot &c = g.a.s[blockIdx.y];
+    ancestors_body<true>(c.bp_new, c.r, g.a.K, c.anc_in, c.anc_out, c.ctl->acc[c.parity], g.l[blockIdx.y].row, &c.ctl->best[c.parity]);
+}
+
+__global__ void stream_decide_set(const LagArgs g)
+{
+    if ((int)blockIdx.y >= g.a.n || threadIdx.x != 0) return;
+    const CheckSlot &c = g.a.s[blockIdx.y];
+    decide_body(c.ctl, c.parity, c.t, g.l[blockIdx.y].max_lag, c.anc_out, g.a.K);
+}
+
+__global__ __launch_bounds__(ANC_BLOCK) void stream_apply_set(const LagArgs g)
+{
+    if ((int)blockIdx.y >= g.a.n) return;
+    const CheckSlot &c = g.a.s[blockIdx.y];
+    apply_body(c.ctl, c.parity, c.t, c.base, c.bp_t, g.a.K, c.anc_out, c.path, g.l[blockIdx.y].row);
 }
 
 }  // namespace fvk
@@ -160,6 +320,8 @@ struct StreamSeq {
     DevBuf<float> rows;                       // the two score rows, by parity of the time
     fvk::StreamCtl *d_ctl = nullptr, *h_ctl = nullptr;      // its device words and their pinned mirror (the owner's)
     fv_stream_stats st{};
+    long long max_lag = 0;                    // fv_set_max_lag's value at the open; 0: unbounded, two launches per check
+    fv_lag_stats lag{};
 };
 
 struct fv_stream : StreamSeq {
@@ -173,6 +335,7 @@ struct fv_stream : StreamSeq {
 
 struct fv_streams {
     int nslots = 0, kernel = FV_KERNEL_AUTO, check_every = STREAM_CHECK_DEFAULT, batch_cap = 1;
+    long long max_lag = 0;                    // every slot's
     std::unique_ptr<StreamSeq[]> slot;
     DevBuf<fvk::StreamCtl> ctl;               // [nslots]
     fvk::StreamCtl *h_ctl = nullptr;          // [nslots], pinned
@@ -200,7 +363,9 @@ int make_room(fv_ctx *ctx, StreamSeq *s, long long n, const std::string &who, lo
         s->off = 0;
         return 0;
     }
-    const size_t cap = std::max(2 * s->cap, 2 * need);
+    // (a lag-bounded sequence's need is bounded — pending <= 2 L + C - 2 — so doubling has nothing to amortise: its buffer
+    // stays within twice the largest need, and is regrown only while that need still rises)
+    const size_t cap = s->max_lag > 0 ? 2 * need : std::max(2 * s->cap, 2 * need);
     DevBuf<int> bp, path;
     if (bp.ensure(cap * K) != hipSuccess || path.ensure(cap) != hipSuccess) {
         (void)hipGetLastError();
@@ -245,6 +410,22 @@ void commit_take(StreamSeq *s, long long count)
         s->st.committed = s->committed;
     }
     s->st.lag_max = std::max(s->st.lag_max, pending(s));
+}
+
+// the forced commits' counters of a sequence whose control record is on the host
+void lag_take(StreamSeq *s)
+{
+    s->lag.forced_commits = s->h_ctl->forced;
+    s->lag.pruned_states = (long long)s->h_ctl->pruned;
+    s->lag.first_forced_time = s->h_ctl->first_forced;
+    s->lag.last_forced_time = s->h_ctl->last_forced;
+}
+
+fv_lag_stats lag_fresh(long long max_lag)
+{
+    fv_lag_stats l{};
+    l.max_lag = max_lag; l.first_forced_time = l.last_forced_time = -1;
+    return l;
 }
 
 // The end of a sequence's input: end pick, back-track of everything pending, the score (fv_stream_close; a slot's close)
@@ -313,10 +494,18 @@ int run_push(fv_ctx *ctx, const float *lb32, const double *lb64, const int *sym,
         if (s->since_check > 0 && (s->since_check == s->check_every || i == n - 1)) {
             const int q = (int)(s->nchecks & 1);
             int *anc_in = s->anc.p + (size_t)q * K, *anc_out = s->anc.p + (size_t)(q ^ 1) * K;
-            hipLaunchKernelGGL(fvk::stream_ancestors, dim3(nblk), dim3(fvk::ANC_BLOCK), 0, ctx->stream, arg_row(j), (int)s->since_check,
-                               ctx->K, anc_in, anc_out, ctl->acc[q]);
-            hipLaunchKernelGGL(fvk::stream_verdict, dim3(nblk), dim3(fvk::ANC_BLOCK), 0, ctx->stream, ctl, q, j, s->committed,
-                               arg_row(j), ctx->K, anc_out, s->path.p);
+            if (s->max_lag > 0) {
+                hipLaunchKernelGGL(fvk::stream_ancestors_lag, dim3(nblk), dim3(fvk::ANC_BLOCK), 0, ctx->stream, arg_row(j),
+                                   (int)s->since_check, ctx->K, anc_in, anc_out, ctl->acc[q], row(j), &ctl->best[q]);
+                hipLaunchKernelGGL(fvk::stream_decide, dim3(1), dim3(64), 0, ctx->stream, ctl, q, j, s->max_lag, anc_out, ctx->K);
+                hipLaunchKernelGGL(fvk::stream_apply, dim3(nblk), dim3(fvk::ANC_BLOCK), 0, ctx->stream, ctl, q, j, s->committed,
+                                   arg_row(j), ctx->K, anc_out, s->path.p, row(j));
+            } else {
+                hipLaunchKernelGGL(fvk::stream_ancestors, dim3(nblk), dim3(fvk::ANC_BLOCK), 0, ctx->stream, arg_row(j), (int)s->since_check,
+                                   ctx->K, anc_in, anc_out, ctl->acc[q]);
+                hipLaunchKernelGGL(fvk::stream_verdict, dim3(nblk), dim3(fvk::ANC_BLOCK), 0, ctx->stream, ctl, q, j, s->committed,
+                                   arg_row(j), ctx->K, anc_out, s->path.p);
+            }
             FV_HIP(hipGetLastError());
             s->nchecks += 1;
             s->since_check = 0;
@@ -327,6 +516,7 @@ int run_push(fv_ctx *ctx, const float *lb32, const double *lb64, const int *sym,
     FV_HIP(hipMemcpyAsync(s->h_ctl, ctl, sizeof(fvk::StreamCtl), hipMemcpyDeviceToHost, ctx->stream));
     FV_HIP(hipStreamSynchronize(ctx->stream));
     s->st.commits = s->h_ctl->commits;
+    lag_take(s);
     *committed_out = 0;
     if (s->h_ctl->dead) {
         s->dead = true;
@@ -367,6 +557,7 @@ int refused(fv_ctx *ctx, int rc)
 void end_stream(fv_ctx *ctx)
 {
     ctx->strm_stats = ctx->strm->st;
+    ctx->strm_lag = ctx->strm->lag;
     fvi::stream_drop(ctx);
 }
 
@@ -375,6 +566,8 @@ void drop_set(fv_ctx *ctx)
     fv_streams *g = ctx->set;
     if (!g) return;
     ctx->set_stats = g->st;
+    ctx->set_lag.clear();
+    for (int id = 0; g->slot && id < g->nslots; ++id) ctx->set_lag.push_back(g->slot[id].lag);
     if (g->h_ctl) (void)hipHostFree(g->h_ctl);
     delete g;                                    // (the device buffers free themselves)
     ctx->set = nullptr;
@@ -424,6 +617,8 @@ extern "C" int fv_stream_open(fv_ctx *ctx, long long lag_rows_hint, int check_ev
     const int rc = [&]() -> int {
         s->kernel = kernel;
         s->check_every = check_every ? check_every : STREAM_CHECK_DEFAULT;
+        s->max_lag = ctx->max_lag;
+        s->lag = lag_fresh(s->max_lag);
         FV_HIP(hipSetDevice(ctx->device));
         FV_HIP(ctx->d_counters.ensure(FV_NCOUNTERS));      // (the step kernels' statistics words, as every decode has them)
         FV_HIP(hipMemsetAsync(ctx->d_counters.p, 0, ctx->d_counters.bytes(), ctx->stream));
@@ -439,6 +634,7 @@ extern "C" int fv_stream_open(fv_ctx *ctx, long long lag_rows_hint, int check_ev
     s->st.kernel = kernel;
     s->st.arg_rows_capacity = (long long)s->cap;
     ctx->strm_stats = s->st;
+    ctx->strm_lag = s->lag;
     ctx->strm_any = true;
     return FV_OK;
 }
@@ -614,17 +810,21 @@ int set_room(fv_ctx *ctx, const SetCall &c)
 {
     fv_streams *g = ctx->set;
     std::vector<fv_stream_stats> was((size_t)c.nids);
+    std::vector<fv_lag_stats> was_lag((size_t)c.nids);
     for (int q = 0; q < c.nids; ++q) {
         StreamSeq &s = g->slot[c.ids[q]];
         was[(size_t)q] = s.st;
+        was_lag[(size_t)q] = s.lag;
         if (s.times == 0) {
             s.st = fv_stream_stats{};
             s.st.kernel = g->kernel; s.st.arg_rows_capacity = (long long)s.cap;
+            s.lag = lag_fresh(s.max_lag);
         }
         if (int rc = make_room(ctx, &s, c.n[(size_t)q], std::string(c.who) + ": " + slot_name(c.ids[q]), &g->st.syncs)) {
             for (int p = 0; p <= q; ++p)
                 if (g->slot[c.ids[p]].times == 0) {       // (the sequences that left keep theirs)
                     g->slot[c.ids[p]].st = was[(size_t)p];
+                    g->slot[c.ids[p]].lag = was_lag[(size_t)p];
                     g->slot[c.ids[p]].st.arg_rows_capacity = (long long)g->slot[c.ids[p]].cap;
                 }
             return rc;
@@ -671,7 +871,8 @@ int run_set_push(fv_ctx *ctx, const SetCall &c, int kind, const float *lb32, con
             g->st.task_steps += nb;
         }
         for (size_t base = 0; base < due.size(); base += fvk::CHECK_SLOTS) {
-            fvk::CheckArgs a;
+            fvk::LagArgs lg;
+            fvk::CheckArgs &a = lg.a;
             a.n = (int)std::min(due.size() - base, (size_t)fvk::CHECK_SLOTS);
             a.K = ctx->K;
             for (int d = 0; d < a.n; ++d) {
@@ -684,14 +885,21 @@ int run_set_push(fv_ctx *ctx, const SetCall &c, int kind, const float *lb32, con
                 cs.r = (int)s.since_check;
                 cs.anc_in = s.anc.p + (size_t)p * K; cs.anc_out = s.anc.p + (size_t)(p ^ 1) * K;
                 cs.ctl = s.d_ctl; cs.parity = p; cs.t = j; cs.base = s.committed; cs.path = s.path.p;
+                lg.l[d] = fvk::LagSlot{ row(s, j), s.max_lag };
                 s.nchecks += 1;
                 s.since_check = 0;
             }
-            for (int d = a.n; d < fvk::CHECK_SLOTS; ++d) a.s[d] = fvk::CheckSlot{};
-            hipLaunchKernelGGL(fvk::stream_ancestors_set, dim3(nblk, a.n), dim3(fvk::ANC_BLOCK), 0, ctx->stream, a);
-            hipLaunchKernelGGL(fvk::stream_verdict_set, dim3(nblk, a.n), dim3(fvk::ANC_BLOCK), 0, ctx->stream, a);
+            for (int d = a.n; d < fvk::CHECK_SLOTS; ++d) { a.s[d] = fvk::CheckSlot{}; lg.l[d] = fvk::LagSlot{}; }
+            if (g->max_lag > 0) {                // (fv_set_max_lag holds for every slot of the set)
+                hipLaunchKernelGGL(fvk::stream_ancestors_lag_set, dim3(nblk, a.n), dim3(fvk::ANC_BLOCK), 0, ctx->stream, lg);
+                hipLaunchKernelGGL(fvk::stream_decide_set, dim3(1, a.n), dim3(64), 0, ctx->stream, lg);
+                hipLaunchKernelGGL(fvk::stream_apply_set, dim3(nblk, a.n), dim3(fvk::ANC_BLOCK), 0, ctx->stream, lg);
+            } else {
+                hipLaunchKernelGGL(fvk::stream_ancestors_set, dim3(nblk, a.n), dim3(fvk::ANC_BLOCK), 0, ctx->stream, a);
+                hipLaunchKernelGGL(fvk::stream_verdict_set, dim3(nblk, a.n), dim3(fvk::ANC_BLOCK), 0, ctx->stream, a);
+            }
             FV_HIP(hipGetLastError());
-            g->st.check_launches += 2;
+            g->st.check_launches += g->max_lag > 0 ? 3 : 2;
             g->st.check_slots += a.n;
         }
     }
@@ -711,6 +919,7 @@ int run_set_push(fv_ctx *ctx, const SetCall &c, int kind, const float *lb32, con
     for (int q = 0; q < c.nids; ++q) {
         StreamSeq &s = g->slot[c.ids[q]];
         s.st.commits = s.h_ctl->commits;
+        lag_take(&s);
         if (s.h_ctl->dead) {
             s.dead = true;
             if (dead_detail.empty()) dead_detail = std::string(c.who) + ": " + slot_name(c.ids[q]) + ": no state of the current time has a predecessor";
@@ -783,6 +992,7 @@ extern "C" int fv_streams_open(fv_ctx *ctx, int nslots, long long lag_rows_hint,
         g->kernel = kernel;
         g->check_every = check_every ? check_every : STREAM_CHECK_DEFAULT;
         g->batch_cap = fvi::stream_batch_cap(ctx, kernel);
+        g->max_lag = ctx->max_lag;
         g->slot.reset(new (std::nothrow) StreamSeq[(size_t)nslots]);
         if (!g->slot) return FV_ERR_NOMEM;
         FV_HIP(hipSetDevice(ctx->device));
@@ -794,6 +1004,8 @@ extern "C" int fv_streams_open(fv_ctx *ctx, int nslots, long long lag_rows_hint,
         for (int id = 0; id < nslots; ++id) {
             StreamSeq *s = &g->slot[id];
             s->d_ctl = g->ctl.p + id; s->h_ctl = g->h_ctl + id;
+            s->max_lag = g->max_lag;
+            s->lag = lag_fresh(s->max_lag);
             if (int r = seq_alloc(ctx, s, cap)) return r;
             if (int r = seq_reset(ctx, s)) return r;
             s->st.kernel = kernel;
@@ -953,5 +1165,37 @@ extern "C" int fv_streams_last_stats(const fv_ctx *ctx, fv_streams_stats *out)
     if (!ctx || !out) return FV_ERR_ARG;
     if (!ctx->set_any) return FV_ERR_STATE;
     *out = ctx->set ? ctx->set->st : ctx->set_stats;
+    return FV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// fv_set_max_lag, fv_last_lag_stats: the bounded commit lag
+
+extern "C" int fv_set_max_lag(fv_ctx *ctx, long long max_lag)
+{
+    if (!ctx) return FV_ERR_ARG;
+    if (max_lag < 0) { ctx->detail = "fv_set_max_lag: max_lag >= 0 (0: unbounded)"; return FV_ERR_ARG; }
+    FV_NO_STREAM(ctx);
+    ctx->max_lag = max_lag;
+    return FV_OK;
+}
+
+extern "C" int fv_last_lag_stats(const fv_ctx *ctx, int slot, fv_lag_stats *out)
+{
+    if (!ctx || !out) return FV_ERR_ARG;
+    if (slot < 0) {
+        if (!ctx->strm_any) return FV_ERR_STATE;
+        *out = ctx->strm ? ctx->strm->lag : ctx->strm_lag;
+        return FV_OK;
+    }
+    if (!ctx->set_any) return FV_ERR_STATE;
+    if (ctx->set) {
+        const StreamSeq *s = set_slot(ctx, slot);
+        if (!s) return FV_ERR_ARG;
+        *out = s->lag;
+        return FV_OK;
+    }
+    if ((size_t)slot >= ctx->set_lag.size()) return FV_ERR_ARG;
+    *out = ctx->set_lag[(size_t)slot];
     return FV_OK;
 }

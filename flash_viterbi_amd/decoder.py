@@ -86,6 +86,15 @@ class StreamsStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LagStats(ctypes.Structure):
+    """fv_lag_stats: the forced commits of a lag-bounded stream or slot (fv_set_max_lag)."""
+    _fields_ = [("max_lag", ctypes.c_longlong), ("forced_commits", ctypes.c_longlong), ("pruned_states", ctypes.c_longlong),
+                ("first_forced_time", ctypes.c_longlong), ("last_forced_time", ctypes.c_longlong)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FlatInfo(ctypes.Structure):
     """fv_flat_info: one right-hand pass of the flat schedule."""
     _fields_ = [("L", ctypes.c_int), ("R", ctypes.c_int), ("generation", ctypes.c_int), ("batch", ctypes.c_int),
@@ -105,7 +114,8 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_stream_open", "fv_stream_push", "fv_stream_push_emissions", "fv_stream_pending", "fv_stream_close",
            "fv_stream_abort", "fv_stream_last_stats",
            "fv_streams_open", "fv_streams_push", "fv_streams_push_emissions", "fv_streams_pending", "fv_streams_close",
-           "fv_streams_abort", "fv_streams_end", "fv_streams_slot_stats", "fv_streams_last_stats"]
+           "fv_streams_abort", "fv_streams_end", "fv_streams_slot_stats", "fv_streams_last_stats",
+           "fv_set_max_lag", "fv_last_lag_stats"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select", "fv_test_device_alloc", "fv_test_device_free",
                 "fv_test_stage_emissions_ms", "fv_test_flat_poison", "fv_test_beam_forward", "fv_test_model_digest"]
@@ -193,6 +203,8 @@ def load_library():
     L.fv_streams_end.argtypes = [vp]
     L.fv_streams_slot_stats.argtypes = [vp, ci, ctypes.POINTER(StreamStats)]
     L.fv_streams_last_stats.argtypes = [vp, ctypes.POINTER(StreamsStats)]
+    L.fv_set_max_lag.argtypes = [vp, cll]
+    L.fv_last_lag_stats.argtypes = [vp, ci, ctypes.POINTER(LagStats)]
     L.fv_test_device_alloc.argtypes = [vp, ctypes.c_size_t, vp, ctypes.POINTER(vp)]
     L.fv_test_device_free.argtypes = [vp, vp]
     L.fv_test_stage_emissions_ms.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
@@ -611,6 +623,19 @@ class FlashViterbi:
     def streams_stats(self):
         s = StreamsStats()
         self._check(self._L.fv_streams_last_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    # ---- fv_set_max_lag: streams and sets opened afterwards commit at the latest max_lag steps behind a check (inexact)
+
+    def set_max_lag(self, max_lag):
+        """fv_set_max_lag: 0 unbounded (the default); >= 1: a check that finds more than one ancestor max_lag or more steps
+        past the anchor forces the commit of the best state's ancestor and prunes the other states."""
+        self._check(self._L.fv_set_max_lag(self._h, int(max_lag)))
+
+    def lag_stats(self, slot=None):
+        """fv_last_lag_stats of the single stream (slot=None) or of a slot of the set: a dict of LagStats' members."""
+        s = LagStats()
+        self._check(self._L.fv_last_lag_stats(self._h, -1 if slot is None else int(slot), ctypes.byref(s)))
         return s.as_dict()
 
     def decode_full(self, ob, n_split=1, mode=MODE_REFERENCE, T=None):

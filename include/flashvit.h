@@ -486,11 +486,54 @@ int fv_streams_abort(fv_ctx *ctx, int id);      /* drops slot id's sequence; the
 int fv_streams_end(fv_ctx *ctx);                /* frees the whole set, whatever its slots hold */
 int fv_streams_slot_stats(const fv_ctx *ctx, int id, fv_stream_stats *out);
 /* The open set, or the last one ended (FV_ERR_STATE: there never was one), summed over its life.  The launch counters
- * are bare launches: step_launches of task_steps tasks in all; check_launches, two per pair, serving check_slots
- * slot-checks; syncs: the times the host waited for the device (at most two per symbol push call, three per score push
- * call, one more per regrow, one per close). */
+ * are bare launches: step_launches of task_steps tasks in all; check_launches, two per pair (in a lag-bounded set,
+ * fv_set_max_lag, the pair becomes three launches: ancestors and best, decide, apply), serving check_slots slot-checks;
+ * syncs: the times the host waited for the device (at most two per symbol push call, three per score push call, one more
+ * per regrow, one per close). */
 typedef struct { long long calls, step_launches, task_steps, check_launches, check_slots, syncs; int nslots, batch_cap, kernel; double push_ms_total; } fv_streams_stats;
 int fv_streams_last_stats(const fv_ctx *ctx, fv_streams_stats *out);
+
+/* Online decodes with a bounded commit lag.
+ * A stream commits a piece only when every survivor path has merged into one ancestor at the anchor.  On models whose
+ * paths never merge (near-deterministic aligners, disconnected components, ties) that never happens: nothing is delivered
+ * before the close and the arg rows grow with T.  max_lag = L >= 1 bounds both, at the price of exactness.
+ *   The rule.  Checks happen when they happen without it (every check_every = C steps and after the last step of a
+ * push).  At a check at time t with anchor a and the set V of the ancestors of the states that have one: V empty, the
+ * stream is dead; one ancestor v, the commit (a, v) of every stream; more than one and t - a >= L, a FORCED commit: s* is
+ * the lowest index among the maxima of the score row of time t (fv_stream_close's end pick), v* its ancestor; every state
+ * whose ancestor is not v* is PRUNED — its score of time t becomes -inf, so no later cell can take it as its source —
+ * (a, v*) is committed exactly like a natural commit, the anchor moves to t and the survivors are re-anchored.
+ *   What this guarantees.
+ *   Connected path: the pieces and the close's piece concatenate to one path, every transition of which has a finite log.
+ *   Exact for the pruned model: path, float32 score and return code are bit for bit those of
+ * fv_decode_full(..., 1, FV_MODE_SINGLE_PASS) on the same input with the emission score of every pruned (t, s) cell set
+ * to -inf (pruning a cell after the step equals a -inf emission at that cell; every other cell of every row keeps its bits).
+ *   Bounded lag: after every accepted push fv_stream_pending <= 2 L + C - 2.  After any check either a commit just moved
+ * the anchor to t or t - a <= L - 1; consecutive checks lie at most C steps apart, so a commit at t_c settles the times
+ * up to an old anchor with t_c - a_old <= L - 1 + C; pending at a push end is (t - t_c) + (t_c - a_old), and before the
+ * first commit at most L.  Device memory is therefore O((largest push + 2 L + C) K) whatever the model.
+ *   What it costs.  The result is no longer the Viterbi path of the whole input.  It depends on where the checks fall, and
+ * so on how the input is cut into pushes (with check_every = 1 it does not).  A forced commit can end in FV_ERR_NO_PRED
+ * where the exact decode finds a path, because the best state of time t may be a dead end, as with any pruning; the stream
+ * then behaves like any dead stream.
+ *   No forced commit, nothing changes: with max_lag = 0, or a max_lag that is never reached, pieces, counts, score, return
+ * codes and every fv_stream_stats counter are those of the stream without a bound.
+ *
+ * fv_set_max_lag: 0 (default): unbounded.  >= 1: streams and sets opened afterwards force commits by the rule above.
+ * FV_ERR_ARG for a negative value, FV_ERR_STATE while a stream or a set is open (as fv_set_option).  Kept across
+ * fv_set_model*; applies to every slot of a set. */
+int fv_set_max_lag(fv_ctx *ctx, long long max_lag);
+
+typedef struct {
+    long long max_lag;            /* in force for this stream / slot */
+    long long forced_commits;     /* commits that were forced (counted in fv_stream_stats.commits too) */
+    long long pruned_states;      /* states with anc >= 0 and anc != v*, summed over the forced commits */
+    long long first_forced_time;  /* time t of the first forced commit, -1: none */
+    long long last_forced_time;
+} fv_lag_stats;
+/* slot < 0: the single stream (open, or the last closed/aborted); else slot of the set (open, or the last ended).
+ * FV_ERR_STATE: there never was one; FV_ERR_ARG: a slot outside the set. */
+int fv_last_lag_stats(const fv_ctx *ctx, int slot, fv_lag_stats *out);
 
 int fv_last_stats(const fv_ctx *ctx, fv_stats *out);
 const char *fv_strerror(int rc);
