@@ -307,7 +307,7 @@ extern "C" int fv_create(fv_ctx **out, int device)
         hipEventCreate(&ctx->ev_s1) != hipSuccess)
         return fail(FV_ERR_DEVICE);
     int rc = 0;
-    if ((rc = fvi::full_setup(ctx)) || (rc = fvi::beam_setup(ctx))) return fail(rc);
+    if ((rc = fvi::full_setup(ctx)) || (rc = fvi::beam_setup(ctx)) || (rc = fvi::sumprod_setup(ctx))) return fail(rc);
     *out = ctx;
     return FV_OK;
 }
@@ -390,6 +390,7 @@ static void drop_model(fv_ctx *ctx, bool keep_dense)
     drop_emissions(ctx, true);           // staged emission scores belong to the model they were staged under, and so does the map
     (void)hipStreamSynchronize(ctx->stream);
     ctx->LA64R.release(); ctx->LAQ16R.release();
+    ctx->SPA.release(); ctx->SPAT.release(); ctx->spa_ready = ctx->spat_ready = false;   // rebuilt by the next fv_loglik / fv_posteriors
     ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release();
     ctx->CSk.release(); ctx->CSq.release(); ctx->CS64.release(); ctx->CSoff.release(); ctx->CSnwb.release();
     ctx->CRptr.release(); ctx->CRcol.release(); ctx->CRlog.release(); ctx->csr_nnz = 0;

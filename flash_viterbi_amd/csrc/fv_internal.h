@@ -7,6 +7,7 @@
 //   fv_comm.hip     multi-GPU: partition, RCCL all-gather, merge, the single-process multi-device context
 //   fv_stream.hip   fv_stream_* / fv_streams_*: the online decode — the ancestor kernels, the buffers of a stream and of a set
 //                   of streams, and their entry points
+//   fv_sumprod.hip  fv_loglik / fv_loglik_batch / fv_posteriors: the sum-product kernels and their driver
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -238,6 +239,19 @@ struct fv_ctx {
     fv_lag_stats strm_lag{};
     std::vector<fv_lag_stats> set_lag;
 
+    // fv_loglik / fv_posteriors (fv_sumprod.hip).  SPA / SPAT: A and its transpose as float32, tile-major as
+    // LA32 with pads of 0, built on the device from LA64 by the first call that needs each; they belong to the model.
+    // sp_rows: the score rows of the forward pass (two per sequence, or all T of fv_posteriors), sp_beta: the backward
+    // pass's, sp_res: [refine counters | one loglik per sequence], sp_gamma / sp_path: results staged for the host
+    DevBuf<float> SPA, SPAT;
+    bool spa_ready = false, spat_ready = false;
+    DevBuf<double> sp_rows, sp_beta;
+    DevBuf<unsigned long long> sp_res;
+    DevBuf<float> sp_gamma;
+    DevBuf<int> sp_path;
+    fv_sumprod_stats sp_stats{};
+    bool sp_any = false;
+
     fv_stats stats{};
     // statistics of a decode about to start: everything cleared but what the model and the staged emissions own
     void start_stats(int kernel, int generations, long long table_bytes_per_step, double density_reported)
@@ -269,6 +283,7 @@ struct fv_ctx {
         f(d_hval); f(d_scores); f(d_slot_val); f(d_hstate); f(d_slot_state); f(d_flags); f(LA64R); f(LAQ16R); f(d_qaux);
         f(d_tie_list); f(d_cut); f(d_cand); f(d_cand_count); f(d_dupwin); f(d_doubt); f(d_doubt_count); f(d_needfull);
         f(d_seqof); f(d_passL); f(d_tie_count); f(d_csr_acc); f(d_csr_tie);
+        f(SPA); f(SPAT); f(sp_rows); f(sp_beta); f(sp_res); f(sp_gamma); f(sp_path);
     }
 };
 
@@ -419,6 +434,7 @@ int begin_decode(fv_ctx *ctx, const int *ob, int T);
 // big-LDS attributes of the kernels each translation unit owns
 int full_setup(fv_ctx *ctx);
 int beam_setup(fv_ctx *ctx);
+int sumprod_setup(fv_ctx *ctx);
 // fvk::init_rows lives with the full-state kernels; the beam driver starts its passes from the same rows
 int launch_init_rows(fv_ctx *ctx, const fvk::PassChunk &ch, float *rows);
 // What a stream (fv_stream.hip) takes from the full-state path, whose kernels live in fv_full.hip.

@@ -95,6 +95,17 @@ class LagStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SumprodStats(ctypes.Structure):
+    """fv_sumprod_stats: the last loglik / loglik_batch / posteriors call."""
+    _fields_ = [("call_ms", ctypes.c_double), ("gpu_ms", ctypes.c_double), ("step_launches", ctypes.c_longlong),
+                ("task_steps", ctypes.c_longlong), ("table_bytes_per_step", ctypes.c_longlong), ("device_bytes", ctypes.c_longlong),
+                ("refine_columns", ctypes.c_longlong), ("refine_finite", ctypes.c_longlong), ("passes", ctypes.c_int),
+                ("batch_cap", ctypes.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FlatInfo(ctypes.Structure):
     """fv_flat_info: one right-hand pass of the flat schedule."""
     _fields_ = [("L", ctypes.c_int), ("R", ctypes.c_int), ("generation", ctypes.c_int), ("batch", ctypes.c_int),
@@ -115,10 +126,12 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_stream_abort", "fv_stream_last_stats",
            "fv_streams_open", "fv_streams_push", "fv_streams_push_emissions", "fv_streams_pending", "fv_streams_close",
            "fv_streams_abort", "fv_streams_end", "fv_streams_slot_stats", "fv_streams_last_stats",
-           "fv_set_max_lag", "fv_last_lag_stats"]
+           "fv_set_max_lag", "fv_last_lag_stats",
+           "fv_loglik", "fv_loglik_batch", "fv_posteriors", "fv_last_sumprod_stats"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select", "fv_test_device_alloc", "fv_test_device_free",
-                "fv_test_stage_emissions_ms", "fv_test_flat_poison", "fv_test_beam_forward", "fv_test_model_digest"]
+                "fv_test_stage_emissions_ms", "fv_test_flat_poison", "fv_test_beam_forward", "fv_test_model_digest",
+                "fv_test_sumprod_rows"]
 TIE_TAG = 1 << 30
 # FV_TS_*: select-kernel instantiations reported by test_beam_select
 TS_BITS = {"topb_select<4,listed>": 1 << 0, "topb_select<4,derived>": 1 << 1, "topb_select<16,listed>": 1 << 2,
@@ -205,6 +218,11 @@ def load_library():
     L.fv_streams_last_stats.argtypes = [vp, ctypes.POINTER(StreamsStats)]
     L.fv_set_max_lag.argtypes = [vp, cll]
     L.fv_last_lag_stats.argtypes = [vp, ci, ctypes.POINTER(LagStats)]
+    L.fv_loglik.argtypes = [vp, vp, ci, ctypes.POINTER(ctypes.c_double)]
+    L.fv_loglik_batch.argtypes = [vp, vp, vp, ci, vp, vp]
+    L.fv_posteriors.argtypes = [vp, vp, ci, vp, cll, vp, ctypes.POINTER(ctypes.c_double)]
+    L.fv_last_sumprod_stats.argtypes = [vp, ctypes.POINTER(SumprodStats)]
+    L.fv_test_sumprod_rows.argtypes = [vp, vp, ci, vp, vp]
     L.fv_test_device_alloc.argtypes = [vp, ctypes.c_size_t, vp, ctypes.POINTER(vp)]
     L.fv_test_device_free.argtypes = [vp, vp]
     L.fv_test_stage_emissions_ms.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
@@ -637,6 +655,67 @@ class FlashViterbi:
         s = LagStats()
         self._check(self._L.fv_last_lag_stats(self._h, -1 if slot is None else int(slot), ctypes.byref(s)))
         return s.as_dict()
+
+    # ---- fv_loglik / fv_posteriors: forward-backward in float64
+
+    def loglik(self, ob=None, T=None):
+        """fv_loglik: log P(ob | model) as a float; -inf (no exception) when the model gives the sequence probability 0.
+        ob=None with T=...: on the first T rows staged by set_emissions."""
+        ob, ptr, T = _ob_arg(ob, T)
+        out = ctypes.c_double(0)
+        rc = self._L.fv_loglik(self._h, ptr, T, ctypes.byref(out))
+        if rc != ERR_NO_PRED:
+            self._check(rc)
+        return float(out.value)
+
+    def loglik_batch(self, obs, lengths=None):
+        """fv_loglik_batch: obs is a list of int sequences (lengths >= 1, may differ).  Returns (logliks: float64 array,
+        statuses: int32 array), per sequence what loglik gives for it alone (the same bits); a sequence of probability 0
+        reports -inf and ERR_NO_PRED and does not raise.  obs=None with lengths=[...]: as decode_full_batch."""
+        ob, ptr, offsets = _batch_arg(obs, lengths)
+        nseq = offsets.size - 1
+        ll = np.zeros(max(nseq, 1), dtype=np.float64)
+        statuses = np.zeros(max(nseq, 1), dtype=np.int32)
+        rc = self._L.fv_loglik_batch(self._h, ptr, _p(offsets), nseq, _p(ll), _p(statuses))
+        if rc != ERR_NO_PRED:
+            self._check(rc)
+        return ll[:nseq], statuses[:nseq]
+
+    def posteriors(self, ob=None, T=None, want_gamma=True, out=None):
+        """fv_posteriors: returns (gamma, path, loglik).  gamma is a float32 array [T, K] of state posteriors (None with
+        want_gamma=False, or with out=...), path the int32 posterior decoding, loglik a float.  out: a device pointer
+        (from test_device_alloc or a torch tensor's data_ptr()) or (pointer, ld) that receives gamma on the device, row
+        pitch ld (default K) in elements.  A sequence of probability 0 gives (None, a path of -1, -inf) and does not raise."""
+        ob, ptr, T = _ob_arg(ob, T)
+        path = np.empty(T, dtype=np.int32)
+        ll = ctypes.c_double(0)
+        gamma, gptr, ld = None, None, self.K
+        if out is not None:
+            gptr, ld = out if isinstance(out, tuple) else (out, self.K)
+            gptr = ctypes.c_void_p(int(gptr))
+        elif want_gamma:
+            gamma = np.empty((T, self.K), dtype=np.float32)
+            gptr = _p(gamma)
+        rc = self._L.fv_posteriors(self._h, ptr, T, gptr, int(ld), _p(path), ctypes.byref(ll))
+        if rc != ERR_NO_PRED:
+            self._check(rc)
+        return (None if rc == ERR_NO_PRED else gamma), path, float(ll.value)
+
+    def sumprod_stats(self):
+        """fv_last_sumprod_stats: a dict of SumprodStats' members for the last loglik / loglik_batch / posteriors."""
+        s = SumprodStats()
+        self._check(self._L.fv_last_sumprod_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    def test_sumprod_rows(self, ob=None, T=None):
+        """fv_test_sumprod_rows: (alpha[T, K], beta[T, K], rc) of fv_posteriors' two passes, float64."""
+        ob, ptr, T = _ob_arg(ob, T)
+        alpha = np.empty((T, self.K), dtype=np.float64)
+        beta = np.empty((T, self.K), dtype=np.float64)
+        rc = self._L.fv_test_sumprod_rows(self._h, ptr, T, _p(alpha), _p(beta))
+        if rc != ERR_NO_PRED:
+            self._check(rc)
+        return alpha, beta, rc
 
     def decode_full(self, ob, n_split=1, mode=MODE_REFERENCE, T=None):
         """ob=None with T=...: decode the first T rows staged by set_emissions (so for every decode_* below)."""

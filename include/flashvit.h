@@ -535,6 +535,76 @@ typedef struct {
  * FV_ERR_STATE: there never was one; FV_ERR_ARG: a slot outside the set. */
 int fv_last_lag_stats(const fv_ctx *ctx, int slot, fv_lag_stats *out);
 
+/* Forward-backward on the device: how probable an observation sequence is under the model (fv_loglik,
+ * fv_loglik_batch) and how sure the model is of a state at a time (fv_posteriors).  The reference has neither: it answers
+ * the arg-max question only.  The sum-product recurrences run on the context's own float64 tables.
+ *   Definitions.  All values are float64.  LPi[j] = log((double)Pi[j]), LA[i][j] = log((double)A[i][j]).  The emission
+ * term e[t][j] is log((double)B[j][ob[t]]); with ob == NULL it is the staged E64[t][j] (fv_set_emissions), under exactly
+ * the ob == NULL rules of the decode calls, an emission map included (the staged tables are T x K).
+ *     alpha[0][j] = LPi[j] + e[0][j]           alpha[t][j] = e[t][j] + log sum_i exp(alpha[t-1][i] + LA[i][j])
+ *     beta[T-1][i] = 0                         beta[t][i] = log sum_j exp(LA[i][j] + e[t+1][j] + beta[t+1][j])
+ *     loglik = log sum_j exp(alpha[T-1][j])    gamma[t][j] = exp(alpha[t][j] + beta[t][j] - loglik)
+ * gamma is rounded to float32 and is 0 where either term is -inf.  gamma_out[t * ld + j], ld >= K in elements, is a host
+ * or a device pointer (hipPointerGetAttributes decides, as in fv_set_emissions; a device block on the context's GPU) and
+ * may be NULL; what lies beyond K in a row is not touched.  path_out[t] (may be NULL) is the lowest index among the maxima
+ * over j of the float64 value alpha[t][j] + beta[t][j] that the device holds: posterior decoding.  loglik_out may be NULL
+ * in fv_posteriors.  T >= 1.
+ *   fv_loglik_batch: the offsets contract of fv_decode_full_batch (sequences back to back, offsets[0] == 0, nseq + 1
+ * non-decreasing entries, the total below 2^31; ob == NULL: sequence s on staged rows offsets[s] .. offsets[s+1]), but
+ * every length >= 1 is allowed.  loglik_out[s] and status_out[s] (may be NULL) are per sequence exactly what fv_loglik on
+ * that sequence delivers, the other sequences are intact, and the return value is the most negative status.  The
+ * sequences advance in lock-step and share the step launches, up to batch_cap tasks per sweep of the table.
+ *   Return codes.  FV_OK.  FV_ERR_NO_PRED when loglik is -inf (the model gives the sequence probability 0): then
+ * *loglik_out = -inf, path_out is filled with -1 and gamma_out is not written.  Refused before any device work, with a
+ * detail text: T < 1, bad pointers or offsets, a symbol outside [0, M), ob == NULL with too few staged rows, ld < K
+ * (FV_ERR_ARG); no model, or an open stream or set (FV_ERR_STATE); multi-device, partitioned and communicator contexts
+ * (FV_ERR_UNSUPPORTED); a model set by fv_set_model_sparse (FV_ERR_UNSUPPORTED, below); K > 20192, the largest K whose
+ * float64 score row the step kernel can stage in LDS (FV_ERR_UNSUPPORTED); a working set beyond the free device memory
+ * (FV_ERR_NOMEM, with the byte count, before anything is allocated).  Model entries above 1 and emission scores above 0
+ * are accepted: nothing here is a filter.
+ *   Memory.  The step streams A itself as float32 (4 bytes per cell, tile-major as the float32 log table, pads 0), built
+ * on the device from the stored logs by the first call; fv_posteriors' backward pass streams the transposed table, built
+ * by the first fv_posteriors.  Both tables belong to the model, cost 4 * K^2 bytes each and are dropped by fv_set_model
+ * and fv_set_model_sparse.  fv_loglik keeps two float64 rows per sequence, fv_posteriors 16 * T * K bytes of alpha and
+ * beta (plus 4 * T * K for a host gamma_out).
+ *   Guarantees.
+ *   1. Accuracy.  Let u = 2^-53 and Amax the largest finite |alpha| or |beta| of the call.  Every finite alpha[t][j] lies
+ * within 2 * (t + 1) * (K + 1024) * u * max(1, Amax) of the exact value, beta[t][i] within the same bound with T - t in
+ * place of t + 1, loglik within the bound at t = T - 1.  The bound is derived, not measured: a sum of K non-negative terms
+ * has relative error at most K * u in any order, an exp argument of magnitude up to 745 carries a relative error of at
+ * most 745 * u, and an error carried in from the row before passes through a convex combination without growing, so the
+ * errors add once per step.  -inf comes out where, and only where, the exact value is -inf.
+ *   2. No flush.  The step works in linear space on p[i] = exp(alpha[i] - max alpha); a column all of whose probability
+ * comes from states more than 745 below the row's maximum still comes out finite and within the bound: a column whose
+ * linear sum falls below 2^-800 is re-evaluated per column as max_i + log sum_i exp(alpha[i] + LA[i][j] - max_i).  The
+ * threshold holds for every float32 model entry: what exp flushed, times an entry below 2^128, over K <= 20192 rows, is
+ * less than 2^-879, below u times any sum that is not re-evaluated.
+ *   3. Reproducible bits.  The same call twice gives the same bits; fv_loglik_batch gives, per sequence, the bits of
+ * fv_loglik, whatever the grouping and whatever FV_OPT_MAX_BATCH; fv_posteriors' *loglik_out has the bits of fv_loglik.
+ * A task's summation order does not depend on the launch form, and no reduction uses floating-point atomics.
+ *   Out of scope.  Models set by fv_set_model_sparse are refused: the forward walk over the stored entries is
+ * straightforward, but the backward pass needs the out-edge form on the device, and nothing holds that today.
+ * Multi-device contexts, streaming likelihoods and Baum-Welch accumulators (xi) are not offered either. */
+int fv_loglik(fv_ctx *ctx, const int *ob, int T, double *loglik_out);
+int fv_loglik_batch(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq,
+                    double *loglik_out, int *status_out);
+int fv_posteriors(fv_ctx *ctx, const int *ob, int T, float *gamma_out, long long ld,
+                  int *path_out, double *loglik_out);
+/* The last fv_loglik, fv_loglik_batch or fv_posteriors that ran (FV_ERR_STATE: there never was one). */
+typedef struct {
+    double call_ms;                 /* host wall time of the call (enqueue .. final sync) */
+    double gpu_ms;                  /* HIP-event time from its first to its last kernel */
+    long long step_launches;        /* launches of the sum-product step kernel */
+    long long task_steps;           /* sum over launches of the tasks advanced by one K * K step */
+    long long table_bytes_per_step; /* bytes of the linear table one step launch streams (4 per cell) */
+    long long device_bytes;         /* device working set of the context after the call */
+    long long refine_columns;       /* columns re-evaluated in the exact per-column form (linear sum below 2^-800) */
+    long long refine_finite;        /* ... those that came out finite */
+    int passes;                     /* 1: forward only (loglik), 2: forward and backward (posteriors) */
+    int batch_cap;                  /* most tasks one step launch takes: the smallest of FV_OPT_MAX_BATCH, 4 and the float64 rows 160 KiB of LDS hold */
+} fv_sumprod_stats;
+int fv_last_sumprod_stats(const fv_ctx *ctx, fv_sumprod_stats *out);
+
 int fv_last_stats(const fv_ctx *ctx, fv_stats *out);
 const char *fv_strerror(int rc);
 const char *fv_last_error_detail(const fv_ctx *ctx);

@@ -72,6 +72,11 @@ int fv_test_model_digest(const float *A, const long long *row_ptr, const int *co
                          const float *Pi, int K, int M, unsigned long long *digests, double *params, char *detail,
                          int detail_cap);
 
+/* The two passes of fv_posteriors alone (same admission, same kernels, same launches), then their T x K float64 rows copied
+ * back: alpha_out[t * K + j] and beta_out[t * K + i] as defined in flashvit.h.  Either pointer may be NULL.  Returns what
+ * fv_posteriors returns (FV_ERR_NO_PRED with the rows still copied).  It exists so that a failing step can be located. */
+int fv_test_sumprod_rows(fv_ctx *ctx, const int *ob, int T, double *alpha_out, double *beta_out);
+
 /* One slot set of a beam step: n entries {val[e], state[e]} (states in [0, K)), beam <= n <= beam + 32. */
 typedef struct { const float *val; const int *state; int n; } fv_test_beam_set;
 /* One entry of a candidate list: a score and its destination state. */
