@@ -393,7 +393,8 @@ static void drop_model(fv_ctx *ctx, bool keep_dense)
     ctx->SPA.release(); ctx->SPAT.release(); ctx->spa_ready = ctx->spat_ready = false;   // rebuilt by the next fv_loglik / fv_posteriors
     ctx->SPdata.release(); ctx->SPoff.release(); ctx->SPnwb.release();
     ctx->CSk.release(); ctx->CSq.release(); ctx->CS64.release(); ctx->CSoff.release(); ctx->CSnwb.release();
-    ctx->CRptr.release(); ctx->CRcol.release(); ctx->CRlog.release(); ctx->csr_nnz = 0;
+    ctx->CRptr.release(); ctx->CRcol.release(); ctx->CRlog.release(); ctx->csr_nnz = 0; ctx->csr_vectors = 0;
+    ctx->CSlin.release(); ctx->CRlin.release(); ctx->cslin_ready = ctx->crlin_ready = false;   // (fv_set_sparse_sumprod: rebuilt on first use)
     ctx->d_csr_acc.release(); ctx->d_csr_tie.release();      // (sized by K; a dense-set model never reads them)
     ctx->EMap.release();
     if (!keep_dense) { ctx->LA32.release(); ctx->LA16.release(); ctx->LAQ16.release(); ctx->LA64.release(); }
@@ -465,7 +466,7 @@ static int upload_csr(fv_ctx *ctx, const HostCsr &h, const long long *row_ptr, c
     if (nnz)
         if ((rc = upload(ctx, ctx->CRcol, col, nnz)) || (rc = upload(ctx, ctx->CRlog, h.rlog.data(), nnz))) return rc;
     if ((rc = finish_upload(ctx, e))) return rc;
-    ctx->csr = true; ctx->csr_nnz = (long long)nnz;
+    ctx->csr = true; ctx->csr_nnz = (long long)nnz; ctx->csr_vectors = (long long)nv;
     ctx->stats.density = ctx->density;
     return FV_OK;
 }

@@ -251,6 +251,17 @@ struct fv_ctx {
     DevBuf<int> sp_path;
     fv_sumprod_stats sp_stats{};
     bool sp_any = false;
+    // fv_set_sparse_sumprod: the same calls on a model set by fv_set_model_sparse (kept across
+    // fv_set_model*).  CSlin / CRlin: the stored values as float32 at the index of CS64 / CRlog (pads 0), built on the
+    // device from those logs by the first call that needs each; they belong to the model.  sp_scaled / sp_scale_m: the
+    // memory form's scaled rows of one step launch, and [their maxima | the partial maxima of sumprod_rowmax].
+    // sp_forms: the FV_SPF_* bits of the step kernels the last call launched (fv_test_sumprod_forms)
+    int opt_sparse_sumprod = 0;
+    long long csr_vectors = 0;   // vectors of the CSC-32 table (CSk holds one element more when there is none)
+    DevBuf<float> CSlin, CRlin;
+    bool cslin_ready = false, crlin_ready = false;
+    DevBuf<double> sp_scaled, sp_scale_m;
+    unsigned long long sp_forms = 0;
 
     fv_stats stats{};
     // statistics of a decode about to start: everything cleared but what the model and the staged emissions own
@@ -284,6 +295,7 @@ struct fv_ctx {
         f(d_tie_list); f(d_cut); f(d_cand); f(d_cand_count); f(d_dupwin); f(d_doubt); f(d_doubt_count); f(d_needfull);
         f(d_seqof); f(d_passL); f(d_tie_count); f(d_csr_acc); f(d_csr_tie);
         f(SPA); f(SPAT); f(sp_rows); f(sp_beta); f(sp_res); f(sp_gamma); f(sp_path);
+        f(CSlin); f(CRlin); f(sp_scaled); f(sp_scale_m);
     }
 };
 

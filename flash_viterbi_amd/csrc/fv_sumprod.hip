@@ -1,6 +1,8 @@
 // fv_sumprod.hip — fv_loglik / fv_loglik_batch / fv_posteriors: the sum-product kernels and their driver.
 // One driver runs forward passes of any number of sequences in lock-step (two float64 rows each); fv_posteriors keeps
 // every row of one sequence, runs the backward pass on the transposed table and finishes with the gamma kernel.
+// A model set by fv_set_model_sparse takes the same driver under fv_set_sparse_sumprod: the step launches
+// are sumprod_step_csr / sumprod_back_csr over the stored transitions, everything else is shared.
 #include "fv_internal.h"
 #include "flashvit_testing.h"
 #include "fv_sumprod_kernels.hip.inc"
@@ -20,25 +22,102 @@ int batch_cap(const fv_ctx *ctx)
     return cap;
 }
 
+// How a call sweeps the transitions: the dense tables, or (csr) the stored entries with the scaled rows in LDS or (mem) in
+// workspace rows.  cap: most tasks of one step launch.
+struct Route { bool csr, mem; int cap; };
+
+Route route_of(const fv_ctx *ctx)
+{
+    Route r{ ctx->csr, false, batch_cap(ctx) };
+    if (r.csr && (ctx->opt_csr_mem || r.cap < 1)) {
+        r.mem = true;
+        r.cap = 1;
+        while (r.cap * 2 <= fvs::MAX_NB && r.cap * 2 <= ctx->opt_max_batch) r.cap *= 2;
+    }
+    return r;
+}
+
+template <int NB> constexpr unsigned long long form_bit(int base) { return 1ull << (base + (NB == 1 ? 0 : NB == 2 ? 1 : 2)); }
+
 template <int NB>
 void launch_step_nb(fv_ctx *ctx, const StepTask *tasks, const float *tab)
 {
     fvs::StepArgs<NB> a;
     for (int b = 0; b < NB; ++b) a.t[b] = tasks[b];
     const int ntiles = (ctx->K + fvk::TILE_W - 1) / fvk::TILE_W;
+    ctx->sp_forms |= form_bit<NB>(FV_SPF_DENSE_SHIFT);
     hipLaunchKernelGGL(fvs::sumprod_step<NB>, dim3(ntiles), dim3(fvs::BLOCK), step_lds_bytes(NB, ctx->nrows), ctx->stream, a, tab,
                        ctx->K, ctx->nrows, ctx->sp_res.p);
 }
 
-// n tasks in launches of the largest instantiation that fits the cap and what is left: every task's bits are those of
-// a launch of its own
-int launch_steps(fv_ctx *ctx, const std::vector<StepTask> &tasks, const float *tab, int cap, fv_sumprod_stats &st)
+// the memory form's scale launch for the NB tasks of the step launch that follows: row maxima, then p and m
+int launch_scale(fv_ctx *ctx, const StepTask *tasks, int nb)
 {
+    fvs::StepArgs<fvs::MAX_NB> a{};
+    for (int b = 0; b < nb; ++b) a.t[b] = tasks[b];
+    double *m = ctx->sp_scale_m.p, *part = m + fvs::MAX_NB;
+    const unsigned blocks = (unsigned)((ctx->K + fvs::SCALE_BLOCK * fvs::SCALE_PER_THREAD - 1) / (fvs::SCALE_BLOCK * fvs::SCALE_PER_THREAD));
+    hipLaunchKernelGGL(fvs::sumprod_rowmax, dim3(fvs::SCALE_PARTS, nb), dim3(fvs::SCALE_BLOCK), 0, ctx->stream, a, ctx->K, part);
+    hipLaunchKernelGGL(fvs::sumprod_scale, dim3(blocks, nb), dim3(fvs::SCALE_BLOCK), 0, ctx->stream, a, ctx->K, part, ctx->sp_scaled.p,
+                       (size_t)ctx->K, m);
+    FV_HIP(hipGetLastError());
+    return 0;
+}
+
+template <int NB, bool MEM>
+void launch_csr_nb(fv_ctx *ctx, const StepTask *tasks, bool backward)
+{
+    const fvs::ScaledRows rows = MEM ? fvs::ScaledRows{ ctx->sp_scaled.p, ctx->sp_scale_m.p } : fvs::ScaledRows{ nullptr, nullptr };
+    if (!backward) {
+        fvs::CsrStepArgs<NB> a;
+        a.ck = ctx->CSk.p; a.clin = ctx->CSlin.p; a.c64 = ctx->CS64.p; a.tile_off = ctx->CSoff.p; a.tile_nwb = ctx->CSnwb.p;
+        a.counters = ctx->sp_res.p;
+        a.K = ctx->K; a.nrows = ctx->nrows; a.ntiles = (ctx->K + fvk::TILE_W - 1) / fvk::TILE_W; a.tiles_per_xcd = (a.ntiles + 7) / 8;
+        a.s = rows;
+        for (int b = 0; b < NB; ++b) a.t[b] = tasks[b];
+        ctx->sp_forms |= form_bit<NB>(MEM ? FV_SPF_CSR_FWD_MEM_SHIFT : FV_SPF_CSR_FWD_LDS_SHIFT);
+        hipLaunchKernelGGL((fvs::sumprod_step_csr<NB, MEM>), dim3(a.tiles_per_xcd * 8), dim3(fvs::CSR_BLOCK),
+                           fvs::csr_step_lds_doubles(NB, ctx->nrows, MEM) * sizeof(double), ctx->stream, a);
+    } else {
+        fvs::CsrBackArgs<NB> a;
+        a.rptr = ctx->CRptr.p; a.rcol = ctx->CRcol.p; a.rlin = ctx->CRlin.p; a.rlog = ctx->CRlog.p;
+        a.counters = ctx->sp_res.p;
+        a.K = ctx->K; a.nrows = ctx->nrows;
+        a.s = rows;
+        for (int b = 0; b < NB; ++b) a.t[b] = tasks[b];
+        ctx->sp_forms |= form_bit<NB>(MEM ? FV_SPF_CSR_BACK_MEM_SHIFT : FV_SPF_CSR_BACK_LDS_SHIFT);
+        hipLaunchKernelGGL((fvs::sumprod_back_csr<NB, MEM>), dim3((ctx->K + fvs::BACK_ROWS - 1) / fvs::BACK_ROWS), dim3(fvs::BLOCK),
+                           fvs::csr_back_lds_doubles(NB, ctx->nrows, MEM) * sizeof(double), ctx->stream, a);
+    }
+}
+
+template <int NB>
+int launch_csr(fv_ctx *ctx, const StepTask *tasks, const Route &r, bool backward)
+{
+    if (r.mem) {
+        if (int rc = launch_scale(ctx, tasks, NB)) return rc;
+        launch_csr_nb<NB, true>(ctx, tasks, backward);
+    } else {
+        launch_csr_nb<NB, false>(ctx, tasks, backward);
+    }
+    return 0;
+}
+
+// n tasks in launches of the largest instantiation that fits the cap and what is left: every task's bits are those of
+// a launch of its own.  backward: the transposed table, or the walk over the caller's rows.
+int launch_steps(fv_ctx *ctx, const std::vector<StepTask> &tasks, const Route &r, bool backward, fv_sumprod_stats &st)
+{
+    const float *tab = backward ? ctx->SPAT.p : ctx->SPA.p;
     size_t at = 0;
     while (at < tasks.size()) {
-        int nb = 1;
-        while (nb * 2 <= cap && (size_t)nb * 2 <= tasks.size() - at) nb *= 2;
-        if (nb == 4) launch_step_nb<4>(ctx, &tasks[at], tab);
+        int nb = 1, rc = 0;
+        while (nb * 2 <= r.cap && (size_t)nb * 2 <= tasks.size() - at) nb *= 2;
+        if (r.csr) {
+            rc = nb == 4 ? launch_csr<4>(ctx, &tasks[at], r, backward) : nb == 2 ? launch_csr<2>(ctx, &tasks[at], r, backward)
+                                                                                 : launch_csr<1>(ctx, &tasks[at], r, backward);
+            if (rc) return rc;
+        }
+        else if (nb == 4) launch_step_nb<4>(ctx, &tasks[at], tab);
         else if (nb == 2) launch_step_nb<2>(ctx, &tasks[at], tab);
         else launch_step_nb<1>(ctx, &tasks[at], tab);
         FV_HIP(hipGetLastError());
@@ -71,12 +150,12 @@ int admission(fv_ctx *ctx, const char *who, const int *&ob, long long T)
         return FV_ERR_UNSUPPORTED;
     }
     if (ctx->K == 0) { ctx->detail = w + ": no model"; return FV_ERR_STATE; }
-    if (ctx->csr) {
+    if (ctx->csr && !ctx->opt_sparse_sumprod) {
         ctx->detail = w + ": models set by fv_set_model_sparse are not supported (the backward pass needs the out-edge form "
                           "on the device); set the model with fv_set_model";
         return FV_ERR_UNSUPPORTED;
     }
-    if (batch_cap(ctx) < 1) {
+    if (!ctx->csr && batch_cap(ctx) < 1) {
         ctx->detail = w + ": K = " + std::to_string(ctx->K) + " is beyond the float64 score row the step kernel stages in LDS (K <= 20192)";
         return FV_ERR_UNSUPPORTED;
     }
@@ -97,6 +176,46 @@ int build_table(fv_ctx *ctx, bool transpose)
     return 0;
 }
 
+// the linear values of a CSR-set model, built on the device from CS64 / CRlog on first use (the buffers are granted by the caller)
+int build_lin(fv_ctx *ctx, bool rows)
+{
+    bool &ready = rows ? ctx->crlin_ready : ctx->cslin_ready;
+    if (ready) return 0;
+    const size_t n = rows ? (size_t)ctx->csr_nnz : 4 * (size_t)ctx->csr_vectors;
+    if (n) {
+        hipLaunchKernelGGL(fvs::sumprod_build_lin, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                           rows ? ctx->CRlog.p : ctx->CS64.p, rows ? ctx->CRlin.p : ctx->CSlin.p, n);
+        FV_HIP(hipGetLastError());
+    }
+    ready = true;
+    return 0;
+}
+
+// what a call asks for beside its rows: the table(s) it sweeps and, in the memory form, the scaled rows of one step launch
+void want_tables(fv_ctx *ctx, fvi::Wants &wants, const Route &r, bool backward)
+{
+    if (!r.csr) {
+        const size_t tab = (size_t)((ctx->K + fvk::TILE_W - 1) / fvk::TILE_W) * ctx->nrows * fvk::TILE_W;
+        wants.add(ctx->SPA, tab);
+        if (backward) wants.add(ctx->SPAT, tab);
+        return;
+    }
+    wants.add(ctx->CSlin, std::max<size_t>(4 * (size_t)ctx->csr_vectors, 1));
+    if (backward) wants.add(ctx->CRlin, std::max<size_t>((size_t)ctx->csr_nnz, 1));
+    if (r.mem) {
+        wants.add(ctx->sp_scaled, (size_t)fvs::MAX_NB * ctx->K);
+        wants.add(ctx->sp_scale_m, (size_t)fvs::MAX_NB * (1 + fvs::SCALE_PARTS));
+    }
+}
+
+int build_tables(fv_ctx *ctx, const Route &r, bool backward)
+{
+    int rc = 0;
+    if (r.csr) { if ((rc = build_lin(ctx, false)) || (backward && (rc = build_lin(ctx, true)))) return rc; }
+    else if ((rc = build_table(ctx, false)) || (backward && (rc = build_table(ctx, true)))) return rc;
+    return 0;
+}
+
 struct Call {
     clk::time_point t0 = clk::now();
     fv_sumprod_stats st{};
@@ -105,7 +224,8 @@ struct Call {
 int begin_call(fv_ctx *ctx, Call &c, int passes, int cap, size_t nres)
 {
     c.st.passes = passes; c.st.batch_cap = cap;
-    c.st.table_bytes_per_step = 4ll * ((ctx->K + fvk::TILE_W - 1) / fvk::TILE_W) * ctx->nrows * fvk::TILE_W;
+    c.st.table_bytes_per_step = ctx->csr ? 8ll * 4 * ctx->csr_vectors : 4ll * ((ctx->K + fvk::TILE_W - 1) / fvk::TILE_W) * ctx->nrows * fvk::TILE_W;
+    ctx->sp_forms = 0;
     FV_HIP(hipMemsetAsync(ctx->sp_res.p, 0, nres * sizeof(unsigned long long), ctx->stream));
     FV_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
     return 0;
@@ -149,16 +269,19 @@ int loglik_batch(fv_ctx *ctx, const char *who, const int *ob, const long long *o
     if (int rc = fvi::batch_symbols(ctx, who, ob, offsets, nseq)) return rc;
     FV_HIP(hipSetDevice(ctx->device));
 
-    const int K = ctx->K, cap = batch_cap(ctx);
+    const Route route = route_of(ctx);
+    const int K = ctx->K, cap = route.cap;
     const size_t tab = (size_t)((K + fvk::TILE_W - 1) / fvk::TILE_W) * ctx->nrows * fvk::TILE_W, nres = fvs::NCOUNTERS + (size_t)nseq;
     fvi::Wants wants;
-    wants.what = w + " workspace"; wants.dominant = "linear table " + std::to_string(4ull * tab);
-    wants.add(ctx->SPA, tab); wants.add(ctx->sp_rows, (size_t)nseq * 2 * K); wants.add(ctx->sp_res, nres);
+    wants.what = w + " workspace";
+    wants.dominant = route.csr ? "linear values " + std::to_string(16ull * (unsigned long long)ctx->csr_vectors) : "linear table " + std::to_string(4ull * tab);
+    want_tables(ctx, wants, route, false);
+    wants.add(ctx->sp_rows, (size_t)nseq * 2 * K); wants.add(ctx->sp_res, nres);
     if (int rc = fvi::grant(ctx, wants, true)) return rc;
 
     Call c;
     int rc = 0;
-    if ((rc = begin_call(ctx, c, 1, cap, nres)) || (rc = build_table(ctx, false))) return rc;
+    if ((rc = begin_call(ctx, c, 1, cap, nres)) || (rc = build_tables(ctx, route, false))) return rc;
     auto row = [&](int s, long long t) { return ctx->sp_rows.p + ((size_t)s * 2 + (size_t)(t & 1)) * K; };
     auto emis = [&](int s, long long t) { return ctx->view.lb64 + (size_t)ob[offsets[s] + t] * K; };
     std::vector<StepTask> tasks;
@@ -172,7 +295,7 @@ int loglik_batch(fv_ctx *ctx, const char *who, const int *ob, const long long *o
         tasks.clear();
         for (int s = 0; s < nseq; ++s)
             if (offsets[s + 1] - offsets[s] > t) tasks.push_back({ row(s, t - 1), nullptr, emis(s, t), row(s, t) });
-        if ((rc = launch_steps(ctx, tasks, ctx->SPA.p, cap, c.st))) return rc;
+        if ((rc = launch_steps(ctx, tasks, route, false, c.st))) return rc;
     }
     tasks.clear();
     double *d_ll = reinterpret_cast<double *>(ctx->sp_res.p + fvs::NCOUNTERS);
@@ -205,25 +328,27 @@ int posteriors(fv_ctx *ctx, const char *who, const int *ob, int T, float *gamma_
             return FV_ERR_ARG;
         }
     FV_HIP(hipSetDevice(ctx->device));
-    const int K = ctx->K, cap = batch_cap(ctx);
+    const Route route = route_of(ctx);
+    const int K = ctx->K, cap = route.cap;
     bool gamma_on_device = false;
     if (gamma_out) {
         const fvi::PointerPlace at = fvi::pointer_place(gamma_out);
         gamma_on_device = at.on_device;
         if (at.on_device && at.device != ctx->device) { ctx->detail = w + ": gamma_out lies on another device than the context"; return FV_ERR_ARG; }
     }
-    const size_t tab = (size_t)((K + fvk::TILE_W - 1) / fvk::TILE_W) * ctx->nrows * fvk::TILE_W, nres = fvs::NCOUNTERS + 1;
+    const size_t nres = fvs::NCOUNTERS + 1;
     const size_t cells = (size_t)T * K;
     fvi::Wants wants;
     wants.what = w + " workspace"; wants.dominant = "alpha and beta rows " + std::to_string(16ull * cells);
-    wants.add(ctx->SPA, tab); wants.add(ctx->SPAT, tab); wants.add(ctx->sp_rows, cells); wants.add(ctx->sp_beta, cells);
+    want_tables(ctx, wants, route, true);
+    wants.add(ctx->sp_rows, cells); wants.add(ctx->sp_beta, cells);
     wants.add(ctx->sp_res, nres); wants.add(ctx->sp_path, (size_t)T);
     if (gamma_out && !gamma_on_device) wants.add(ctx->sp_gamma, cells);
     if (int rc = fvi::grant(ctx, wants, true)) return rc;
 
     Call c;
     int rc = 0;
-    if ((rc = begin_call(ctx, c, 2, cap, nres)) || (rc = build_table(ctx, false)) || (rc = build_table(ctx, true))) return rc;
+    if ((rc = begin_call(ctx, c, 2, cap, nres)) || (rc = build_tables(ctx, route, true))) return rc;
     double *alpha = ctx->sp_rows.p, *beta = ctx->sp_beta.p;
     auto emis = [&](int t) { return ctx->view.lb64 + (size_t)ob[t] * K; };
     std::vector<StepTask> one(1);
@@ -231,7 +356,7 @@ int posteriors(fv_ctx *ctx, const char *who, const int *ob, int T, float *gamma_
     if ((rc = launch_small(ctx, one, false))) return rc;
     for (int t = 1; t < T; ++t) {
         one[0] = { alpha + (size_t)(t - 1) * K, nullptr, emis(t), alpha + (size_t)t * K };
-        if ((rc = launch_steps(ctx, one, ctx->SPA.p, cap, c.st))) return rc;
+        if ((rc = launch_steps(ctx, one, route, false, c.st))) return rc;
     }
     double *d_ll = reinterpret_cast<double *>(ctx->sp_res.p + fvs::NCOUNTERS);
     one[0] = { alpha + (size_t)(T - 1) * K, nullptr, nullptr, d_ll };
@@ -240,7 +365,7 @@ int posteriors(fv_ctx *ctx, const char *who, const int *ob, int T, float *gamma_
     if ((rc = launch_small(ctx, one, false))) return rc;
     for (int t = T - 2; t >= 0; --t) {
         one[0] = { beta + (size_t)(t + 1) * K, emis(t + 1), nullptr, beta + (size_t)t * K };
-        if ((rc = launch_steps(ctx, one, ctx->SPAT.p, cap, c.st))) return rc;
+        if ((rc = launch_steps(ctx, one, route, true, c.st))) return rc;
     }
     if (gamma_out || path_out) {
         float *g = !gamma_out ? nullptr : gamma_on_device ? gamma_out : ctx->sp_gamma.p;
@@ -272,7 +397,11 @@ int posteriors(fv_ctx *ctx, const char *who, const int *ob, int T, float *gamma_
 int fvi::sumprod_setup(fv_ctx *ctx)
 {
     const void *steps[] = { reinterpret_cast<const void *>(&fvs::sumprod_step<1>), reinterpret_cast<const void *>(&fvs::sumprod_step<2>),
-                            reinterpret_cast<const void *>(&fvs::sumprod_step<4>) };
+                            reinterpret_cast<const void *>(&fvs::sumprod_step<4>),
+                            reinterpret_cast<const void *>(&fvs::sumprod_step_csr<1, false>), reinterpret_cast<const void *>(&fvs::sumprod_step_csr<2, false>),
+                            reinterpret_cast<const void *>(&fvs::sumprod_step_csr<4, false>),
+                            reinterpret_cast<const void *>(&fvs::sumprod_back_csr<1, false>), reinterpret_cast<const void *>(&fvs::sumprod_back_csr<2, false>),
+                            reinterpret_cast<const void *>(&fvs::sumprod_back_csr<4, false>) };
     for (const void *f : steps) FV_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, fvk::LDS_LIMIT));
     return 0;
 }
@@ -308,5 +437,22 @@ extern "C" int fv_last_sumprod_stats(const fv_ctx *ctx, fv_sumprod_stats *out)
     if (!ctx || !out) return FV_ERR_ARG;
     if (!ctx->sp_any) return FV_ERR_STATE;
     *out = ctx->sp_stats;
+    return FV_OK;
+}
+
+extern "C" int fv_set_sparse_sumprod(fv_ctx *ctx, int on)
+{
+    if (!ctx) return FV_ERR_ARG;
+    if (on != 0 && on != 1) { ctx->detail = "fv_set_sparse_sumprod: on is 0 (the default) or 1"; return FV_ERR_ARG; }
+    FV_NO_STREAM(ctx);
+    ctx->opt_sparse_sumprod = on;
+    return FV_OK;
+}
+
+extern "C" int fv_test_sumprod_forms(const fv_ctx *ctx, unsigned long long *mask_out)
+{
+    if (!ctx || !mask_out) return FV_ERR_ARG;
+    if (!ctx->sp_any) return FV_ERR_STATE;
+    *mask_out = ctx->sp_forms;
     return FV_OK;
 }

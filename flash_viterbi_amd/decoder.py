@@ -127,11 +127,21 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_streams_open", "fv_streams_push", "fv_streams_push_emissions", "fv_streams_pending", "fv_streams_close",
            "fv_streams_abort", "fv_streams_end", "fv_streams_slot_stats", "fv_streams_last_stats",
            "fv_set_max_lag", "fv_last_lag_stats",
-           "fv_loglik", "fv_loglik_batch", "fv_posteriors", "fv_last_sumprod_stats"]
+           "fv_loglik", "fv_loglik_batch", "fv_posteriors", "fv_last_sumprod_stats", "fv_set_sparse_sumprod"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select", "fv_test_device_alloc", "fv_test_device_free",
                 "fv_test_stage_emissions_ms", "fv_test_flat_poison", "fv_test_beam_forward", "fv_test_model_digest",
-                "fv_test_sumprod_rows"]
+                "fv_test_sumprod_rows", "fv_test_sumprod_forms"]
+# FV_SPF_* of include/flashvit_testing.h (test_sumprod_forms): three bits per family of sum-product step kernels, for NB = 1, 2, 4
+# tasks at shift + 0, + 1, + 2
+SPF_DENSE_SHIFT, SPF_CSR_FWD_LDS_SHIFT, SPF_CSR_FWD_MEM_SHIFT, SPF_CSR_BACK_LDS_SHIFT, SPF_CSR_BACK_MEM_SHIFT = 0, 3, 6, 9, 12
+
+
+def spf_family(shift):
+    """FV_SPF_FAMILY: the three bits of one family"""
+    return 7 << shift
+
+
 TIE_TAG = 1 << 30
 # FV_TS_*: select-kernel instantiations reported by test_beam_select
 TS_BITS = {"topb_select<4,listed>": 1 << 0, "topb_select<4,derived>": 1 << 1, "topb_select<16,listed>": 1 << 2,
@@ -223,6 +233,8 @@ def load_library():
     L.fv_posteriors.argtypes = [vp, vp, ci, vp, cll, vp, ctypes.POINTER(ctypes.c_double)]
     L.fv_last_sumprod_stats.argtypes = [vp, ctypes.POINTER(SumprodStats)]
     L.fv_test_sumprod_rows.argtypes = [vp, vp, ci, vp, vp]
+    L.fv_set_sparse_sumprod.argtypes = [vp, ci]
+    L.fv_test_sumprod_forms.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
     L.fv_test_device_alloc.argtypes = [vp, ctypes.c_size_t, vp, ctypes.POINTER(vp)]
     L.fv_test_device_free.argtypes = [vp, vp]
     L.fv_test_stage_emissions_ms.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
@@ -716,6 +728,18 @@ class FlashViterbi:
         if rc != ERR_NO_PRED:
             self._check(rc)
         return alpha, beta, rc
+
+    def set_sparse_sumprod(self, on):
+        """fv_set_sparse_sumprod: 0 (the default) / 1: loglik, loglik_batch and posteriors run on a model set by
+        set_model_sparse (refused under 0); kept across set_model / set_model_sparse, no effect on a model set by set_model."""
+        self._check(self._L.fv_set_sparse_sumprod(self._h, int(on)))
+
+    def test_sumprod_forms(self):
+        """fv_test_sumprod_forms: the SPF_* bits of the step kernels the last loglik / loglik_batch / posteriors /
+        test_sumprod_rows launched."""
+        mask = ctypes.c_ulonglong(0)
+        self._check(self._L.fv_test_sumprod_forms(self._h, ctypes.byref(mask)))
+        return int(mask.value)
 
     def decode_full(self, ob, n_split=1, mode=MODE_REFERENCE, T=None):
         """ob=None with T=...: decode the first T rows staged by set_emissions (so for every decode_* below)."""

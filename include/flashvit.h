@@ -582,9 +582,9 @@ int fv_last_lag_stats(const fv_ctx *ctx, int slot, fv_lag_stats *out);
  *   3. Reproducible bits.  The same call twice gives the same bits; fv_loglik_batch gives, per sequence, the bits of
  * fv_loglik, whatever the grouping and whatever FV_OPT_MAX_BATCH; fv_posteriors' *loglik_out has the bits of fv_loglik.
  * A task's summation order does not depend on the launch form, and no reduction uses floating-point atomics.
- *   Out of scope.  Models set by fv_set_model_sparse are refused: the forward walk over the stored entries is
- * straightforward, but the backward pass needs the out-edge form on the device, and nothing holds that today.
- * Multi-device contexts, streaming likelihoods and Baum-Welch accumulators (xi) are not offered either. */
+ *   Out of scope.  Models set by fv_set_model_sparse are refused unless fv_set_sparse_sumprod (below) has switched their
+ * route on; the refusal's text is the one this library always gave.  Multi-device contexts, streaming likelihoods and
+ * Baum-Welch accumulators (xi) are not offered either. */
 int fv_loglik(fv_ctx *ctx, const int *ob, int T, double *loglik_out);
 int fv_loglik_batch(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq,
                     double *loglik_out, int *status_out);
@@ -604,6 +604,28 @@ typedef struct {
     int batch_cap;                  /* most tasks one step launch takes: the smallest of FV_OPT_MAX_BATCH, 4 and the float64 rows 160 KiB of LDS hold */
 } fv_sumprod_stats;
 int fv_last_sumprod_stats(const fv_ctx *ctx, fv_sumprod_stats *out);
+/* fv_loglik, fv_loglik_batch and fv_posteriors on a model set by fv_set_model_sparse.  on = 0 (the
+ * default): such a model is refused, as above, and every call behaves as it did before this function existed.  on = 1: the
+ * three calls run on the stored transitions, with the definitions, return codes, ob == NULL rules (emission maps
+ * included), gamma_out / ld rules and FV_ERR_NO_PRED behaviour above; model entries above 1 and staged scores above 0 are
+ * accepted.  Any other value: FV_ERR_ARG.  While a stream or a set of streams is open: FV_ERR_STATE, as fv_set_option.  The
+ * setting is kept across fv_set_model and fv_set_model_sparse; on a model set by fv_set_model it changes nothing.
+ * Multi-device, partitioned and communicator contexts stay refused.
+ *   K.  The K <= 20192 limit does not apply to this route: K is bounded by memory.  The forward step walks the CSC-32 table the
+ * decodes walk, the backward step the caller's rows; both stream 8 bytes per entry: the source state or column and the
+ * stored value itself as float32 (CSlin, CRlin: built on the device from the stored float64 logs by the first call that
+ * needs each, 4 bytes per padded entry and 4 bytes per stored entry; they belong to the model and are dropped by
+ * fv_set_model and fv_set_model_sparse).  While NB float64 score rows fit LDS a step stages them there; beyond (every K
+ * above 20192), or under FV_OPT_DEBUG bit 31, a small scale launch leaves p[i] = exp(row[i] - max) in workspace rows
+ * (8 * 4 * K bytes) and the step gathers from memory.  fv_sumprod_stats.table_bytes_per_step is 8 bytes per padded entry
+ * of the CSC-32 table, batch_cap in the memory form the smaller of FV_OPT_MAX_BATCH and 4; step_launches and task_steps
+ * count step kernels, not scale launches.
+ *   Guarantees 1 to 3 hold unchanged.  The 2^-800 threshold holds for any K < 2^31: what exp flushed, times an entry below
+ * 2^128, over fewer than 2^31 terms, is less than 2^-863, below u * 2^-800.  Order rule: a task's summation order is a
+ * function of the stored table alone; it does not depend on the number of tasks in a launch, on FV_OPT_MAX_BATCH, on how a
+ * batch is grouped, or on whether the score rows were staged in LDS or read from memory, and stored entries equal to 0 change
+ * no bit of any result: they are the same as absent entries. */
+int fv_set_sparse_sumprod(fv_ctx *ctx, int on);
 
 int fv_last_stats(const fv_ctx *ctx, fv_stats *out);
 const char *fv_strerror(int rc);

@@ -77,6 +77,18 @@ int fv_test_model_digest(const float *A, const long long *row_ptr, const int *co
  * fv_posteriors returns (FV_ERR_NO_PRED with the rows still copied).  It exists so that a failing step can be located. */
 int fv_test_sumprod_rows(fv_ctx *ctx, const int *ob, int T, double *alpha_out, double *beta_out);
 
+/* The step-kernel instantiations the last fv_loglik, fv_loglik_batch, fv_posteriors or fv_test_sumprod_rows launched, as FV_SPF_*
+ * bits (recorded on the host, launch by launch; scale launches, init rows, final sums and the gamma kernel are not step
+ * kernels).  FV_ERR_ARG: a NULL pointer; FV_ERR_STATE: no such call has run.  Three bits per family, for NB = 1, 2, 4 tasks:
+ * bit (shift + 0), (shift + 1), (shift + 2). */
+#define FV_SPF_DENSE_SHIFT         0    /* sumprod_step<NB>: a model set by fv_set_model, forward and backward */
+#define FV_SPF_CSR_FWD_LDS_SHIFT   3    /* sumprod_step_csr<NB, false>: fv_set_sparse_sumprod, scaled rows staged in LDS */
+#define FV_SPF_CSR_FWD_MEM_SHIFT   6    /* sumprod_step_csr<NB, true>: scaled rows left in memory by the scale launch */
+#define FV_SPF_CSR_BACK_LDS_SHIFT  9    /* sumprod_back_csr<NB, false> */
+#define FV_SPF_CSR_BACK_MEM_SHIFT  12   /* sumprod_back_csr<NB, true> */
+#define FV_SPF_FAMILY(shift)       (7ull << (shift))
+int fv_test_sumprod_forms(const fv_ctx *ctx, unsigned long long *mask_out);
+
 /* One slot set of a beam step: n entries {val[e], state[e]} (states in [0, K)), beam <= n <= beam + 32. */
 typedef struct { const float *val; const int *state; int n; } fv_test_beam_set;
 /* One entry of a candidate list: a score and its destination state. */
