@@ -21,7 +21,8 @@ HOST_LIB = os.path.join(PKG, "libfvhost.so")
 HIP_LIB = os.path.join(PKG, "libflashvit.so")
 
 HIP_SOURCES = ["fv_context.hip", "fv_full.hip", "fv_beam.hip", "fv_comm.hip", "fv_stream.hip", "fv_sumprod.hip", "fv_schedule.cpp", "fv_model.cpp"]
-HIP_DEPS = ["fv_internal.h", "fv_layout.h", "fv_device_common.h", "fv_kernels.hip.inc", "fv_beam_kernels.hip.inc", "fv_sumprod_kernels.hip.inc", "fv_schedule.h"]
+HIP_DEPS = ["fv_internal.h", "fv_layout.h", "fv_device_common.h", "fv_kernels.hip.inc", "fv_beam_kernels.hip.inc", "fv_sumprod_kernels.hip.inc", "fv_counts_kernels.hip.inc",
+            "fv_schedule.h"]
 OBJ_DIR = os.path.join(PKG, "_obj")
 # The timing build keeps the kernel switches that change results (FV_OPT_DEBUG bits 0, 4, 11, 12: parts of a kernel
 # left out to time the rest); tools/ load it, the shipped library refuses those bits (fv_set_option: FV_ERR_ARG).

@@ -7,7 +7,7 @@
 //   fv_comm.hip     multi-GPU: partition, RCCL all-gather, merge, the single-process multi-device context
 //   fv_stream.hip   fv_stream_* / fv_streams_*: the online decode — the ancestor kernels, the buffers of a stream and of a set
 //                   of streams, and their entry points
-//   fv_sumprod.hip  fv_loglik / fv_loglik_batch / fv_posteriors: the sum-product kernels and their driver
+//   fv_sumprod.hip  fv_loglik / fv_loglik_batch / fv_posteriors: the sum-product kernels and their driver; fv_expected_counts
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -262,6 +262,14 @@ struct fv_ctx {
     bool cslin_ready = false, crlin_ready = false;
     DevBuf<double> sp_scaled, sp_scale_m;
     unsigned long long sp_forms = 0;
+    // fv_expected_counts (fv_sumprod.hip).  ct_p / ct_q: the scaled rows P and Q of the sequence in flight
+    // ((T - 1) x K each), ct_wide: its wide-time flags, ct_ob: the call's observations; the call's float64 accumulators
+    // ct_trans (K x K, unless trans_out is a device block), ct_emit (K x M) and ct_vec [init | occ]; ct_emit_seq: the
+    // emission sums of the sequence in flight
+    DevBuf<double> ct_p, ct_q, ct_trans, ct_emit, ct_emit_seq, ct_vec;
+    DevBuf<int> ct_ob, ct_wide;
+    fv_counts_stats ct_stats{};
+    bool ct_any = false;
 
     fv_stats stats{};
     // statistics of a decode about to start: everything cleared but what the model and the staged emissions own
@@ -296,6 +304,7 @@ struct fv_ctx {
         f(d_seqof); f(d_passL); f(d_tie_count); f(d_csr_acc); f(d_csr_tie);
         f(SPA); f(SPAT); f(sp_rows); f(sp_beta); f(sp_res); f(sp_gamma); f(sp_path);
         f(CSlin); f(CRlin); f(sp_scaled); f(sp_scale_m);
+        f(ct_p); f(ct_q); f(ct_trans); f(ct_emit); f(ct_emit_seq); f(ct_vec); f(ct_ob); f(ct_wide);
     }
 };
 

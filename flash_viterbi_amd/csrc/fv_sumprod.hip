@@ -3,9 +3,12 @@
 // every row of one sequence, runs the backward pass on the transposed table and finishes with the gamma kernel.
 // A model set by fv_set_model_sparse takes the same driver under fv_set_sparse_sumprod: the step launches
 // are sumprod_step_csr / sumprod_back_csr over the stored transitions, everything else is shared.
+// fv_expected_counts runs the two passes of fv_posteriors per sequence and the counting kernels of
+// fv_counts_kernels.hip.inc behind them.
 #include "fv_internal.h"
 #include "flashvit_testing.h"
 #include "fv_sumprod_kernels.hip.inc"
+#include "fv_counts_kernels.hip.inc"
 
 namespace {
 
@@ -314,6 +317,31 @@ int loglik_batch(fv_ctx *ctx, const char *who, const int *ob, const long long *o
     return worst;
 }
 
+// The two passes of one sequence, every launch single-task: the alpha rows, loglik into *d_ll, the beta rows.  emis(t): the
+// emission row of time t.
+template <class Emis>
+int two_passes(fv_ctx *ctx, const Route &route, int T, Emis &&emis, double *alpha, double *beta, double *d_ll, fv_sumprod_stats &st)
+{
+    const int K = ctx->K;
+    int rc = 0;
+    std::vector<StepTask> one(1);
+    one[0] = { ctx->LPi64.p, nullptr, emis(0), alpha };
+    if ((rc = launch_small(ctx, one, false))) return rc;
+    for (int t = 1; t < T; ++t) {
+        one[0] = { alpha + (size_t)(t - 1) * K, nullptr, emis(t), alpha + (size_t)t * K };
+        if ((rc = launch_steps(ctx, one, route, false, st))) return rc;
+    }
+    one[0] = { alpha + (size_t)(T - 1) * K, nullptr, nullptr, d_ll };
+    if ((rc = launch_small(ctx, one, true))) return rc;
+    one[0] = { nullptr, nullptr, nullptr, beta + (size_t)(T - 1) * K };
+    if ((rc = launch_small(ctx, one, false))) return rc;
+    for (int t = T - 2; t >= 0; --t) {
+        one[0] = { beta + (size_t)(t + 1) * K, emis(t + 1), nullptr, beta + (size_t)t * K };
+        if ((rc = launch_steps(ctx, one, route, true, st))) return rc;
+    }
+    return 0;
+}
+
 // fv_posteriors and fv_test_sumprod_rows: alpha_out / beta_out are the hook's
 int posteriors(fv_ctx *ctx, const char *who, const int *ob, int T, float *gamma_out, long long ld, int *path_out, double *loglik_out,
                double *alpha_out, double *beta_out)
@@ -351,22 +379,8 @@ int posteriors(fv_ctx *ctx, const char *who, const int *ob, int T, float *gamma_
     if ((rc = begin_call(ctx, c, 2, cap, nres)) || (rc = build_tables(ctx, route, true))) return rc;
     double *alpha = ctx->sp_rows.p, *beta = ctx->sp_beta.p;
     auto emis = [&](int t) { return ctx->view.lb64 + (size_t)ob[t] * K; };
-    std::vector<StepTask> one(1);
-    one[0] = { ctx->LPi64.p, nullptr, emis(0), alpha };
-    if ((rc = launch_small(ctx, one, false))) return rc;
-    for (int t = 1; t < T; ++t) {
-        one[0] = { alpha + (size_t)(t - 1) * K, nullptr, emis(t), alpha + (size_t)t * K };
-        if ((rc = launch_steps(ctx, one, route, false, c.st))) return rc;
-    }
     double *d_ll = reinterpret_cast<double *>(ctx->sp_res.p + fvs::NCOUNTERS);
-    one[0] = { alpha + (size_t)(T - 1) * K, nullptr, nullptr, d_ll };
-    if ((rc = launch_small(ctx, one, true))) return rc;
-    one[0] = { nullptr, nullptr, nullptr, beta + (size_t)(T - 1) * K };
-    if ((rc = launch_small(ctx, one, false))) return rc;
-    for (int t = T - 2; t >= 0; --t) {
-        one[0] = { beta + (size_t)(t + 1) * K, emis(t + 1), nullptr, beta + (size_t)t * K };
-        if ((rc = launch_steps(ctx, one, route, true, c.st))) return rc;
-    }
+    if ((rc = two_passes(ctx, route, T, emis, alpha, beta, d_ll, c.st))) return rc;
     if (gamma_out || path_out) {
         float *g = !gamma_out ? nullptr : gamma_on_device ? gamma_out : ctx->sp_gamma.p;
         hipLaunchKernelGGL(fvs::sumprod_gamma, dim3(T), dim3(fvs::BLOCK), 0, ctx->stream, alpha, beta, d_ll, K, g,
@@ -390,6 +404,131 @@ int posteriors(fv_ctx *ctx, const char *who, const int *ob, int T, float *gamma_
     FV_HIP(hipStreamSynchronize(ctx->stream));
     publish(ctx, c);
     return dead ? FV_ERR_NO_PRED : FV_OK;
+}
+
+// fv_expected_counts.  Sequence by sequence on the one stream: posteriors()'s two passes, then the scale
+// launch, the xi kernel and the gamma sums, each adding the sequence's finished values into the call's accumulators.  The
+// host learns which sequences were dead from the logliks, after the call's one wait.
+int expected_counts(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, double *trans_out, long long ld, double *emit_out,
+                    double *init_out, double *occ_out, double *loglik_out, int *status_out)
+{
+    const std::string w = "fv_expected_counts";
+    if (!offsets || nseq < 1) { ctx->detail = w + ": offsets != NULL and nseq >= 1"; return FV_ERR_ARG; }
+    if (offsets[0] != 0) { ctx->detail = w + ": offsets[0] must be 0"; return FV_ERR_ARG; }
+    long long longest = 0;
+    for (int s = 0; s < nseq; ++s) {
+        const long long len = offsets[s + 1] - offsets[s];
+        if (len < 0) { ctx->detail = w + ": offsets decrease at sequence " + std::to_string(s); return FV_ERR_ARG; }
+        if (len < 1) { ctx->detail = w + ": sequence " + std::to_string(s) + " has no observation (T >= 1)"; return FV_ERR_ARG; }
+        if (offsets[s + 1] > 0x7fffffffLL) { ctx->detail = w + ": more than 2^31 - 1 observations in all (at sequence " + std::to_string(s) + ")"; return FV_ERR_ARG; }
+        longest = std::max(longest, len);
+    }
+    if (!ob && emit_out) { ctx->detail = w + ": emit_out must be NULL with ob == NULL (staged emissions have no symbol alphabet)"; return FV_ERR_ARG; }
+    FV_NO_STREAM(ctx);
+    if (ctx->csr && !ctx->group && !ctx->comm && ctx->nranks <= 1) {
+        ctx->detail = w + ": models set by fv_set_model_sparse are not supported, with or without fv_set_sparse_sumprod (the "
+                          "counts over the stored transitions are a follow-up); set the model with fv_set_model";
+        return FV_ERR_UNSUPPORTED;
+    }
+    const bool staged = !ob;
+    if (int rc = admission(ctx, "fv_expected_counts", ob, offsets[nseq])) return rc;
+    const int K = ctx->K, M = ctx->M;
+    if (trans_out && (ld < K || ld > (1ll << 59) / K)) { ctx->detail = w + ": ld >= K"; return FV_ERR_ARG; }
+    if (int rc = fvi::batch_symbols(ctx, "fv_expected_counts", ob, offsets, nseq)) return rc;
+    FV_HIP(hipSetDevice(ctx->device));
+    bool trans_on_device = false;
+    if (trans_out) {
+        const fvi::PointerPlace at = fvi::pointer_place(trans_out);
+        trans_on_device = at.on_device;
+        if (at.on_device && at.device != ctx->device) { ctx->detail = w + ": trans_out lies on another device than the context"; return FV_ERR_ARG; }
+    }
+
+    const Route route = route_of(ctx);
+    const size_t total = (size_t)offsets[nseq], cells = (size_t)longest * K, pq = std::max<size_t>((size_t)(longest - 1) * K, 1);
+    const size_t nres = fvs::NCOUNTERS + (size_t)nseq + 1, km = (size_t)K * std::max(M, 1);
+    const bool want_emit = emit_out && !staged, want_vec = init_out || occ_out;
+    fvi::Wants wants;
+    wants.what = w + " workspace"; wants.dominant = "alpha, beta, P and Q rows " + std::to_string(16ull * cells + 16ull * (cells - K));
+    want_tables(ctx, wants, route, true);
+    wants.add(ctx->sp_rows, cells); wants.add(ctx->sp_beta, cells); wants.add(ctx->sp_res, nres);
+    wants.add(ctx->ct_ob, total);
+    if (trans_out) { wants.add(ctx->ct_p, pq); wants.add(ctx->ct_q, pq); wants.add(ctx->ct_wide, (size_t)longest); }
+    if (trans_out && !trans_on_device) wants.add(ctx->ct_trans, (size_t)K * K);
+    if (want_emit) { wants.add(ctx->ct_emit, km); wants.add(ctx->ct_emit_seq, km); }
+    if (want_vec) wants.add(ctx->ct_vec, 2 * (size_t)K);
+    if (int rc = fvi::grant(ctx, wants, true)) return rc;
+
+    const clk::time_point t0 = clk::now();
+    fv_counts_stats cs{};
+    fv_sumprod_stats steps{};
+    const unsigned long long forms = ctx->sp_forms;         // fv_test_sumprod_forms keeps reporting the sum-product calls
+    int rc = 0;
+    FV_HIP(hipMemsetAsync(ctx->sp_res.p, 0, nres * sizeof(unsigned long long), ctx->stream));
+    FV_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
+    if ((rc = build_tables(ctx, route, true))) return rc;
+    FV_HIP(hipMemcpyAsync(ctx->ct_ob.p, ob, total * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    double *acc = !trans_out ? nullptr : trans_on_device ? trans_out : ctx->ct_trans.p;
+    const long long acc_ld = trans_on_device ? ld : (long long)K;
+    if (acc) FV_HIP(hipMemset2DAsync(acc, (size_t)acc_ld * sizeof(double), 0, (size_t)K * sizeof(double), (size_t)K, ctx->stream));
+    if (want_emit) FV_HIP(hipMemsetAsync(ctx->ct_emit.p, 0, km * sizeof(double), ctx->stream));
+    if (want_vec) FV_HIP(hipMemsetAsync(ctx->ct_vec.p, 0, 2 * (size_t)K * sizeof(double), ctx->stream));
+    double *alpha = ctx->sp_rows.p, *beta = ctx->sp_beta.p;
+    double *d_ll = reinterpret_cast<double *>(ctx->sp_res.p + fvs::NCOUNTERS);
+    unsigned long long *d_wide = ctx->sp_res.p + fvs::NCOUNTERS + (size_t)nseq;
+    const unsigned tiles = (unsigned)((K + fvc::TILE - 1) / fvc::TILE);
+    for (int s = 0; s < nseq && !rc; ++s) {
+        const int T = (int)(offsets[s + 1] - offsets[s]);
+        const int *sob = ob + offsets[s], *d_sob = ctx->ct_ob.p + offsets[s];
+        auto emis = [&](int t) { return ctx->view.lb64 + (size_t)sob[t] * K; };
+        if ((rc = two_passes(ctx, route, T, emis, alpha, beta, d_ll + s, steps))) break;
+        if (acc && T >= 2) {
+            hipLaunchKernelGGL(fvc::counts_scale, dim3(T - 1), dim3(fvc::SCALE_BLOCK), 0, ctx->stream, alpha, beta, ctx->view.lb64, d_sob,
+                               d_ll + s, K, ctx->ct_p.p, ctx->ct_q.p, ctx->ct_wide.p, d_wide);
+            hipLaunchKernelGGL(fvc::counts_xi, dim3(tiles, tiles), dim3(fvc::XI_BLOCK), 0, ctx->stream, ctx->ct_p.p, ctx->ct_q.p,
+                               ctx->ct_wide.p, d_ll + s, T - 1, K, ctx->nrows, ctx->SPA.p, ctx->LA64.p, acc, acc_ld);
+            cs.xi_launches += 1;
+        }
+        if (want_emit || want_vec) {
+            if (want_emit) FV_HIP(hipMemsetAsync(ctx->ct_emit_seq.p, 0, km * sizeof(double), ctx->stream));
+            hipLaunchKernelGGL(fvc::counts_gamma, dim3((K + fvc::GAMMA_BLOCK - 1) / fvc::GAMMA_BLOCK), dim3(fvc::GAMMA_BLOCK), 0, ctx->stream,
+                               alpha, beta, d_ll + s, d_sob, T, K, M, init_out ? ctx->ct_vec.p : nullptr,
+                               occ_out ? ctx->ct_vec.p + K : nullptr, want_emit ? ctx->ct_emit_seq.p : nullptr);
+            if (want_emit)
+                hipLaunchKernelGGL(fvc::counts_add, dim3((unsigned)((km + 255) / 256)), dim3(256), 0, ctx->stream, ctx->ct_emit.p,
+                                   ctx->ct_emit_seq.p, d_ll + s, km);
+        }
+        FV_HIP(hipGetLastError());
+    }
+    ctx->sp_forms = forms;
+    if (rc) return rc;
+    FV_HIP(hipEventRecord(ctx->ev_stop, ctx->stream));
+    std::vector<unsigned long long> res(nres);
+    FV_HIP(hipMemcpyAsync(res.data(), ctx->sp_res.p, nres * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (trans_out && !trans_on_device)
+        FV_HIP(hipMemcpy2DAsync(trans_out, (size_t)ld * sizeof(double), ctx->ct_trans.p, (size_t)K * sizeof(double), (size_t)K * sizeof(double),
+                                (size_t)K, hipMemcpyDeviceToHost, ctx->stream));
+    if (want_emit) FV_HIP(hipMemcpyAsync(emit_out, ctx->ct_emit.p, km * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (init_out) FV_HIP(hipMemcpyAsync(init_out, ctx->ct_vec.p, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (occ_out) FV_HIP(hipMemcpyAsync(occ_out, ctx->ct_vec.p + K, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    FV_HIP(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    FV_HIP(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+    int worst = FV_OK;
+    for (int s = 0; s < nseq; ++s) {
+        const double ll = as_double(res[fvs::NCOUNTERS + (size_t)s]);
+        const int st = ll > -HUGE_VAL ? FV_OK : FV_ERR_NO_PRED;
+        if (loglik_out) loglik_out[s] = ll;
+        if (status_out) status_out[s] = st;
+        worst = std::min(worst, st);
+        if (st == FV_OK) cs.times += offsets[s + 1] - offsets[s]; else cs.dead_sequences += 1;
+    }
+    cs.gpu_ms = ms; cs.sequences = nseq;
+    cs.step_launches = steps.step_launches; cs.task_steps = steps.task_steps;
+    cs.wide_times = (long long)res[fvs::NCOUNTERS + (size_t)nseq];
+    cs.call_ms = ms_since(t0);
+    cs.device_bytes = (long long)fvi::device_bytes(ctx);
+    ctx->ct_stats = cs; ctx->ct_any = true;
+    return worst;
 }
 
 }  // namespace
@@ -430,6 +569,21 @@ extern "C" int fv_test_sumprod_rows(fv_ctx *ctx, const int *ob, int T, double *a
 {
     if (!ctx) return FV_ERR_ARG;
     return fvi::drained(ctx, posteriors(ctx, "fv_test_sumprod_rows", ob, T, nullptr, 0, nullptr, nullptr, alpha_out, beta_out));
+}
+
+extern "C" int fv_expected_counts(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq, double *trans_out, long long ld,
+                                  double *emit_out, double *init_out, double *occ_out, double *loglik_out, int *status_out)
+{
+    if (!ctx) return FV_ERR_ARG;
+    return fvi::drained(ctx, expected_counts(ctx, ob, offsets, nseq, trans_out, ld, emit_out, init_out, occ_out, loglik_out, status_out));
+}
+
+extern "C" int fv_last_counts_stats(const fv_ctx *ctx, fv_counts_stats *out)
+{
+    if (!ctx || !out) return FV_ERR_ARG;
+    if (!ctx->ct_any) return FV_ERR_STATE;
+    *out = ctx->ct_stats;
+    return FV_OK;
 }
 
 extern "C" int fv_last_sumprod_stats(const fv_ctx *ctx, fv_sumprod_stats *out)

@@ -106,6 +106,17 @@ class SumprodStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CountsStats(ctypes.Structure):
+    """fv_counts_stats: the last expected_counts call."""
+    _fields_ = [("call_ms", ctypes.c_double), ("gpu_ms", ctypes.c_double), ("sequences", ctypes.c_longlong),
+                ("dead_sequences", ctypes.c_longlong), ("times", ctypes.c_longlong), ("step_launches", ctypes.c_longlong),
+                ("task_steps", ctypes.c_longlong), ("xi_launches", ctypes.c_longlong), ("wide_times", ctypes.c_longlong),
+                ("device_bytes", ctypes.c_longlong)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FlatInfo(ctypes.Structure):
     """fv_flat_info: one right-hand pass of the flat schedule."""
     _fields_ = [("L", ctypes.c_int), ("R", ctypes.c_int), ("generation", ctypes.c_int), ("batch", ctypes.c_int),
@@ -127,7 +138,8 @@ EXPORTS = ["fv_create", "fv_destroy", "fv_set_model", "fv_set_option", "fv_decod
            "fv_streams_open", "fv_streams_push", "fv_streams_push_emissions", "fv_streams_pending", "fv_streams_close",
            "fv_streams_abort", "fv_streams_end", "fv_streams_slot_stats", "fv_streams_last_stats",
            "fv_set_max_lag", "fv_last_lag_stats",
-           "fv_loglik", "fv_loglik_batch", "fv_posteriors", "fv_last_sumprod_stats", "fv_set_sparse_sumprod"]
+           "fv_loglik", "fv_loglik_batch", "fv_posteriors", "fv_last_sumprod_stats", "fv_set_sparse_sumprod",
+           "fv_expected_counts", "fv_last_counts_stats"]
 # include/flashvit_testing.h: hooks for the test suite, not part of the drop-in ABI above
 TEST_EXPORTS = ["fv_test_forward", "fv_test_beam_step", "fv_test_beam_select", "fv_test_device_alloc", "fv_test_device_free",
                 "fv_test_stage_emissions_ms", "fv_test_flat_poison", "fv_test_beam_forward", "fv_test_model_digest",
@@ -234,6 +246,8 @@ def load_library():
     L.fv_last_sumprod_stats.argtypes = [vp, ctypes.POINTER(SumprodStats)]
     L.fv_test_sumprod_rows.argtypes = [vp, vp, ci, vp, vp]
     L.fv_set_sparse_sumprod.argtypes = [vp, ci]
+    L.fv_expected_counts.argtypes = [vp, vp, vp, ci, vp, cll, vp, vp, vp, vp, vp]
+    L.fv_last_counts_stats.argtypes = [vp, ctypes.POINTER(CountsStats)]
     L.fv_test_sumprod_forms.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
     L.fv_test_device_alloc.argtypes = [vp, ctypes.c_size_t, vp, ctypes.POINTER(vp)]
     L.fv_test_device_free.argtypes = [vp, vp]
@@ -741,6 +755,41 @@ class FlashViterbi:
         self._check(self._L.fv_test_sumprod_forms(self._h, ctypes.byref(mask)))
         return int(mask.value)
 
+    # ---- fv_expected_counts: the Baum-Welch E-step in float64
+
+    def expected_counts(self, obs=None, lengths=None, want_trans=True, trans_out=None):
+        """fv_expected_counts: obs is a list of int sequences (lengths >= 1, may differ); obs=None with lengths=[...]: on
+        the staged emission rows, as loglik_batch.  Returns a dict of float64 arrays: trans [K, K] (None with
+        want_trans=False or with trans_out=...), emit [K, M] (None with obs=None), init [K], occ [K], loglik [nseq], and
+        status (int32 [nseq]).  trans_out: a device pointer or (pointer, ld) that receives trans on the device, row pitch
+        ld (default K) in elements.  A sequence of probability 0 reports -inf and ERR_NO_PRED, contributes nothing and
+        does not raise."""
+        ob, ptr, offsets = _batch_arg(obs, lengths)
+        nseq = offsets.size - 1
+        K = self.K
+        trans, tptr, ld = None, None, K
+        if trans_out is not None:
+            tptr, ld = trans_out if isinstance(trans_out, tuple) else (trans_out, K)
+            tptr = ctypes.c_void_p(int(tptr))
+        elif want_trans:
+            trans = np.empty((K, K), dtype=np.float64)
+            tptr = _p(trans)
+        emit = None if ob is None else np.empty((K, self.M), dtype=np.float64)
+        init, occ = np.empty(K, dtype=np.float64), np.empty(K, dtype=np.float64)
+        ll = np.zeros(max(nseq, 1), dtype=np.float64)
+        statuses = np.zeros(max(nseq, 1), dtype=np.int32)
+        rc = self._L.fv_expected_counts(self._h, ptr, _p(offsets), nseq, tptr, int(ld), None if emit is None else _p(emit),
+                                        _p(init), _p(occ), _p(ll), _p(statuses))
+        if rc != ERR_NO_PRED:
+            self._check(rc)
+        return dict(trans=trans, emit=emit, init=init, occ=occ, loglik=ll[:nseq], status=statuses[:nseq])
+
+    def counts_stats(self):
+        """fv_last_counts_stats: a dict of CountsStats' members for the last expected_counts."""
+        s = CountsStats()
+        self._check(self._L.fv_last_counts_stats(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
     def decode_full(self, ob, n_split=1, mode=MODE_REFERENCE, T=None):
         """ob=None with T=...: decode the first T rows staged by set_emissions (so for every decode_* below)."""
         ob, ptr, T = _ob_arg(ob, T)
@@ -960,6 +1009,23 @@ class FlashViterbi:
     def comm_init(self, rank, nranks, unique_id):
         buf = ctypes.create_string_buffer(bytes(unique_id), UNIQUE_ID_BYTES)
         self._check(self._L.fv_comm_init(self._h, rank, nranks, buf))
+
+
+def normalise_rows(counts):
+    """The M-step of one table: every row of float64 counts divided by its sum; an all-zero row stays zero."""
+    counts = np.asarray(counts, dtype=np.float64)
+    total = counts.sum(axis=-1, keepdims=True)
+    return np.divide(counts, total, out=np.zeros_like(counts), where=total > 0)
+
+
+def baum_welch_step(fv, obs):
+    """One EM iteration on the model fv holds: the E-step by fv.expected_counts(obs), the M-step on the host in float64
+    (rows of trans and emit and the vector init normalised, all-zero rows left at zero), then fv.set_model with the float32
+    result.  Returns the summed loglik of obs under the model it was called with."""
+    c = fv.expected_counts(obs)
+    fv.set_model(normalise_rows(c["trans"]).astype(np.float32), normalise_rows(c["emit"]).astype(np.float32),
+                 normalise_rows(c["init"]).astype(np.float32))
+    return float(np.sum(c["loglik"]))
 
 
 def device_count():

@@ -627,6 +627,74 @@ int fv_last_sumprod_stats(const fv_ctx *ctx, fv_sumprod_stats *out);
  * no bit of any result: they are the same as absent entries. */
 int fv_set_sparse_sumprod(fv_ctx *ctx, int on);
 
+/* Baum-Welch E-step accumulators on the device: the expected counts a re-estimation of the model needs,
+ * summed over the sequences of one call.  This is what is now offered of the accumulators the block above leaves out; the
+ * M-step (normalising the rows) is the caller's.
+ *   Definitions, on top of alpha, beta, e and loglik above, all float64.  For one sequence of length T,
+ *     xi_t[i][j] = exp(alpha[t][i] + LA[i][j] + e[t+1][j] + beta[t+1][j] - loglik)   for t = 0 .. T-2,
+ *     g_t[j]     = exp(alpha[t][j] + beta[t][j] - loglik)                            for t = 0 .. T-1.
+ * The sums run over the live sequences s of the call, in sequence order:
+ *     trans_out[i * ld + j] = sum_s sum_t xi_t[i][j]          ld >= K in elements; a host or a device pointer on the
+ *                                                             context's GPU, as gamma_out; beyond K a row is not touched
+ *     emit_out[j * M + m]   = sum_s sum_{t : ob[t] = m} g_t[j]   K x M, host
+ *     init_out[j]           = sum_s g_0[j]                       host
+ *     occ_out[j]            = sum_s sum_t g_t[j]                 host
+ *     loglik_out[s], status_out[s]: as fv_loglik_batch           host
+ * Any output pointer may be NULL.  Outputs are overwritten, not added to.  The offsets contract is fv_loglik_batch's; every
+ * length >= 1 is allowed, and a sequence of length 1 contributes to init, occ and emit only.  ob == NULL works as in
+ * fv_posteriors (sequence s on staged rows offsets[s] .. offsets[s+1], an emission map included); emit_out must then be
+ * NULL, because there is no symbol alphabet (FV_ERR_ARG).  A sequence of probability 0 (loglik = -inf) has status
+ * FV_ERR_NO_PRED and contributes nothing, the others are intact, and the return value is the most negative status.
+ *   Refused before any device work, with a detail text: the argument errors of fv_loglik_batch, ld < K, a trans_out on
+ * another device, a non-NULL emit_out with ob == NULL (FV_ERR_ARG); no model, or an open stream or set (FV_ERR_STATE);
+ * multi-device, partitioned and communicator contexts, and K > 20192 (FV_ERR_UNSUPPORTED); a model set by
+ * fv_set_model_sparse, whether or not fv_set_sparse_sumprod is on (FV_ERR_UNSUPPORTED: the CSR route of the counts is a
+ * follow-up); a working set beyond the free device memory (FV_ERR_NOMEM, with the byte count, before anything is
+ * allocated).  Model entries above 1 and emission scores above 0 are accepted.  fv_last_sumprod_stats and fv_last_stats
+ * keep reporting their own last calls.
+ *   How.  Sequence by sequence the two passes of fv_posteriors run unchanged (the same kernels, the same bits).  A scale
+ * launch then leaves, per time, P[t][i] = exp(alpha[t][i] - a_t) and Q[t][j] = exp(e[t+1][j] + beta[t+1][j] - b_t + w_t),
+ * a_t and b_t the two row maxima and w_t = a_t + b_t - loglik; the xi kernel sums the outer products P[t] Q[t]^T over the
+ * times in registers, one float64 fma per cell and time, and multiplies once by (double)A[i][j]; one kernel sums gamma.
+ * Memory: 32 * T * K bytes for the longest sequence (alpha, beta, P, Q), 8 * K^2 for a host trans_out, 16 * K * M for
+ * emit_out, beside the two tables of fv_posteriors.
+ *   Guarantees.
+ *   G1. Accuracy.  Let R = 3 * tol(T - 1), tol(t) = 2 * (t + 1) * (K + 1024) * u * max(1, Amax) the bound of guarantee 1
+ * above and T the longest sequence of the call: alpha's share, beta's share and loglik's (exp arguments and the sum over
+ * the times sit inside the third).  Every count lies within R * exact + n * 2^-160 of the exact value, n the number of times
+ * summed.  A transition count is exactly 0 where A[i][j] == 0.
+ *   G2. No flush.  A time with w_t above 500 is a wide time: the cells that carry its mass can have P or Q flushed by exp,
+ * so it is left out of the outer product and added per cell in the exact form of the definition (K^2 exp calls for that
+ * time); fv_counts_stats.wide_times counts them.  Below the threshold no term of the linear form that is dropped or
+ * denormalised exceeds 2^-160, for every float32 model entry: a flushed factor is below e^-708, the other at most e^500, the
+ * entry below 2^128, and e^(-708 + 500) * 2^128 < 2^-171.  Ordinary models have wide_times == 0.
+ *   G3. Reproducible bits.  The same call twice gives the same bits.  A batch gives, for every output, bit for bit the
+ * left-to-right float64 sum of the single-sequence calls' outputs (the first term stands alone), whatever FV_OPT_MAX_BATCH
+ * is; loglik_out[s] has the bits of fv_loglik.  Every cell has exactly one owner and a fixed order: times ascending within
+ * a sequence (the ordinary times, then the wide ones), one add of the finished per-sequence value into the accumulator,
+ * sequences in order.  No floating-point atomics anywhere.
+ *   Identities, within G1: sum_j trans[i][j] = occ[i] - sum_s g_{T_s - 1}[i]; sum_ij trans = sum_s (T_s - 1); sum_j init =
+ * the number of live sequences; sum_m emit[j][m] = occ[j].
+ *   Out of scope: CSR-set models, lock-step passes across the sequences of a batch, accumulating across calls, per-time
+ * xi output, multi-device contexts. */
+int fv_expected_counts(fv_ctx *ctx, const int *ob, const long long *offsets, int nseq,
+                       double *trans_out, long long ld, double *emit_out, double *init_out, double *occ_out,
+                       double *loglik_out, int *status_out);
+/* The last fv_expected_counts that ran (FV_ERR_STATE: there never was one). */
+typedef struct {
+    double call_ms;                 /* host wall time of the call (enqueue .. final sync) */
+    double gpu_ms;                  /* HIP-event time from its first to its last kernel */
+    long long sequences;            /* sequences of the call */
+    long long dead_sequences;       /* ... those of probability 0 */
+    long long times;                /* sum of T over the live sequences */
+    long long step_launches;        /* launches of the sum-product step kernel, forward and backward together */
+    long long task_steps;           /* sum over those launches of the tasks advanced by one K * K step */
+    long long xi_launches;          /* launches of the xi kernel: one per sequence of length >= 2 when trans_out is given */
+    long long wide_times;           /* times added in the exact per-cell form (w_t above 500) */
+    long long device_bytes;         /* device working set of the context after the call */
+} fv_counts_stats;
+int fv_last_counts_stats(const fv_ctx *ctx, fv_counts_stats *out);
+
 int fv_last_stats(const fv_ctx *ctx, fv_stats *out);
 const char *fv_strerror(int rc);
 const char *fv_last_error_detail(const fv_ctx *ctx);
